@@ -12,9 +12,12 @@ frames, 32 depth bins, fp32.  Multi-GPU: keyframes are independent, so every ran
 of keyframes (weak scaling, no data-path collective) and the ranks all-gather a tiny per-rank summary
 once at the end of the timed region (RCCL over xGMI).
 
-Prints ONE JSON line on rank 0 with the whole-job keyframes/s, the roofline of the dominant kernel
-(the fp32-MFMA convolution, measured live with HIP events on the launch stream) and - at N=1 - the CPU
-baseline (the oracle port of the reference timed on this box's host cores).
+Prints ONE JSON line on rank 0 with the whole-job keyframes/s (`value`) and `ms_per_step`.  A plain run does
+only that: set-up, warm-up, the K timed steps, the outputs of the last step (--dump-outputs DIR), the line.
+With --full the line also carries everything measured beside the headline: the roofline of the dominant
+kernel (the fp32-MFMA convolution, measured live with HIP events on the launch stream), the 200-step and
+host-primed lines, forward() and - at N=1 - the CPU baseline (the oracle port of the reference timed on
+the host's cores) and the secondary configurations.
 """
 import argparse
 import json
@@ -102,7 +105,47 @@ def parse():
     ap.add_argument("--host-mats", action="store_true",
                     help="keep the 4x4 pose / intrinsics matrices of the resident batch on the host (what kitti.DeviceLoader hands out): "
                          "submit() then never waits for a device-to-host copy of them")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and report the rest: 200-step and host-primed lines, per-launch roofline, forward(), "
+                         "CPU baseline and the secondary configurations (a plain run times the K steps and nothing else)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the output tensors of the last timed step as DIR/<name>.npy (float32; integer outputs float64), "
+                         f"at most {DUMP_BUDGET_BYTES // 10**6} MB in all: over that budget the largest outputs are a fixed, seeded sample of their elements")
+    args = ap.parse_args()
+    if args.dump_layers and not args.full:
+        ap.error("--dump-layers needs --full (the per-launch timing passes run only there)")
+    return args
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6            # array data; the .npy headers stay well inside 64 MB
+
+
+def dump_outputs(out, inputs, path):
+    """The arrays a caller of the timed path receives from the last step (every tensor-valued key of the output dict that is not an
+    input or a host timing; a list of tensors as <name>_<i>), as float32 (float64 for integer tensors).  When they exceed
+    DUMP_BUDGET_BYTES the budget is shared out from the smallest array up: an array larger than its share is written as the
+    elements at a sorted, seeded sample of its flat indices (seed 0, the same indices in every run of the same shape)."""
+    import numpy as np
+    arrays = []
+    for key, v in out.items():
+        if key in inputs or key == "cv_module_time":       # cv_module_time: a wall-clock duration (as in the reference), not a result
+            continue
+        if torch.is_tensor(v):
+            arrays.append((key, v))
+        elif isinstance(v, (list, tuple)) and v and all(torch.is_tensor(t) for t in v):
+            arrays.extend((f"{key}_{i}", t) for i, t in enumerate(v))
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES
+    arrays.sort(key=lambda kv: kv[1].numel())
+    for n, (name, t) in enumerate(arrays):
+        a = t.detach().cpu()
+        a = (a.float() if a.is_floating_point() else a.double()).numpy()
+        cap = budget // (len(arrays) - n) // a.itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        budget -= a.nbytes
 
 
 def time_layers(model, batch_dev, plan_key, reps=9):
@@ -768,9 +811,11 @@ def main():
     total_keyframes = float(sum(g[0].item() for g in gathered))
     if args.primer:
         return
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, batch_dev, args.dump_outputs)      # before anything else reuses the slot buffers that hold them
 
     value_200 = None
-    if world == 1 and args.steps < 200 and not args.no_forward_api:
+    if args.full and world == 1 and args.steps < 200 and not args.no_forward_api:
         # the same loop over 200 timed steps, driver-timed too (20 steps = 30 ms are inside the spread of a fresh box;
         # the builder's 200-step lines are consistently higher) - a secondary key, `value` stays the K steps the driver asked for
         torch.cuda.synchronize()
@@ -781,7 +826,7 @@ def main():
         torch.cuda.synchronize()
         value_200 = 200 * args.batch / (time.perf_counter() - t200)
     value_primed = None
-    if world == 1 and args.host_prime_ms <= 0 and not args.no_forward_api:
+    if args.full and world == 1 and args.host_prime_ms <= 0 and not args.no_forward_api:
         # round 4's headline regime as a SECONDARY key: the same K steps once more, preceded by 3 ms of prepare() calls (pose algebra of a
         # request; no forward) between the closing synchronize() and the timed region - a benchmark-only step no caller performs
         torch.cuda.synchronize()
@@ -795,7 +840,10 @@ def main():
         drain()
         torch.cuda.synchronize()
         value_primed = args.steps * args.batch / (time.perf_counter() - tp0)
-    if rank == 0:
+    shape = (args.batch, args.height, args.width, args.frames, args.depths)
+    cfg_name = {(1, 256, 512, 2, 32): "c2 (BASELINE configs[1])", (8, 256, 512, 4, 64): "c3 (BASELINE configs[2])",
+                (1, 512, 1024, 4, 48): "c5 shape (BASELINE configs[4]: 512x1024, 4 source frames, 48 bins)"}.get(shape, "custom")
+    if rank == 0 and args.full:
         plan_key = next(iter(model._plans))
         rows = time_layers(model, batch_dev, plan_key)
         conv_rows = [r for r in rows if r["macs"] > 0]
@@ -804,7 +852,6 @@ def main():
         conv_flops_executed = 2.0 * sum(r["macs"] for r in conv_rows)   # what the launches execute (phase-decomposed Upconv: 9/16)
         achieved = conv_flops / conv_s / 1e12
         cv_row = next(r for r in rows if r["name"] == "cost_volume")
-        shape = (args.batch, args.height, args.width, args.frames, args.depths)
         fp32 = not (args.bf16 or args.bf16x3)
         cfg_tag = {(1, 256, 512, 2, 32): "c2", (8, 256, 512, 4, 64): "c3"}.get(shape) if (fp32 and not args.cv_separable) else None
         if args.bf16 and shape == (1, 512, 1024, 4, 48) and not args.lean_outputs:
@@ -813,8 +860,6 @@ def main():
         current, stamp_info = profile_is_current(cfg_tag, model._plans[plan_key].launch_stamp()) if cfg_tag else (False, None)
         pmc, pmc_src = committed_pmc(cfg_tag) if (cfg_tag and current) else ({}, None)
         kst, kst_src = committed_kernel_stats(cfg_tag) if (cfg_tag and current) else (None, None)
-        cfg_name = {(1, 256, 512, 2, 32): "c2 (BASELINE configs[1])", (8, 256, 512, 4, 64): "c3 (BASELINE configs[2])",
-                    (1, 512, 1024, 4, 48): "c5 shape (BASELINE configs[4]: 512x1024, 4 source frames, 48 bins)"}.get(shape, "custom")
         cv_bytes = 4.0 * args.batch * args.height * args.width * (3 + args.depths) * (1 + args.frames)
         peak = BF16_MFMA_PEAK_TFLOPS if args.bf16 else FP32_MFMA_PEAK_TFLOPS
         VALU_PEAK = 78.6e12          # lane-instructions / s: 1024 SIMD-32 x 2.4 GHz (MI355X_MICROARCH.md)
@@ -949,6 +994,22 @@ def main():
             aux_bytes += 4.0 * args.batch * hw_ * (1 + 2 * args.depths)
         if any(r["name"] == "depth.heads" for r in rows):
             aux_bytes += 4.0 * args.batch * hw_ * (1 + 1 / 4 + 1 / 16 + 1 / 64)
+        full_keys = {
+            "roofline": roof,
+            "cost_volume_kernel": cv_block,
+            "one_channel_layers": {"kernels": "mask_classifier_kernel (+ mask multiply), depth_heads_kernel (csrc/heads.hip): HBM-bound, "
+                                              "not part of the MFMA roofline above",
+                                   "launches": [r["name"] for r in rows if r.get("aux_ref_macs")],
+                                   "algorithmic_gflop_per_step": 2.0 * sum(r.get("aux_ref_macs", 0) for r in rows) / 1e9,
+                                   "algorithmic_MB_per_step": aux_bytes / 1e6,
+                                   "us_per_step": aux_s * 1e6,
+                                   "achieved_GBps": (aux_bytes / aux_s / 1e9) if aux_s > 0 else None, "peak_GBps": 8000.0,
+                                   "hbm_frac": (aux_bytes / aux_s / 8e12) if aux_s > 0 else None,
+                                   "note": "bytes = inputs once + outputs once (+ the cost volume read and written by the mask multiply); "
+                                           "at batch 1 both launches are latency chains (launch floor ~6 us each), not bandwidth"},
+            "device_ms_per_step_sum_of_kernels": sum(r["seconds"] for r in rows) * 1e3,
+        }
+    if rank == 0:
         result = {
             "metric": "frames/sec (keyframes/s), KITTI 256x512 2-src/32-bin cost-volume inference",
             "value": total_keyframes / elapsed,
@@ -987,32 +1048,20 @@ def main():
                        "env_overrides": engine_env_overrides(),
                        "env_overrides_note": "kernel-selection environment overrides active in this process (monorec_amd.engine.ENV_OVERRIDES: candidate tables, A/B switches, the diagnostic library); {} = the committed tables and defaults",
                        "parallelism": f"dp{world} (independent keyframes per rank)"},
-            "roofline": roof,
-            "cost_volume_kernel": cv_block,
-            "one_channel_layers": {"kernels": "mask_classifier_kernel (+ mask multiply), depth_heads_kernel (csrc/heads.hip): HBM-bound, "
-                                              "not part of the MFMA roofline above",
-                                   "launches": [r["name"] for r in rows if r.get("aux_ref_macs")],
-                                   "algorithmic_gflop_per_step": 2.0 * sum(r.get("aux_ref_macs", 0) for r in rows) / 1e9,
-                                   "algorithmic_MB_per_step": aux_bytes / 1e6,
-                                   "us_per_step": aux_s * 1e6,
-                                   "achieved_GBps": (aux_bytes / aux_s / 1e9) if aux_s > 0 else None, "peak_GBps": 8000.0,
-                                   "hbm_frac": (aux_bytes / aux_s / 8e12) if aux_s > 0 else None,
-                                   "note": "bytes = inputs once + outputs once (+ the cost volume read and written by the mask multiply); "
-                                           "at batch 1 both launches are latency chains (launch floor ~6 us each), not bandwidth"},
-            "device_ms_per_step_sum_of_kernels": sum(r["seconds"] for r in rows) * 1e3,
+            **(full_keys if args.full else {}),
         }
         if value_200 is not None:
             result["value_200_steps"] = value_200
         if value_primed is not None:
             result["value_host_primed"] = value_primed
             result["value_host_primed_note"] = "secondary: the same K steps timed after 3 ms of prepare() calls between the closing synchronize() and the timed region (round 4's headline regime); `value` has nothing in between"
-        if world == 1 and not args.no_forward_api:
+        if args.full and world == 1 and not args.no_forward_api:
             result["forward_api"] = forward_api(model, batch_dev, args.batch)
         if args.dump_layers:
             os.makedirs(os.path.dirname(os.path.abspath(args.dump_layers)), exist_ok=True)
             with open(args.dump_layers, "w") as f:
                 json.dump(rows, f, indent=1)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             base, ref = cpu_baseline(sd, batch_cpu, args.depths)
             result["cpu_baseline"] = base
             with torch.no_grad():

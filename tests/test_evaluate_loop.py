@@ -200,7 +200,7 @@ def test_bench_multi_rank_branch_with_two_ranks_on_one_device(hip_lib, tmp_path)
     env = dict(os.environ, MR_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "40", "--warmup", "5",
-           "--spinup-seconds", "1.0", "--height", "128", "--width", "256", "--depths", "16", "--no-cpu-baseline"]
+           "--spinup-seconds", "1.0", "--height", "128", "--width", "256", "--depths", "16", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Where the wall time of ONE keyframe goes when nothing overlaps it (VERDICT r4 next #1a): from a rocprofv3 kernel trace (csv) of
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python bench.py --steps 40 --in-flight 1 --single-stream --no-cpu-baseline --no-primer --no-forward-api
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o t -- python bench.py --full --steps 40 --in-flight 1 --single-stream --no-cpu-baseline --no-primer --no-forward-api
 
 take the steady-state keyframes (one cost-volume sad launch each), and per launch position within the keyframe report the kernel, its
 median duration and the median GAP in front of it (start - end of the previous launch on the device: dispatch latency of a dependent launch,
