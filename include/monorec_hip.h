@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 19
+#define MR_ABI_VERSION 20
 
 #define MR_COMPUTE_F32  0
 #define MR_COMPUTE_BF16 1
@@ -572,6 +572,51 @@ int mr_depth_heads_f32(const mr_head_desc* heads, int32_t num_heads, float act_p
  * sum(log dp - log dg)^2, n(thresh<1.25), n(thresh<1.25^2), n(thresh<1.25^3)]. */
 int mr_sparse_metric_sums_f32(const float* prediction, const float* target, int32_t batch, int32_t height,
                               int32_t width, const int32_t* roi, float max_distance, double* sums, void* stream);
+
+/* ---- median scaling and the dense-target metrics (evaluater/evaluater.py:36-43, utils/util.py:135-142,
+ *      model/metric_functions/sparse_metrics.py:6-78) ------------------------------------------------------------
+ *
+ * Per-sample exact masked order statistics, mask = target > 0 over the whole (uncropped) image, one entry per sample:
+ *   count          selection size
+ *   target_median  lower median sorted[(count-1)/2] of target[mask] (torch.median); NaN when count == 0
+ *   lo, hi         prediction[mask] sorted[(count-1)/2] and sorted[count/2]; NaN when count == 0
+ *   nans, zeros, infs  number of NaN, +-0 and +-inf values in prediction[mask] (after mr_median_stage_scales_f32: non-zero
+ *                  = present).  The values are only defined when nans == 0. */
+typedef struct {
+    int32_t count;
+    float target_median;
+    float lo, hi;
+    int32_t nans, zeros, infs;
+    int32_t reserved;
+} mr_median_stats;
+
+/* Bytes of device workspace mr_median_select_f32 needs: the compacted selections (2 x batch x height x width x 4). */
+int64_t mr_median_select_workspace_bytes(int32_t batch, int32_t height, int32_t width);
+
+/* Radix select over order-preserving keys of the fp32 bit patterns, integer LDS histograms: exact and deterministic.
+ * prediction/target (batch,1,H,W); stats: batch entries on the device.  One workgroup per (sample, tensor). */
+int mr_median_select_f32(const float* prediction, const float* target, int32_t batch, int32_t height, int32_t width,
+                         void* workspace, mr_median_stats* stats, void* stream);
+
+/* The reference's median_scaling applied num_stages times in a row (once per configured metric, evaluater.py:40-43):
+ * scales[b * num_stages + j] = median(target) / median(prediction after stages 0..j-1) in fp32, each stage multiplying
+ * the prediction by its ratio.  Derived from the stats by the exact recurrence (a positive ratio keeps the order of the
+ * selection, a negative one reverses it; a 0 / inf ratio meeting an inf / 0 makes the selection NaN).  stats_out (may be
+ * NULL or alias stats) receives the statistics after the last stage.  One wave, no host synchronisation. */
+int mr_median_stage_scales_f32(const mr_median_stats* stats, int32_t batch, int32_t num_stages, float* scales,
+                               mr_median_stats* stats_out, void* stream);
+
+#define MR_MAX_METRIC_STAGES 16
+#define MR_METRIC_DENSE 0x100   /* or-ed into a stage column: the dense-target form (no mask, sparse_metrics.py:6-78) */
+
+/* One pass over prediction and target for up to MR_MAX_METRIC_STAGES metric evaluations.  Stage j multiplies the
+ * prediction by scales[b * num_stages + j] (fp32, after the multiplies of stages 0..j-1; scales NULL = no scaling) and
+ * feeds the sum of column stage_columns[j] & 0xff (1..7, the layout of mr_sparse_metric_sums_f32), masked like that
+ * entry point or, with MR_METRIC_DENSE, over every pixel of the roi.  relu / clamp_min keep NaN like torch.
+ * sums: batch x (2 + num_stages) doubles on the device: [#valid (sparse mask), #pixels of the roi, stage 0, ...]. */
+int mr_metric_stage_sums_f32(const float* prediction, const float* target, int32_t batch, int32_t height, int32_t width,
+                             const int32_t* roi, float max_distance, const float* scales, int32_t num_stages,
+                             const int32_t* stage_columns, double* sums, void* stream);
 
 /* ---- point-cloud path: create_pointcloud.py + utils/ply_utils.py -------------------------------
  *

@@ -88,7 +88,7 @@ class B8ConvDesc(ctypes.Structure):
 
 
 MR_MAX_COPY_SEGMENTS = 24
-MR_ABI_VERSION = 19            # include/monorec_hip.h
+MR_ABI_VERSION = 20            # include/monorec_hip.h
 
 
 class CopySegment(ctypes.Structure):
@@ -223,6 +223,14 @@ ABI = {
     "mr_sparse_metric_sums_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
                                                  ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_float,
                                                  ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_median_select_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "mr_median_select_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_median_stage_scales_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p]),
+    "mr_metric_stage_sums_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_float, ctypes.c_void_p, ctypes.c_int32,
+                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p]),
     "mr_static_mask_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]),
     "mr_pointcloud_append_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,

@@ -23,6 +23,7 @@ SOURCES = [
     ("pointcloud.hip", ["-ffp-contract=off"]),
     ("preprocess.hip", ["-ffp-contract=off"]),
     ("eltwise.hip", []),
+    ("select.hip", ["-ffp-contract=off"]),          # median scaling: exact masked selection; stage-scaled metric sums
     ("heads.hip", []),
     ("conv_wino.hip", []),
     ("convt_wino.hip", []),

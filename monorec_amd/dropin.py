@@ -11,6 +11,8 @@ directory / sys.path must be the reference checkout) and rebinds exactly these n
 
     model.model.MonoRecModel, model.monorec.monorec_model.MonoRecModel   -> monorec_amd.MonoRecModel
     model.metric.<the seven sparse metrics of eval_monorec.json:53-61>    -> monorec_amd.metrics.<same name>
+    model.metric.<the seven dense-target metrics, a1_metric .. sq_rel_metric> -> monorec_amd.metrics.<same name>
+    utils.median_scaling, utils.util.median_scaling                       -> monorec_amd.metrics.median_scaling
     utils.PLYSaver, utils.ply_utils.PLYSaver                              -> monorec_amd.pointcloud.PLYSaver
 
 Nothing else of the reference is touched (data loaders, config parser, Evaluater stay the reference's own code) - unless asked:
@@ -50,8 +52,13 @@ def install(model=True, metrics=True, pointcloud=True, data_loader=False):
                               "checkout (or put it on sys.path)")
     if metrics:
         from . import metrics as hip_metrics
-        for name in hip_metrics.SPARSE_METRICS:
+        for name in hip_metrics.SPARSE_METRICS + hip_metrics.DENSE_METRICS:
             _rebind("model.metric", name, getattr(hip_metrics, name))
+        # evaluater/evaluater.py:7 does `from utils import median_scaling`: bound here, before the script imports evaluater
+        _rebind("utils.util", "median_scaling", hip_metrics.median_scaling)
+        _rebind("utils", "median_scaling", hip_metrics.median_scaling)
+        if "evaluater.evaluater" in sys.modules:           # imported already (not by the reference's scripts): rebind its copy too
+            _rebind("evaluater.evaluater", "median_scaling", hip_metrics.median_scaling)
     if pointcloud:
         from .pointcloud import PLYSaver
         _rebind("utils.ply_utils", "PLYSaver", PLYSaver)

@@ -41,7 +41,7 @@ def evaluation_log(per_batch_metrics, batch_sizes):
 
 
 class Evaluater:
-    """`Evaluater(model, roi=, max_distance=).eval(data_loader)` -> the reference's log dict (without the loss entries,
+    """`Evaluater(model, roi=, max_distance=, metric_names=, median_scaling=).eval(data_loader)` -> the reference's log dict (without the loss entries,
     which are constant zero there, evaluater.py:85-86).  `data_loader` yields `(data_dict, target)` like the reference's
     loaders; tensors may live on the host (they are moved) or already on the model's device.
 
@@ -53,17 +53,31 @@ class Evaluater:
     (`evaluation_log`: NaN batch => invalid, mean over valid batches, batch-size-weighted running mean, evaluater.py:45-49,
     94-118) then runs on the index-sorted union, so the log equals the single-process log bit for bit on every rank."""
 
-    def __init__(self, model, roi=None, max_distance=None, metric_names=_metrics.SPARSE_METRICS, in_flight=None, sums_fn=None):
-        unknown = [m for m in metric_names if m not in _metrics.SPARSE_METRICS]
+    def __init__(self, model, roi=None, max_distance=None, metric_names=_metrics.SPARSE_METRICS, in_flight=None, sums_fn=None,
+                 median_scaling=False):
+        unknown = [m for m in metric_names if m not in _metrics.SPARSE_METRICS + _metrics.DENSE_METRICS]
         if unknown:
-            raise NotImplementedError(f"metrics outside the fused sparse set: {unknown}")
+            raise NotImplementedError(f"metrics outside the fused sparse and dense-target sets: {unknown}")
         self.model, self.roi, self.max_distance = model, roi, max_distance
         self.metric_names = tuple(metric_names)
-        self._cols = [_metrics.SPARSE_METRICS.index(m) for m in self.metric_names]
+        self.median_scaling = bool(median_scaling)
+        # median scaling (evaluater.py:36,40-43) or a dense-target metric: the staged reduction, one sum column per metric in
+        # config order (with median scaling metric j sees the prediction rescaled j + 1 times); otherwise the fused sparse sums
+        self._staged = self.median_scaling or any(m in _metrics.DENSE_METRICS for m in self.metric_names)
+        if self._staged:
+            if len(self.metric_names) > _metrics.MAX_STAGES:
+                raise NotImplementedError(f"more than {_metrics.MAX_STAGES} metrics in one evaluation")
+            self._columns = tuple(_metrics.stage_column(m) for m in self.metric_names)
+            self._cols = list(range(len(self.metric_names)))
+        else:
+            self._cols = [_metrics.SPARSE_METRICS.index(m) for m in self.metric_names]
         # forwards kept in flight: never more than the model has slots - a deeper queue would let submit() reuse a slot whose
         # resident `result` has not been reduced yet (the metric launch would then read the wrong keyframe's prediction)
         slots = int(getattr(model, "hip_in_flight", in_flight or 2))
         self.in_flight = max(1, min(int(in_flight) if in_flight is not None else slots, slots))      # default: every slot of the model
+        if sums_fn is None and self._staged:
+            cols, ms = self._columns, self.median_scaling
+            sums_fn = lambda data, roi, dist: _metrics.staged_metric_sums_device(data, cols, roi, dist, ms)   # noqa: E731
         self._sums_fn = sums_fn or _metrics.sparse_metric_sums_device   # (B, 8) per-sample sums; injectable for host-logic tests
 
     # the 4x4 matrices feed the model's HOST-side pose algebra (model.host_geometry): moved to the device they would have to come back,
@@ -117,7 +131,7 @@ class Evaluater:
         if sums:
             host = [s.cpu() for s in sums] if len({tuple(s.shape) for s in sums}) > 1 else list(torch.stack(sums).cpu())
             for s in host:
-                vals = _metrics.metrics_from_sums(s)
+                vals = _metrics.metrics_from_stage_sums(s, self._columns) if self._staged else _metrics.metrics_from_sums(s)
                 per_batch.append([float(vals[c]) for c in self._cols])
         if distributed and _dist.group_active():      # also a one-rank group: the collective is the code path under test there
             per_batch, sizes, indices = _dist.gather_batch_records(per_batch, sizes, indices, len(self._cols))

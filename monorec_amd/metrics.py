@@ -37,6 +37,8 @@ def sparse_metric_sums_device(data_dict, roi=None, max_distance=None, pred_all_v
     assert gt.shape == pred.shape
     sums = torch.empty(b, 8, dtype=torch.float64, device=pred.device)
     roi_arr = (ctypes.c_int32 * 4)(*[int(v) for v in roi]) if roi is not None else None
+    if _MEDIAN_KEY in data_dict:     # a median_scaling() result: relu / clamp_min keep NaN there, like the reference (a NaN ratio)
+        return metric_stage_sums_device(pred, gt, tuple(range(1, 8)), roi, max_distance)[:, [0] + list(range(2, 9))]
     stream = torch.cuda.current_stream(pred.device).cuda_stream
     _lib.check(lib.mr_sparse_metric_sums_f32(pred.data_ptr(), gt.data_ptr(), b, h, w, roi_arr,
                                              float(max_distance) if max_distance else 0.0, sums.data_ptr(), stream),
@@ -119,3 +121,165 @@ _variants()
 
 SPARSE_METRICS = ("abs_rel_sparse_metric", "sq_rel_sparse_metric", "rmse_sparse_metric", "rmse_log_sparse_metric",
                   "a1_sparse_metric", "a2_sparse_metric", "a3_sparse_metric")     # configs/evaluate/eval_monorec.json:53-61
+
+
+# ---- median scaling and the dense-target metrics (evaluater/evaluater.py:36-43, utils/util.py:135-142, sparse_metrics.py:6-78) ----
+
+DENSE_METRICS = ("abs_rel_metric", "sq_rel_metric", "rmse_metric", "rmse_log_metric", "a1_metric", "a2_metric", "a3_metric")
+MAX_STAGES = 16                 # MR_MAX_METRIC_STAGES
+_DENSE = 0x100                  # MR_METRIC_DENSE
+_MEDIAN_KEY = "_monorec_amd_median_stats"
+_DENSE_KEY = "_monorec_amd_dense_sums"
+_STATS_FIELDS = 8               # mr_median_stats: count, target_median, lo, hi, nans, zeros, infs, reserved (4 bytes each)
+
+
+def stage_column(name):
+    """Column of mr_metric_stage_sums_f32 for a metric name: 1..7 (the mr_sparse_metric_sums_f32 layout), | MR_METRIC_DENSE."""
+    if name in SPARSE_METRICS:
+        return SPARSE_METRICS.index(name) + 1
+    if name in DENSE_METRICS:
+        return (DENSE_METRICS.index(name) + 1) | _DENSE
+    raise NotImplementedError(f"no fused form of {name}")
+
+
+def _device_pair(data_dict):
+    pred, gt = data_dict["result"], data_dict["target"]
+    if not pred.is_cuda:
+        raise RuntimeError("monorec_amd.metrics needs result/target on a HIP device; there is no CPU path")
+    assert gt.shape == pred.shape
+    return pred.contiguous().float(), gt.contiguous().float()
+
+
+def median_stats_device(pred, gt):
+    """(B, 8) int32 DEVICE tensor holding one mr_median_stats per sample (view the float fields with .view(torch.float32)):
+    exact lower median of target[target > 0], prediction order statistics sorted[(n-1)//2], sorted[n//2] over the same mask,
+    NaN / zero / inf counts.  One launch, no host synchronisation."""
+    lib = _lib.load()
+    b, _, h, w = pred.shape
+    ws = torch.empty(int(lib.mr_median_select_workspace_bytes(b, h, w)), dtype=torch.uint8, device=pred.device)
+    stats = torch.empty(b, _STATS_FIELDS, dtype=torch.int32, device=pred.device)
+    stream = torch.cuda.current_stream(pred.device).cuda_stream
+    _lib.check(lib.mr_median_select_f32(pred.data_ptr(), gt.data_ptr(), b, h, w, ws.data_ptr(), stats.data_ptr(), stream),
+               "mr_median_select_f32")
+    return stats
+
+
+def median_stage_scales_device(stats, num_stages):
+    """(B, num_stages) float32 ratios of num_stages median_scaling calls in a row and the (B, 8) statistics after them."""
+    lib = _lib.load()
+    b = stats.shape[0]
+    scales = torch.empty(b, num_stages, dtype=torch.float32, device=stats.device)
+    after = torch.empty_like(stats)
+    stream = torch.cuda.current_stream(stats.device).cuda_stream
+    _lib.check(lib.mr_median_stage_scales_f32(stats.data_ptr(), b, num_stages, scales.data_ptr(), after.data_ptr(), stream),
+               "mr_median_stage_scales_f32")
+    return scales, after
+
+
+def metric_stage_sums_device(pred, gt, columns, roi=None, max_distance=None, scales=None):
+    """(B, 2 + k) float64 DEVICE sums of mr_metric_stage_sums_f32: [#valid, #roi pixels, stage 0, ..., stage k-1]."""
+    if not 1 <= len(columns) <= MAX_STAGES:
+        raise NotImplementedError(f"{len(columns)} metrics in one pass (at most {MAX_STAGES})")
+    lib = _lib.load()
+    b, _, h, w = pred.shape
+    sums = torch.empty(b, 2 + len(columns), dtype=torch.float64, device=pred.device)
+    roi_arr = (ctypes.c_int32 * 4)(*[int(v) for v in roi]) if roi is not None else None
+    cols = (ctypes.c_int32 * len(columns))(*columns)
+    stream = torch.cuda.current_stream(pred.device).cuda_stream
+    _lib.check(lib.mr_metric_stage_sums_f32(pred.data_ptr(), gt.data_ptr(), b, h, w, roi_arr,
+                                            float(max_distance) if max_distance else 0.0,
+                                            None if scales is None else scales.data_ptr(), len(columns), cols, sums.data_ptr(),
+                                            stream), "mr_metric_stage_sums_f32")
+    return sums
+
+
+def staged_metric_sums_device(data_dict, columns, roi=None, max_distance=None, median_scaling=False):
+    """One Evaluater batch: (B, 2 + k) float64 device sums of the k configured metrics (stage_column codes, config order).
+    With median_scaling, metric j sees the prediction rescaled j + 1 times (evaluater.py:40-43): one selection launch, one
+    single-wave launch for the ratios, one reduction launch; no host synchronisation."""
+    pred, gt = _device_pair(data_dict)
+    scales = median_stage_scales_device(median_stats_device(pred, gt), len(columns))[0] if median_scaling else None
+    return metric_stage_sums_device(pred, gt, columns, roi, max_distance, scales)
+
+
+def metrics_from_stage_sums(s, columns):
+    """The k metric values of one batch from its (B, 2 + k) CPU float64 stage sums."""
+    out = []
+    for j, c in enumerate(columns):
+        t = torch.stack([s[:, 1] if c & _DENSE else s[:, 0], s[:, 2 + j]], 1)
+        out.append(_per_sample_rms(t, 1) if (c & 0xff) in (3, 4) else _batch_ratio(t, 1))
+    return out
+
+
+def stage_ratios_host(count, target_median, lo, hi, nans, zeros, infs, num_stages):
+    """Host mirror (numpy float32) of mr_median_stage_scales_f32: the ratios of num_stages median_scaling calls in a row."""
+    import numpy as np
+    f = np.float32
+    tm, lo, hi = f(target_median), f(lo), f(hi)
+    nan = bool(nans) or count == 0
+    out = []
+    with np.errstate(all="ignore"):
+        for _ in range(num_stages):
+            r = f("nan") if nan else tm / lo
+            out.append(r)
+            if np.isnan(r) or (r == 0 and infs) or (np.isinf(r) and zeros):
+                nan = True
+                continue
+            a, c = lo * r, hi * r
+            lo, hi = (c, a) if np.signbit(r) else (a, c)
+            if r == 0:
+                zeros, infs = count, 0
+            elif np.isinf(r):
+                zeros, infs = 0, count
+    return out
+
+
+def _key(t):
+    return (t.data_ptr(), t._version)
+
+
+def median_scaling(data_dict):
+    """utils/util.py:135-142: a NEW dict whose "result" is the prediction times median(target[mask]) / median(prediction[mask])
+    per sample (mask = target > 0 over the whole image), the same fp32 multiply by the same ratio as the reference.  The
+    selected statistics ride along on the returned dict: calling median_scaling on it again (evaluater.py:40-43 does, once per
+    metric) derives the next ratio from them on the device instead of selecting again."""
+    pred, gt = data_dict["result"], data_dict["target"]
+    if not pred.is_cuda:
+        raise RuntimeError("monorec_amd.metrics needs result/target on a HIP device; there is no CPU path")
+    cached = data_dict.get(_MEDIAN_KEY)
+    if cached is not None and cached[0] == (_key(pred), _key(gt)):
+        stats = cached[1]
+    else:
+        stats = median_stats_device(*_device_pair(data_dict))
+    scales, after = median_stage_scales_device(stats, 1)
+    out = dict(data_dict)
+    out["result"] = pred * scales.view(-1, 1, 1, 1)
+    out[_MEDIAN_KEY] = ((_key(out["result"]), _key(gt)), after)
+    return out
+
+
+def dense_metric_sums(data_dict, roi=None, max_distance=None):
+    """(B, 9) float64 CPU stage sums of the seven dense-target metrics (DENSE_METRICS order), one launch per data dict."""
+    pred, gt = data_dict["result"], data_dict["target"]
+    if not pred.is_cuda:
+        raise RuntimeError("monorec_amd.metrics needs result/target on a HIP device; there is no CPU path")
+    key = (_key(pred), _key(gt), None if roi is None else tuple(roi), max_distance)
+    cached = data_dict.get(_DENSE_KEY)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    p, g = _device_pair(data_dict)
+    out = metric_stage_sums_device(p, g, tuple(c | _DENSE for c in range(1, 8)), roi, max_distance).cpu()
+    data_dict[_DENSE_KEY] = (key, out)
+    return out
+
+
+def _dense_metric(col):
+    def metric(data_dict, roi=None, max_distance=None):
+        s = dense_metric_sums(data_dict, roi, max_distance)
+        t = torch.stack([s[:, 1], s[:, 1 + col]], 1)
+        return _per_sample_rms(t, 1) if col in (3, 4) else _batch_ratio(t, 1)
+    metric.__name__ = metric.__qualname__ = DENSE_METRICS[col - 1]
+    return metric
+
+
+abs_rel_metric, sq_rel_metric, rmse_metric, rmse_log_metric, a1_metric, a2_metric, a3_metric = (_dense_metric(c) for c in range(1, 8))

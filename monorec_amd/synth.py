@@ -90,6 +90,33 @@ def make_depth_pair(batch=2, height=64, width=96, seed=7, valid_fraction=0.18):
     return pred.contiguous(), (gt * keep).contiguous()
 
 
+MEDIAN_SCALING_VARIANTS = ("plain", "ties", "empty", "nan_pred", "zero_median", "negative", "dense")
+
+
+def make_median_scaling_pair(batch, height, width, seed, variant="plain"):
+    """(prediction, target) for median scaling (utils/util.py:135-142), seeded, reproducible anywhere.  Variants:
+    plain (make_depth_pair), ties (both quantised: many equal values), empty (last sample without a valid target: NaN ratio),
+    nan_pred (a NaN prediction at a valid pixel of sample 0), zero_median (sample 0 predicts 0 on ~60 % of the pixels: an
+    infinite ratio, then NaN), negative (last sample negated on ~70 % of the pixels: a negative ratio), dense (every pixel valid)."""
+    if variant not in MEDIAN_SCALING_VARIANTS:
+        raise ValueError(variant)
+    pred, gt = make_depth_pair(batch, height, width, seed, valid_fraction=1.0 if variant == "dense" else 0.18)
+    g = torch.Generator().manual_seed(seed + 1000)
+    if variant == "ties":
+        pred = torch.clamp_min(torch.round(pred * 64) / 64, 1 / 64)
+        gt = torch.where(gt > 0, torch.ceil(gt * 32) / 32, torch.zeros_like(gt))
+    elif variant == "empty":
+        gt[-1] = 0
+    elif variant == "nan_pred":
+        first = int(torch.nonzero(gt[0].flatten() > 0)[0])
+        pred[0].view(-1)[first] = float("nan")
+    elif variant == "zero_median":
+        pred[0] = torch.where(torch.rand(pred[0].shape, generator=g) < 0.6, torch.zeros_like(pred[0]), pred[0])
+    elif variant == "negative":
+        pred[-1] = torch.where(torch.rand(pred[-1].shape, generator=g) < 0.7, -pred[-1], pred[-1])
+    return pred.contiguous(), gt.contiguous()
+
+
 def make_metric_flag_inputs(batch, height, width, seed):
     """(prediction with exact zeros on ~10 % of the pixels, sparse target, moving-object mask) for the `pred_all_valid=False` /
     `use_cvmask=True` options of the sparse metrics (sparse_metrics.py:81-212) - seeded, reproducible anywhere."""
