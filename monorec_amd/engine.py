@@ -16,8 +16,11 @@ Because nothing in a stage allocates or synchronises, each stage can be recorded
 ~100 Python-driven launches.  The 4x4 pose algebra (:171,198,207) runs on the host between the two
 stages, overlapped with the encoder stage (see MonoRecModel._forward_hip).
 """
+import collections
 import ctypes
+import json
 import math
+import os
 import re
 
 import numpy as np
@@ -37,24 +40,33 @@ def same_pad(n, k, s):
     return math.floor(total / 2), math.ceil(total / 2)
 
 
+def _int32s(values):
+    return (ctypes.c_int32 * len(values))(*values)
+
+
+def pack_weights(count, pack, weight, *args, dtype=torch.float32):
+    """`weight` (fp32 CPU copy) through a (count, pack) pair of C-ABI entries: count(*args) elements of `dtype`, then pack(weight, *args, out);
+    returns `out` (CPU).  args: (cout, int32 source channels, number of sources, the entry pair's own parameters)."""
+    lib = _lib.load()
+    w = weight.detach().to(torch.float32).contiguous().cpu()
+    n = getattr(lib, count)(*args)
+    assert n > 0, (count, args[3:])
+    out = torch.empty(n, dtype=dtype)
+    _lib.check(getattr(lib, pack)(w.data_ptr(), *args, out.data_ptr()), pack)
+    return out
+
+
 def pack_conv_weight(weight, src_channels, mb, ck, bf16=False):
     """(Cout, sum(src_channels), kh, kw) fp32 CPU tensor -> packed A-fragment stream (CPU tensor) for a
     launch with `mb` cout blocks per workgroup and `ck` channels per LDS chunk (csrc/conv_layout.h);
     bf16 = compute mode: 0 / False fp32, 1 / True the bf16 stream of MR_COMPUTE_BF16 launches, 2 the hi / lo bf16 pairs of
     MR_COMPUTE_BF16X3."""
-    lib = _lib.load()
-    w = weight.detach().to(torch.float32).contiguous().cpu()
-    cout, cin, kh, kw = w.shape
+    cout, cin, kh, kw = weight.shape
     assert cin == sum(src_channels), (cin, src_channels)
-    sc = (ctypes.c_int32 * len(src_channels))(*src_channels)
-    count, pack = {0: (lib.mr_conv_packed_weight_floats, lib.mr_conv_pack_weights_f32),
-                   1: (lib.mr_conv_packed_weight_floats_bf16, lib.mr_conv_pack_weights_bf16),
-                   2: (lib.mr_conv_packed_weight_floats_bf16x3, lib.mr_conv_pack_weights_bf16x3)}[int(bf16)]
-    n = count(cout, sc, len(src_channels), kh, kw, mb, ck)
-    assert n > 0, (mb, ck)
-    out = torch.empty(n, dtype=torch.float32)
-    _lib.check(pack(w.data_ptr(), cout, sc, len(src_channels), kh, kw, mb, ck, out.data_ptr()), "mr_conv_pack_weights")
-    return out
+    count, pack = {0: ("mr_conv_packed_weight_floats", "mr_conv_pack_weights_f32"),
+                   1: ("mr_conv_packed_weight_floats_bf16", "mr_conv_pack_weights_bf16"),
+                   2: ("mr_conv_packed_weight_floats_bf16x3", "mr_conv_pack_weights_bf16x3")}[int(bf16)]
+    return pack_weights(count, pack, weight, cout, _int32s(src_channels), len(src_channels), kh, kw, mb, ck)
 
 
 def fold_batchnorm(weight, sd, bn_prefix):
@@ -135,6 +147,44 @@ def lds_bytes(geo, taps, cpads, mb, ck, split_k=1, bf16=False, reduce_bytes=0):
     return max(nbuf * 4 * (ck * geo["plane"] + taps * ck_max * mb * (8 if int(bf16) == 1 else 16)), reduce_bytes)    # bf16x3 blocks: hi + lo = fp32 size
 
 
+# LAUNCH_* kind -> the C-ABI entry that runs one descriptor of that kind: mirrors the mr_run_launches switch (csrc/eltwise.hip)
+_NATIVE_ENTRY = {
+    _lib.LAUNCH_CONV2D: lambda lib, d, arg, s: lib.mr_conv2d_f32(d, s),
+    _lib.LAUNCH_WINO3X3: lambda lib, d, arg, s: lib.mr_conv3x3_winograd_f32(d, s),
+    _lib.LAUNCH_WINO_T: lambda lib, d, arg, s: lib.mr_convt4x4s2_winograd_f32(d, s),
+    _lib.LAUNCH_WINO_1D: lambda lib, d, arg, s: lib.mr_conv1d3_winograd_f32(d, arg, s),
+    _lib.LAUNCH_UPCONV: lambda lib, d, arg, s: lib.mr_upconv2x2_winograd_f32(d, s),
+    _lib.LAUNCH_WINO44: lambda lib, d, arg, s: lib.mr_conv3x3_winograd44_f32(d, s),
+    _lib.LAUNCH_WINO44S: lambda lib, d, arg, s: lib.mr_conv3x3_winograd44s_f32(d, s),
+    _lib.LAUNCH_WINO44W: lambda lib, d, arg, s: lib.mr_conv3x3_winograd44w_f32(d, s),
+    _lib.LAUNCH_CONV_B8: lambda lib, d, arg, s: lib.mr_conv2d_b8(d, s),
+    _lib.LAUNCH_COOKTOOM_1D: lambda lib, d, arg, s: lib.mr_conv1d_cooktoom_f32(d, arg & 15, (arg >> 4) & 15, (arg >> 8) & 15, s),
+}
+
+# The 3x3 stride-1 reduced-multiply forms, by WINOGRAD code variant (decode_form("", code).variant): weight count / pack entries (taking the
+# code's mbw, or no parameter), LDS query, launch kind, output rows x columns x channels (x mbw where the entries take it) per workgroup, the
+# ck / waves conv_log reports, multiplies per output of the direct sum, and whether it is the tail form (32 a + 1..16 channels, mbw 1).
+Wino3x3Form = collections.namedtuple("Wino3x3Form", "count pack takes_mbw lds kind rows cols ch ck waves ratio tail")
+_W22, _W44 = ("mr_wino_packed_weight_floats", "mr_wino_pack_weights_f32"), ("mr_wino44_packed_weight_floats", "mr_wino44_pack_weights_f32")
+WINO3X3_FORMS = {
+    0: Wino3x3Form(*_W22, True, "mr_conv3x3_winograd_lds_bytes", _lib.LAUNCH_WINO3X3, 8, 32, 32, 8, 8, (4, 9), False),     # F(2x2,3x3), LDS buffer (conv_wino.hip)
+    1: Wino3x3Form(*_W22, True, "mr_conv3x3_winograd_lds_bytes", _lib.LAUNCH_WINO3X3, 8, 32, 32, 8, 8, (4, 9), False),     # input transform in registers
+    2: Wino3x3Form("mr_wino_packed_weight_floats_tail", "mr_wino_pack_weights_tail_f32", False, "mr_conv3x3_winograd_lds_bytes", _lib.LAUNCH_WINO3X3,
+                   8, 32, 32, 8, 8, (4, 9), True),            # 32 a + (1..16) channels: the tail by 16-row workgroups (conv_wino.hip: wino_rb_tail)
+    3: Wino3x3Form(*_W44, False, "mr_conv3x3_winograd44_lds_bytes", _lib.LAUNCH_WINO44, 16, 64, 32, 8, 8, (1, 4), False),  # F(4x4,3x3) (conv_wino44.hip)
+    4: Wino3x3Form("mr_wino44s_packed_weight_floats", "mr_wino44s_pack_weights_f32", False, "mr_conv3x3_winograd44s_lds_bytes", _lib.LAUNCH_WINO44S,
+                   8, 64, 32, 4, 8, (1, 4), False),           # F(4x4,3x3), a tile's positions over two waves: two workgroups per CU (conv_wino44s.hip)
+    5: Wino3x3Form(*_W44, False, "mr_conv3x3_winograd44w_lds_bytes", _lib.LAUNCH_WINO44W, 16, 64, 32, 4, 4, (1, 4), False),  # one wave per SIMD (conv_wino44w.hip)
+}
+
+
+def _conv_spec(**given):
+    """`spec` of an fp32 conv_log entry - the arguments the launch was built from (tools/ rebuild single layers from it): `given` over the
+    defaults of a dense stride-1 launch."""
+    return dict(dict(src_shapes=None, w_shape=None, stride=(1, 1), pad=(0, 0), grid=None, in_mode=IN_DIRECT, tf=TF_NONE, act=ACT_NONE, p0=0.0,
+                     p1=0.0, residual=False, out_shape=None, out_step=(1, 1), out_off=(0, 0), phases=None), **given)
+
+
 # Buffers of a plan that the model hands out as outputs (monorec_model.py:256-279,690,713-727).  `Plan.rebind_outputs` can point every
 # launch that writes or reads them at caller-owned memory instead (MonoRecModel.forward: the outputs are produced where the caller
 # keeps them - no copy), and back at the resident buffers (submit()).
@@ -162,7 +212,6 @@ _warned_env = [False]
 
 def active_env_overrides():
     """{name: value} of the kernel-selection overrides set in this process's environment (empty = the committed tables and defaults)."""
-    import os
     return {k: os.environ[k] for k in ENV_OVERRIDES if os.environ.get(k) not in (None, "")}
 
 
@@ -177,67 +226,36 @@ def _warn_env_overrides():
                       "tables / defaults (tuning aid; unset them for the measured configuration)")
 
 
-TUNED = {}          # signature -> (mb, nb, split_k, ck[, waves[, k_split_waves]]); filled from tuned_schedules.json when present
+def _load_table(filename, env=None, value=int):
+    """{key: value(entry)} of monorec_amd/<filename>, or of the file $env names (MR_TUNED_*: the tuning sessions A/B a candidate table before
+    it replaces the committed one); empty when the file does not exist."""
+    path = (env and os.environ.get(env)) or os.path.join(os.path.dirname(os.path.abspath(__file__)), filename)
+    if not os.path.exists(path):
+        return {}
+    with open(path) as f:
+        return {k: value(v) for k, v in json.load(f).items()}
 
 
-def _load_tuned():
-    import json
-    import os
-    # (MR_TUNED_SCHEDULES / MR_TUNED_WINOGRAD: another table file - the tuning sessions A/B a candidate table before it replaces this one)
-    path = os.environ.get("MR_TUNED_SCHEDULES") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_schedules.json")
-    if os.path.exists(path):
-        with open(path) as f:
-            TUNED.update({k: tuple(v) for k, v in json.load(f).items()})
+TUNED = _load_table("tuned_schedules.json", "MR_TUNED_SCHEDULES", tuple)    # signature -> (mb, nb, split_k, ck[, waves[, k_split_waves]])
+WINOGRAD = _load_table("tuned_winograd.json", "MR_TUNED_WINOGRAD")          # kernel-form signature -> form code (decode_form); measured
+# signature of a mr_conv2d_b8 launch (Plan.conv_b8: b8_co.._ci.._k.._s.._o.._b.._p.. + _f<fp32 source>) -> (MB, NB, waves); measured
+# (tools/tune_b8.py) - launches without an entry follow the rule of Plan.b8_schedule
+B8_SCHEDULES = _load_table("tuned_b8.json", "MR_TUNED_B8", lambda v: tuple(int(x) for x in v))
+# conv_forms = "f2": for a key whose table entry is a larger form (F(4,.), F(4x4,3x3)), the F(2,.) code that was measured best for it before
+# the larger forms existed (0 = direct kernel: the 7-tap layers).  MEASURED for the c2 / c3 keys only (15 of the 68 larger-form keys); every
+# other key falls back to a rule - variant 11 for 3x3, the direct kernel for 1-D layers - whose throughput is unmeasured (INTEGRATION.md
+# section 4; ADVICE r4)
+WINOGRAD_F2 = _load_table("tuned_winograd_f2.json")
+
+_parsed = {}        # table name -> (copy of the content it was parsed from, parsed form)
 
 
-_load_tuned()
-
-WINOGRAD = {}       # signature (without the phase / mode suffixes) -> 0 (direct kernel), 1 or 2 (cout blocks per wave; + 10: the variant
-                    # with the input transform in registers); measured
-
-
-def _load_winograd():
-    import json
-    import os
-    path = os.environ.get("MR_TUNED_WINOGRAD") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_winograd.json")
-    if os.path.exists(path):
-        with open(path) as f:
-            WINOGRAD.update({k: int(v) for k, v in json.load(f).items()})
-
-
-_load_winograd()
-
-B8_SCHEDULES = {}   # signature of a mr_conv2d_b8 launch (Plan.conv_b8: b8_co.._ci.._k.._s.._o.._b.._p.. + _f<fp32 source>) -> (MB, NB, waves); measured
-                    # (tools/tune_b8.py) - launches without an entry follow the rule of Plan.b8_schedule
-
-
-def _load_b8_schedules():
-    import json
-    import os
-    path = os.environ.get("MR_TUNED_B8") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_b8.json")
-    if os.path.exists(path):
-        with open(path) as f:
-            B8_SCHEDULES.update({k: tuple(int(x) for x in v) for k, v in json.load(f).items()})
-
-
-_load_b8_schedules()
-
-WINOGRAD_F2 = {}    # conv_forms = "f2": for a key whose table entry is a larger form (F(4,.), F(4x4,3x3)), the F(2,.) code that was
-                    # measured best for it before the larger forms existed (0 = direct kernel: the 7-tap layers).  MEASURED for the c2 / c3
-                    # keys only (15 of the 68 larger-form keys); every other key falls back to a rule - variant 11 for 3x3, the direct kernel
-                    # for 1-D layers - whose throughput is unmeasured
-
-
-def _load_winograd_f2():
-    import json
-    import os
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "tuned_winograd_f2.json")
-    if os.path.exists(path):
-        with open(path) as f:
-            WINOGRAD_F2.update({k: int(v) for k, v in json.load(f).items()})
-
-
-_load_winograd_f2()
+def _parsed_table(name, table, parse):
+    """parse(table), cached on the table's CONTENT: tools rewrite entries in place (tools/tune_pipeline.py), so a length is no key."""
+    hit = _parsed.get(name)
+    if hit is None or hit[0] != table:
+        hit = _parsed[name] = (dict(table), parse(table))
+    return hit[1]
 
 
 def winograd_signature(cout, src_channels, h, w, batch):
@@ -245,20 +263,36 @@ def winograd_signature(cout, src_channels, h, w, batch):
 
 
 _WSIG_RE = re.compile(r"^((?:[a-z]+\d*_)|(?:s2k\d+_))?co(\d+)_ci([\d+]+)_o(\d+)x(\d+)_b(\d+)$")
-_parsed_wino = [None, 0]
 
 
-def _wino_by_prefix():
-    if _parsed_wino[0] is None or _parsed_wino[1] != len(WINOGRAD):
-        by = {}
-        for key, code in WINOGRAD.items():
-            m = _WSIG_RE.match(key)
-            if not m:
-                continue
+def _wino_by_prefix(table):
+    by = {}
+    for key, code in table.items():
+        m = _WSIG_RE.match(key)
+        if m:
             cis = [int(c) for c in m.group(3).split("+")]
             by.setdefault(m.group(1) or "", []).append((int(m.group(2)), sum(cis), int(m.group(4)) * int(m.group(5)), int(m.group(6)), key, int(code)))
-        _parsed_wino[0], _parsed_wino[1] = by, len(WINOGRAD)
-    return _parsed_wino[0]
+    return by
+
+
+FormCode = collections.namedtuple("FormCode", "mbw variant m mbw_x", defaults=(0, 2, 0))
+
+
+def decode_form(prefix, code):
+    """The fields of a WINOGRAD table value of the family `prefix` (0 everywhere: the direct MFMA kernel).  mbw: blocks of output channels
+    per workgroup (32 each for 3x3 / Refine, 16 for 1-D / Upconv / stride-2).
+      ''  3x3, 't_' Refine:             10 variant + mbw  (choose_winograd / choose_winograd_t)
+      'x_' 'y_' 'x7_' 'y7_' 1-D:         10 m + mbw, m = 2 (F(2,3)) below 10  (choose_winograd_1d)
+      'u_' Upconv:                      mbw
+      's2k<taps>_' stride-2 pair:        10 mbw (the k x 1 half) + mbw_x (the 1 x k half; 0: on the direct kernel)  (choose_stride2)"""
+    if prefix in ("", "t_"):
+        return FormCode(mbw=code % 10, variant=code // 10)
+    if prefix.startswith(("x", "y")):
+        return FormCode(mbw=code % 10, m=code // 10 if code >= 10 else 2)
+    if prefix.startswith("s2k"):
+        return FormCode(mbw=code // 10, mbw_x=code % 10)
+    assert prefix == "u_", prefix
+    return FormCode(mbw=code)
 
 
 def nearest_form(prefix, cout, cin, pixels, batch, valid=lambda code: True, exclude=(), max_distance=4.0):
@@ -266,7 +300,7 @@ def nearest_form(prefix, cout, cin, pixels, batch, valid=lambda code: True, excl
     1-D, 't_' Refine, 'u_' Upconv, 's2k<taps>_' stride-2 pairs) whose code is launchable for this layer (`valid`), or None: what a layer WITHOUT a table
     entry runs instead of the old "direct kernel unless the workgroup count says otherwise" rule (VERDICT r5 #6).  Distance as in nearest_schedules."""
     best = None
-    for (co, ci, px, b, key, code) in _wino_by_prefix().get(prefix, ()):
+    for (co, ci, px, b, key, code) in _parsed_table("WINOGRAD", WINOGRAD, _wino_by_prefix).get(prefix, ()):
         if key in exclude or not valid(code):
             continue
         dist = abs(math.log2(co / cout)) + abs(math.log2(ci / cin)) + abs(math.log2(px / pixels)) + 0.5 * abs(math.log2(b / batch))
@@ -289,28 +323,28 @@ def choose_winograd(cout, src_channels, h, w, batch, f2=False):
     sig = winograd_signature(cout, src_channels, h, w, batch)
     if sig in WINOGRAD:
         code = WINOGRAD[sig]
-        if f2 and code // 10 in (3, 4, 5):      # F(4x4,3x3), either kernel -> the F(2x2,3x3) variant measured before it (else: transform in registers, 32 channels)
+        if f2 and decode_form("", code).variant in (3, 4, 5):     # F(4x4,3x3), any kernel -> the F(2x2,3x3) variant measured before it (else: transform in registers, 32 channels)
             code = WINOGRAD_F2.get(sig, 11)
         return code
+
     def ok(code):
-        variant, mbw = code // 10, code % 10
+        f = decode_form("", code)
         if code == 0:
             return True
-        if variant == 2:
-            return mbw == 1 and 0 < cout % 32 <= 16
-        if variant in (0, 1):
-            return mbw == 1 or cout > 32
-        return variant in (3, 4, 5)
+        if f.variant == 2:
+            return f.mbw == 1 and 0 < cout % 32 <= 16
+        if f.variant in (0, 1):
+            return f.mbw == 1 or cout > 32
+        return f.variant in (3, 4, 5)
     code = nearest_form("", cout, sum(src_channels), h * w, batch, valid=ok)
     if code is not None:
-        if f2 and code // 10 in (3, 4, 5):
+        if f2 and decode_form("", code).variant in (3, 4, 5):
             code = 11
         return code
     tiles = math.ceil(h / 8) * math.ceil(w / 32) * batch
     if tiles * math.ceil(cout / 32) < 256:
         return 0
     return 2 if (cout > 32 and tiles * math.ceil(cout / 64) >= 256) else 11
-
 
 
 def choose_winograd_t(cout, src_channels, h, w, batch):
@@ -323,7 +357,12 @@ def choose_winograd_t(cout, src_channels, h, w, batch):
     key = "t_" + winograd_signature(cout, src_channels, h, w, batch)
     if key in WINOGRAD:
         return WINOGRAD[key]
-    return nearest_form("t_", cout, sum(src_channels), h * w, batch, valid=lambda c: c == 0 or (c % 10) * 32 <= max(32, cout)) or 0
+    return nearest_form("t_", cout, sum(src_channels), h * w, batch, valid=lambda c: c == 0 or decode_form("t_", c).mbw * 32 <= max(32, cout)) or 0
+
+
+def wino1d_prefix(axis, taps):
+    """WINOGRAD key prefix of a 1-D layer: 'x_' / 'y_' (3 taps along x / y), 'x7_' / 'y7_' (7 taps)."""
+    return ("x", "y")[axis] + ("" if taps == 3 else str(taps)) + "_"
 
 
 def choose_winograd_1d(axis, cout, src_channels, h, w, batch, taps=3, f2=False):
@@ -334,15 +373,15 @@ def choose_winograd_1d(axis, cout, src_channels, h, w, batch, taps=3, f2=False):
     `x_` / `y_` for 3 taps, `x7_` / `y7_` for 7)."""
     if w % 4:
         return 0
-    prefix = ("x", "y")[axis] + ("" if taps == 3 else str(taps)) + "_"
+    prefix = wino1d_prefix(axis, taps)
     key = prefix + winograd_signature(cout, src_channels, h, w, batch)
     if key in WINOGRAD:
         code = WINOGRAD[key]
     else:                                    # no entry: the form of the nearest measured signature of the same axis / tap count
-        code = nearest_form(prefix, cout, sum(src_channels), h * w, batch, valid=lambda c: c == 0 or (c % 10) <= math.ceil(cout / 16)) or 0
-        if f2 and code >= 40:
+        code = nearest_form(prefix, cout, sum(src_channels), h * w, batch, valid=lambda c: c == 0 or decode_form(prefix, c).mbw <= math.ceil(cout / 16)) or 0
+        if f2 and decode_form(prefix, code).m >= 4:
             return 0
-    if f2 and code >= 40:                    # F(4,.) -> what was measured best among F(2,.) and the direct kernel before the larger forms
+    if f2 and decode_form(prefix, code).m >= 4:     # F(4,.) -> what was measured best among F(2,.) and the direct kernel before the larger forms
         code = WINOGRAD_F2.get(key, 0)
     return code
 
@@ -362,7 +401,8 @@ def choose_stride2(taps, cout, cin, out_h, out_w, batch):
     if key in WINOGRAD:
         return WINOGRAD[key]
     cb = math.ceil(cout / 16)
-    return nearest_form(f"s2k{taps}_", cout, cin, out_h * out_w, batch, valid=lambda c: c == 0 or (c // 10 <= cb and c % 10 <= cb)) or 0
+    return nearest_form(f"s2k{taps}_", cout, cin, out_h * out_w, batch,
+                        valid=lambda c: c == 0 or (decode_form("s2k", c).mbw <= cb and decode_form("s2k", c).mbw_x <= cb)) or 0
 
 
 def stride2_unified_weights(w, n, axis):
@@ -429,22 +469,18 @@ def candidate_schedules(cout, src_channels, kh, kw, sh, sw, out_h, out_w, batch,
 
 
 _SIG_RE = re.compile(r"^co(\d+)_ci([\d+]+)_k(\d+)x(\d+)_s(\d+)x(\d+)_o(\d+)x(\d+)_b(\d+)_p(\d+)(u?)(_bf16x3|_bf16)?$")
-_parsed_tuned = [None, 0]
 
 
-def _tuned_by_class():
-    """TUNED parsed once: (kh, kw, sh, sw, phases, mixed, mode) -> [(cout, cin, nsrc, pixels, batch, key, schedule)]."""
-    if _parsed_tuned[0] is None or _parsed_tuned[1] != len(TUNED):
-        by = {}
-        for key, sched in TUNED.items():
-            m = _SIG_RE.match(key)
-            if not m:
-                continue
+def _tuned_by_class(table):
+    """(kh, kw, sh, sw, phases, mixed, mode) -> [(cout, cin, nsrc, pixels, batch, key, schedule)]."""
+    by = {}
+    for key, sched in table.items():
+        m = _SIG_RE.match(key)
+        if m:
             cis = [int(c) for c in m.group(2).split("+")]
             cls = (int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(6)), int(m.group(10)), m.group(11), m.group(12) or "")
             by.setdefault(cls, []).append((int(m.group(1)), sum(cis), len(cis), int(m.group(7)) * int(m.group(8)), int(m.group(9)), key, tuple(sched)))
-        _parsed_tuned[0], _parsed_tuned[1] = by, len(TUNED)
-    return _parsed_tuned[0]
+    return by
 
 
 def nearest_schedules(cout, src_channels, kh, kw, sh, sw, out_h, out_w, batch, phases=1, bf16=False, mixed_phases=False, exclude=(), limit=6, max_distance=4.0):
@@ -455,7 +491,7 @@ def nearest_schedules(cout, src_channels, kh, kw, sh, sw, out_h, out_w, batch, p
     cls = (kh, kw, sh, sw, phases, "u" if mixed_phases else "", ("", "_bf16", "_bf16x3")[int(bf16)])
     cin, nsrc, pix = sum(src_channels), len(src_channels), out_h * out_w
     scored = []
-    for (co, ci, ns, px, b, key, sched) in _tuned_by_class().get(cls, ()):
+    for (co, ci, ns, px, b, key, sched) in _parsed_table("TUNED", TUNED, _tuned_by_class).get(cls, ()):
         if key in exclude:
             continue
         dist = (abs(math.log2(co / cout)) + abs(math.log2(ci / cin)) + abs(math.log2(px / pix)) + 0.5 * abs(math.log2(b / batch)) + (0.5 if ns != nsrc else 0.0))
@@ -569,9 +605,8 @@ class Plan:
         self.bf16 = int(bf16)         # convolutions: 0 fp32 MFMA, 1 bf16 MFMA (MR_COMPUTE_BF16), 2 bf16x3 split (MR_COMPUTE_BF16X3); everything else fp32
         # bf16 MFMA mode: the activations BETWEEN the convolutions of the mask and depth nets are stored channel-blocked in bf16 ("B8",
         # csrc/conv_b8.hip) - half the HBM bytes, the MFMA operand read from LDS as it is.  MR_B8=0: A/B aid (fp32 storage as in rounds 1-3)
-        import os as _os0
-        self.b8 = self.bf16 == 1 and _os0.environ.get("MR_B8", "1") != "0"
-        self.b8_feature_copies = _os0.environ.get("MR_B8_FEATS", "1") != "0"      # MR_B8_FEATS=0: A/B aid (decoders read the fp32 image features, rounds 4-5)
+        self.b8 = self.bf16 == 1 and os.environ.get("MR_B8", "1") != "0"
+        self.b8_feature_copies = os.environ.get("MR_B8_FEATS", "1") != "0"      # MR_B8_FEATS=0: A/B aid (decoders read the fp32 image features, rounds 4-5)
         self.sd = state
         self.buf = {}
         self.keep = []          # packed weights / biases (device tensors kept alive)
@@ -579,12 +614,10 @@ class Plan:
         self.conv_log = []      # (name, macs, mb, nb, split_k, wgs) for bench / tuning
         self.aux_log = []       # one-channel layers that run on their own HBM-bound kernels (csrc/heads.hip): name, ref_macs
         if one_channel_kernels is None:         # MR_ONE_CHANNEL_KERNELS=0: A/B aid - classifier / depth heads as mr_conv2d_f32 launches
-            import os
             one_channel_kernels = os.environ.get("MR_ONE_CHANNEL_KERNELS", "1") != "0"
         self.one_channel_kernels = bool(one_channel_kernels)
-        import os as _os
         # 3x3 stride-1 convolutions on the Winograd F(2x2,3x3) kernel where it is faster (choose_winograd); MR_WINOGRAD=0: A/B aid
-        self.winograd = _os.environ.get("MR_WINOGRAD", "1") != "0" if winograd is None else bool(winograd)
+        self.winograd = os.environ.get("MR_WINOGRAD", "1") != "0" if winograd is None else bool(winograd)
         # which reduced-multiply forms the measured table may select (MonoRecModel(hip_exact_convs=...)):
         #   "table"  everything it holds, F(4,3) / F(4,7) / F(4x4,3x3) included (transform constants up to 89 and 1/2835);
         #   "f2"     the F(2,.) forms only (constants 0, +-1, +-1/2: rounding like the direct sum) - a layer the table gives to a larger
@@ -726,40 +759,76 @@ class Plan:
         return d
 
     # ------------------------------------------------------------------ op builders
-    def _launch_conv(self, desc, name):
-        lib = self.lib
+    def _emit(self, stage, name, desc, kind, arg=0, keep=()):
+        """Append one native launch: `desc` (ConvDesc / WinoDesc / B8ConvDesc, complete) run by the C-ABI entry of LAUNCH_* `kind`.  Its
+        keyframe source slots follow bind_inputs; the descriptor and `keep` (what its raw pointers name) live as long as the plan.  The
+        closure runs the launch on its own (tools call plan.stages[...][i][1](stream)); run_stage folds runs of such closures into one
+        mr_run_launches call through `.native`."""
+        kf = self.buf.get("keyframe")
+        for i in range(desc.num_src):
+            if kf is not None and desc.src[i] == kf.data_ptr():
+                self._input_srcs.append((desc, i, "keyframe"))
+        self.keep += [desc] + list(keep)
+        lib, entry = self.lib, _NATIVE_ENTRY[kind]
 
         def run(stream):
-            _lib.check(lib.mr_conv2d_f32(ctypes.byref(desc), stream), name)
-        run.native = (_lib.LAUNCH_CONV2D, desc, 0)          # run_stage walks runs of such launches in one host call (mr_run_launches)
-        return run
+            _lib.check(entry(lib, ctypes.byref(desc), arg, stream), name)
+        run.native = (kind, desc, arg)
+        self.stages[stage].append((name, run))
+
+    def _log(self, name, *, macs, mb, wgs, lds, cout, cin, k, out, batch, sig, spec, ref_macs=None, nb=0, split_k=1, ck=8, waves=8, kws=0,
+             phases=1, bf16=0, **family):
+        """Append one conv_log entry (bench.py, tools/ and the host tests read this schema): the keys every entry has, then `family` - the keys
+        of one kernel family only (winograd, wino_variant, wino_axis / wino_m / wino_taps / stride2, upconv, b8 / f32_source)."""
+        self.conv_log.append(dict(name=name, macs=macs, ref_macs=macs if ref_macs is None else ref_macs, mb=mb, nb=nb, split_k=split_k, ck=ck,
+                                  waves=waves, kws=kws, wgs=wgs, lds=int(lds), cout=cout, cin=cin, k=k, out=out, batch=batch, phases=phases,
+                                  **family, bf16=bf16, sig=sig, spec=spec))
+
+    def _wino_desc(self, ptrs, channels, n, h, w, out, cout, packed, bias, act, p0, mbw, variant=0):
+        """mr_wino_desc of a reduced-multiply launch (csrc/conv_wino*.hip, convt_wino.hip, conv1d_wino.hip); `packed`: CPU weights."""
+        d = WinoDesc()
+        for i, (p, c) in enumerate(zip(ptrs, channels)):
+            d.src[i], d.src_channels[i] = p, c
+        d.num_src, d.batch, d.height, d.width = len(ptrs), n, h, w
+        d.dst, d.out_channels = out.data_ptr(), cout
+        d.packed_weights = self._dev(packed).data_ptr()
+        d.bias = self._dev(bias).data_ptr() if bias is not None else None
+        d.activation, d.act_p0, d.cout_blocks_per_wave, d.variant = act, p0, mbw, variant
+        return d
+
+    @staticmethod
+    def _dense_srcs(srcs):
+        """(batch, height, width, channels) of the dense NCHW sources of one launch, concatenated on channels."""
+        n, _, hs, ws = srcs[0].shape
+        assert all(s.shape[0] == n and s.shape[2] == hs and s.shape[3] == ws and s.is_contiguous() for s in srcs)
+        return n, hs, ws, [int(s.shape[1]) for s in srcs]
+
+    def _check_lds(self, lds, what):
+        if lds < 0:
+            _lib.check(int(lds), what)
+        return lds
 
     def conv(self, stage, name, srcs, weight, bias, out, *, stride=(1, 1), pad=(0, 0), grid=None,
              act=ACT_NONE, p0=0.0, p1=0.0, in_mode=IN_DIRECT, tf=TF_NONE, residual=None,
              out_step=(1, 1), out_off=(0, 0), out_ch_offset=0, phases=None, ref_macs=None):
-        """Append one mr_conv2d_f32 launch. srcs: list of (N,C,Hs,Ws) tensors concatenated on channels.
-        phases: optional list of 4 (weight, pad_top, pad_left, out_off_h, out_off_w) run in one launch."""
-        n, _, hs, ws = srcs[0].shape
-        src_channels = [int(s.shape[1]) for s in srcs]
-        for s in srcs:
-            assert s.shape[0] == n and s.shape[2] == hs and s.shape[3] == ws and s.is_contiguous()
-        w0 = weight if phases is None else phases[0][0]
-        cout, cin, kh, kw = w0.shape
-        if (self.winograd and phases is None and (kh, kw) == (3, 3) and tuple(stride) == (1, 1) and tuple(pad) == (1, 1) and
-                in_mode == IN_DIRECT and tf == TF_NONE and tuple(out_step) == (1, 1) and tuple(out_off) == (0, 0) and out_ch_offset == 0 and
-                out.shape[1] == cout and tuple(grid) == (hs, ws) and act in (ACT_NONE, ACT_RELU, ACT_LEAKY_RELU) and self.bf16 == 0 and
-                name not in self.schedule_override):
-            mbw = choose_winograd(cout, src_channels, hs, ws, n, f2=self.conv_forms == "f2")
-            if mbw:
-                return self._conv_winograd(stage, name, srcs, weight, bias, out, act, p0, residual, mbw % 10, mbw // 10)
-        if (self.winograd and phases is None and (kh, kw) in ((1, 3), (3, 1), (1, 7), (7, 1)) and tuple(stride) == (1, 1) and tuple(pad) == (kh // 2, kw // 2) and
-                in_mode == IN_DIRECT and tf == TF_NONE and tuple(out_step) == (1, 1) and tuple(out_off) == (0, 0) and out_ch_offset == 0 and
-                out.shape[1] == cout and tuple(grid) == (hs, ws) and act in (ACT_NONE, ACT_RELU, ACT_LEAKY_RELU) and self.bf16 == 0 and
-                residual is None and name not in self.schedule_override):
-            axis = 0 if kh == 1 else 1
-            code = choose_winograd_1d(axis, cout, src_channels, hs, ws, n, max(kh, kw), f2=self.conv_forms == "f2")
+        """Append one mr_conv2d_f32 launch - or one launch of the reduced-multiply form the measured table gives the layer. srcs: list of
+        (N,C,Hs,Ws) tensors concatenated on channels.  phases: optional list of 4 (weight, pad_top, pad_left, out_off_h, out_off_w) run in one launch."""
+        n, hs, ws, src_channels = self._dense_srcs(srcs)
+        cout, cin, kh, kw = (weight if phases is None else phases[0][0]).shape
+        # a dense stride-1 fp32 launch the table may move to a reduced-multiply form
+        dense = (self.winograd and phases is None and tuple(stride) == (1, 1) and in_mode == IN_DIRECT and tf == TF_NONE and
+                 tuple(out_step) == (1, 1) and tuple(out_off) == (0, 0) and out_ch_offset == 0 and out.shape[1] == cout and tuple(grid) == (hs, ws) and
+                 act in (ACT_NONE, ACT_RELU, ACT_LEAKY_RELU) and self.bf16 == 0 and name not in self.schedule_override)
+        if dense and (kh, kw) == (3, 3) and tuple(pad) == (1, 1):
+            code = choose_winograd(cout, src_channels, hs, ws, n, f2=self.conv_forms == "f2")
             if code:
-                return self._conv_winograd_1d(stage, name, srcs, weight, bias, out, act, p0, axis, code % 10, code // 10 if code >= 10 else 2)
+                return self._conv_winograd(stage, name, srcs, weight, bias, out, act, p0, residual, decode_form("", code))
+        if dense and (kh, kw) in ((1, 3), (3, 1), (1, 7), (7, 1)) and tuple(pad) == (kh // 2, kw // 2) and residual is None:
+            axis, taps = (0 if kh == 1 else 1), max(kh, kw)
+            code = choose_winograd_1d(axis, cout, src_channels, hs, ws, n, taps, f2=self.conv_forms == "f2")
+            if code:
+                f = decode_form(wino1d_prefix(axis, taps), code)
+                return self._conv_winograd_1d(stage, name, srcs, weight, bias, out, act, p0, axis, f.mbw, f.m)
         if phases is not None:                 # the common kh x kw sizes the input tile: the maximum over the phases
             kh, kw = max(p[0].shape[2] for p in phases), max(p[0].shape[3] for p in phases)
         mixed = phases is not None and any(tuple(p[0].shape[2:]) != (kh, kw) for p in phases)
@@ -771,10 +840,7 @@ class Plan:
                  schedule_candidates(cout, src_channels, kh, kw, stride[0], stride[1], out_h, out_w, n, nph, bf16, mixed))
         d = ConvDesc()
         for i, s in enumerate(srcs):
-            d.src[i] = s.data_ptr()
-            d.src_channels[i] = src_channels[i]
-            if "keyframe" in self.buf and s is self.buf["keyframe"]:
-                self._input_srcs.append((d, i, "keyframe"))
+            d.src[i], d.src_channels[i] = s.data_ptr(), src_channels[i]
         d.num_src, d.batch, d.src_h, d.src_w = len(srcs), n, hs, ws
         d.in_mode, d.in_transform = in_mode, tf
         d.kh, d.kw, d.stride_h, d.stride_w, d.pad_top, d.pad_left = kh, kw, stride[0], stride[1], pad[0], pad[1]
@@ -784,11 +850,10 @@ class Plan:
         d.out_channels, d.dst_total_channels, d.dst_channel_offset = cout, out.shape[1], out_ch_offset
         d.dst_plane_h, d.dst_plane_w = out.shape[2], out.shape[3]
         d.out_step_h, d.out_step_w, d.out_off_h, d.out_off_w = out_step[0], out_step[1], out_off[0], out_off[1]
-        d.num_phases = 1 if phases is None else nph
-        if phases is not None:
-            for i, (wp, pt, pl, oh, ow) in enumerate(phases):
-                d.phase_pad_top[i], d.phase_pad_left[i], d.phase_out_off_h[i], d.phase_out_off_w[i] = pt, pl, oh, ow
-                d.phase_kh[i], d.phase_kw[i] = wp.shape[2], wp.shape[3]
+        d.num_phases = nph
+        for i, (wp, pt, pl, oh, ow) in enumerate(phases or ()):
+            d.phase_pad_top[i], d.phase_pad_left[i], d.phase_out_off_h[i], d.phase_out_off_w[i] = pt, pl, oh, ow
+            d.phase_kh[i], d.phase_kw[i] = wp.shape[2], wp.shape[3]
         d.bias = self._dev(bias).data_ptr() if bias is not None else None
         if residual is not None:
             assert residual.shape == out.shape
@@ -796,7 +861,8 @@ class Plan:
         d.activation, d.act_p0, d.act_p1 = act, p0, p1
         d.compute_dtype = int(bf16)
         # the first candidate the library itself accepts (LDS budget, chunk counts, DMA constraints: mr_conv2d_lds_bytes validates the whole descriptor);
-        # a table entry or an override is the only candidate and must launch
+        # a table entry or an override is the only candidate and must launch.  Only the geometry is validated here: the weight and workspace
+        # slots hold non-null placeholders until the loop ends.
         lds, sched = -1, None
         for sched in cands:
             mb, nb, split_k, ck = sched[:4]
@@ -804,20 +870,18 @@ class Plan:
             kws = int(sched[5]) if len(sched) > 5 else 0       # K split across the waves of a workgroup
             d.cout_blocks_per_wg, d.pixel_blocks_per_wave, d.split_k, d.chunk_channels = mb, nb, split_k, ck
             d.waves_per_wg, d.k_split_waves = waves, kws
-            d.workspace = 1 if split_k > 1 else None           # placeholder (non-null) until the shared workspace exists
-            d.packed_weights = 1                               # (placeholders: only the geometry is validated here)
+            d.workspace = 1 if split_k > 1 else None
+            d.packed_weights = 1
             for i in range(nph if phases is not None else 0):
                 d.phase_weights[i] = 1
             lds = self.lib.mr_conv2d_lds_bytes(ctypes.byref(d))
             if lds >= 0:
                 break
-        if lds < 0:
-            _lib.check(int(lds), f"plan {name} sched={sched}")
-        if phases is None:
-            d.packed_weights = self._dev(pack_conv_weight(weight, src_channels, mb, ck, bf16)).data_ptr()
-        else:
-            for i, (wp, pt, pl, oh, ow) in enumerate(phases):
-                d.phase_weights[i] = self._dev(pack_conv_weight(wp, src_channels, mb, ck, bf16)).data_ptr()
+        self._check_lds(lds, f"plan {name} sched={sched}")
+        d.workspace = None                                     # finalize() points split-K launches at their stage's workspace
+        d.packed_weights = self._dev(pack_conv_weight(weight, src_channels, mb, ck, bf16)).data_ptr() if phases is None else None
+        for i, (wp, pt, pl, oh, ow) in enumerate(phases or ()):
+            d.phase_weights[i] = self._dev(pack_conv_weight(wp, src_channels, mb, ck, bf16)).data_ptr()
         if split_k > 1:
             self._ws_floats[stage] = max(self._ws_floats.get(stage, 0),
                                          split_k * nph * n * ((cout + 15) // 16 * 16) * out_h * out_w)
@@ -825,95 +889,38 @@ class Plan:
         taps = kh * kw if phases is None else sum(p[0].shape[2] * p[0].shape[3] for p in phases)
         macs = n * out_h * out_w * cout * cin * taps
         geo = conv_geometry(out_h, out_w, kh, kw, stride[0], stride[1], nb, waves, kws)
-        wgs = geo["tiles"] * math.ceil(((cout + 15) // 16) / mb) * n * split_k * nph
-        self.conv_log.append(dict(name=name, macs=macs, ref_macs=macs if ref_macs is None else ref_macs, mb=mb, nb=nb, split_k=split_k, ck=ck, waves=waves, kws=kws, wgs=wgs, lds=int(lds),
-                                  cout=cout, cin=cin, k=(kh, kw), out=(out_h, out_w), batch=n, phases=nph,
-                                  sig=schedule_signature(cout, src_channels, kh, kw, stride[0], stride[1], out_h, out_w, n, nph, bf16, mixed), bf16=bf16,
-                                  spec=dict(src_shapes=[tuple(s.shape) for s in srcs], w_shape=(cout, cin, kh, kw),
-                                            stride=tuple(stride), pad=tuple(pad), grid=(out_h, out_w), in_mode=in_mode,
-                                            tf=tf, act=act, p0=p0, p1=p1, residual=residual is not None,
-                                            out_shape=tuple(out.shape), out_step=tuple(out_step), out_off=tuple(out_off),
-                                            phases=None if phases is None else [(pt, pl, oh, ow, int(wp.shape[2]), int(wp.shape[3]))
-                                                                                for wp, pt, pl, oh, ow in phases])))
-        self.keep += [d, out, residual] + list(srcs)      # the descriptor only holds raw pointers
-        self.stages[stage].append((name, self._launch_conv(d, name)))
+        self._log(name, macs=macs, ref_macs=ref_macs, mb=mb, nb=nb, split_k=split_k, ck=ck, waves=waves, kws=kws,
+                  wgs=geo["tiles"] * math.ceil(((cout + 15) // 16) / mb) * n * split_k * nph, lds=lds, cout=cout, cin=cin, k=(kh, kw),
+                  out=(out_h, out_w), batch=n, phases=nph, bf16=bf16,
+                  sig=schedule_signature(cout, src_channels, kh, kw, stride[0], stride[1], out_h, out_w, n, nph, bf16, mixed),
+                  spec=_conv_spec(src_shapes=[tuple(s.shape) for s in srcs], w_shape=(cout, cin, kh, kw), stride=tuple(stride), pad=tuple(pad),
+                                  grid=(out_h, out_w), in_mode=in_mode, tf=tf, act=act, p0=p0, p1=p1, residual=residual is not None,
+                                  out_shape=tuple(out.shape), out_step=tuple(out_step), out_off=tuple(out_off),
+                                  phases=None if phases is None else [(pt, pl, oh, ow, int(wp.shape[2]), int(wp.shape[3])) for wp, pt, pl, oh, ow in phases]))
+        self._emit(stage, name, d, _lib.LAUNCH_CONV2D, keep=[out, residual] + list(srcs))
         return out
 
-    def _conv_winograd(self, stage, name, srcs, weight, bias, out, act, p0, residual, mbw, variant=0):
-        """One mr_conv3x3_winograd_f32 launch (csrc/conv_wino.hip) in place of a 3x3 stride-1 mr_conv2d_f32 launch."""
-        lib = self.lib
-        n, _, hs, ws = srcs[0].shape
-        src_channels = [int(s.shape[1]) for s in srcs]
+    def _conv_winograd(self, stage, name, srcs, weight, bias, out, act, p0, residual, form):
+        """One launch of the 3x3 stride-1 reduced-multiply form WINO3X3_FORMS[form.variant] in place of a mr_conv2d_f32 launch."""
+        rec, mbw = WINO3X3_FORMS[form.variant], form.mbw
+        n, hs, ws, src_channels = self._dense_srcs(srcs)
         cout, cin = int(weight.shape[0]), int(weight.shape[1])
-        sc = (ctypes.c_int32 * len(src_channels))(*src_channels)
-        w = weight.detach().to(torch.float32).contiguous().cpu()
-        if variant == 4:       # F(4x4,3x3) with the positions split over two waves (csrc/conv_wino44s.hip): 8 x 64 pixels x 32 channels, two workgroups per CU
-            nfl = lib.mr_wino44s_packed_weight_floats(cout, sc, len(src_channels))
-            packed = torch.empty(nfl, dtype=torch.float32)
-            _lib.check(lib.mr_wino44s_pack_weights_f32(w.data_ptr(), cout, sc, len(src_channels), packed.data_ptr()), "mr_wino44s_pack_weights_f32")
-        elif variant in (3, 5):     # F(4x4,3x3) (csrc/conv_wino44.hip; 5: csrc/conv_wino44w.hip, one wave per SIMD): 36 positions, 16 x 64 pixels x 32 channels per workgroup
-            nfl = lib.mr_wino44_packed_weight_floats(cout, sc, len(src_channels))
-            packed = torch.empty(nfl, dtype=torch.float32)
-            _lib.check(lib.mr_wino44_pack_weights_f32(w.data_ptr(), cout, sc, len(src_channels), packed.data_ptr()), "mr_wino44_pack_weights_f32")
-        elif variant == 2:     # 32 a + (1..16) output channels: the tail group by 16-row workgroups (csrc/conv_wino.hip: wino_rb_tail)
-            assert mbw == 1 and 0 < cout % 32 <= 16, (name, cout)
-            nfl = lib.mr_wino_packed_weight_floats_tail(cout, sc, len(src_channels))
-            packed = torch.empty(nfl, dtype=torch.float32)
-            _lib.check(lib.mr_wino_pack_weights_tail_f32(w.data_ptr(), cout, sc, len(src_channels), packed.data_ptr()), "mr_wino_pack_weights_tail_f32")
-        else:
-            nfl = lib.mr_wino_packed_weight_floats(cout, sc, len(src_channels), mbw)
-            packed = torch.empty(nfl, dtype=torch.float32)
-            _lib.check(lib.mr_wino_pack_weights_f32(w.data_ptr(), cout, sc, len(src_channels), mbw, packed.data_ptr()), "mr_wino_pack_weights_f32")
-        d = WinoDesc()
-        for i, s_ in enumerate(srcs):
-            d.src[i], d.src_channels[i] = s_.data_ptr(), src_channels[i]
-            if "keyframe" in self.buf and s_ is self.buf["keyframe"]:
-                self._input_srcs.append((d, i, "keyframe"))
-        d.num_src, d.batch, d.height, d.width = len(srcs), n, hs, ws
-        d.dst, d.out_channels = out.data_ptr(), cout
+        assert not rec.tail or (mbw == 1 and 0 < cout % 32 <= 16), (name, cout)
+        packed = pack_weights(rec.count, rec.pack, weight, cout, _int32s(src_channels), len(src_channels), *((mbw,) if rec.takes_mbw else ()))
         assert out.is_contiguous() and tuple(out.shape) == (n, cout, hs, ws)
-        d.packed_weights = self._dev(packed).data_ptr()
-        d.bias = self._dev(bias).data_ptr() if bias is not None else None
+        d = self._wino_desc([s_.data_ptr() for s_ in srcs], src_channels, n, hs, ws, out, cout, packed, bias, act, p0, mbw, form.variant)
         if residual is not None:
             assert residual.shape == out.shape
             d.residual = residual.data_ptr()
-        d.activation, d.act_p0, d.cout_blocks_per_wave, d.variant = act, p0, mbw, variant
-        lds = (lib.mr_conv3x3_winograd44s_lds_bytes(ctypes.byref(d)) if variant == 4 else lib.mr_conv3x3_winograd44w_lds_bytes(ctypes.byref(d)) if variant == 5 else
-               lib.mr_conv3x3_winograd44_lds_bytes(ctypes.byref(d)) if variant == 3 else lib.mr_conv3x3_winograd_lds_bytes(ctypes.byref(d)))
-        if lds < 0:
-            _lib.check(int(lds), f"plan {name} winograd")
+        lds = self._check_lds(getattr(self.lib, rec.lds)(ctypes.byref(d)), f"plan {name} winograd")
         ref = n * hs * ws * cout * cin * 9
-        if variant == 4:
-            wgs = math.ceil(hs / 8) * math.ceil(ws / 64) * n * math.ceil(cout / 32)
-        elif variant in (3, 5):
-            wgs = math.ceil(hs / 16) * math.ceil(ws / 64) * n * math.ceil(cout / 32)
-        else:
-            wgs = math.ceil(hs / 8) * math.ceil(ws / 32) * n * math.ceil(cout / (32 * mbw))
-        self.conv_log.append(dict(name=name, macs=ref // 4 if variant in (3, 4, 5) else ref * 4 // 9, ref_macs=ref, mb=mbw, nb=0, split_k=1, ck=4 if variant in (4, 5) else 8, waves=4 if variant == 5 else 8, kws=0, wgs=wgs, lds=int(lds),
-                                  cout=cout, cin=cin, k=(3, 3), out=(hs, ws), batch=n, phases=1, winograd=mbw, wino_variant=variant, bf16=0,
-                                  sig=winograd_signature(cout, src_channels, hs, ws, n),
-                                  spec=dict(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 3, 3), stride=(1, 1), pad=(1, 1),
-                                            grid=(hs, ws), in_mode=IN_DIRECT, tf=TF_NONE, act=act, p0=p0, p1=0.0, residual=residual is not None,
-                                            out_shape=tuple(out.shape), out_step=(1, 1), out_off=(0, 0), phases=None)))
-        self.keep += [d, out, residual] + list(srcs)
-
-        if variant == 4:
-            def run(stream):
-                _lib.check(lib.mr_conv3x3_winograd44s_f32(ctypes.byref(d), stream), name)
-            run.native = (_lib.LAUNCH_WINO44S, d, 0)
-        elif variant == 5:
-            def run(stream):
-                _lib.check(lib.mr_conv3x3_winograd44w_f32(ctypes.byref(d), stream), name)
-            run.native = (_lib.LAUNCH_WINO44W, d, 0)
-        elif variant == 3:
-            def run(stream):
-                _lib.check(lib.mr_conv3x3_winograd44_f32(ctypes.byref(d), stream), name)
-            run.native = (_lib.LAUNCH_WINO44, d, 0)
-        else:
-            def run(stream):
-                _lib.check(lib.mr_conv3x3_winograd_f32(ctypes.byref(d), stream), name)
-            run.native = (_lib.LAUNCH_WINO3X3, d, 0)
-        self.stages[stage].append((name, run))
+        wg_ch = rec.ch * (mbw if rec.takes_mbw else 1)
+        self._log(name, macs=ref * rec.ratio[0] // rec.ratio[1], ref_macs=ref, mb=mbw, ck=rec.ck, waves=rec.waves,
+                  wgs=math.ceil(hs / rec.rows) * math.ceil(ws / rec.cols) * n * math.ceil(cout / wg_ch), lds=lds, cout=cout, cin=cin, k=(3, 3),
+                  out=(hs, ws), batch=n, winograd=mbw, wino_variant=form.variant, sig=winograd_signature(cout, src_channels, hs, ws, n),
+                  spec=_conv_spec(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 3, 3), pad=(1, 1), grid=(hs, ws), act=act, p0=p0,
+                                  residual=residual is not None, out_shape=tuple(out.shape)))
+        self._emit(stage, name, d, rec.kind, keep=[out, residual] + list(srcs))
         return out
 
     def _conv_winograd_1d(self, stage, name, srcs, weight, bias, out, act, p0, axis, mbw, m=2, view=None, dst_split=False, ref_macs=None, ref_k=None,
@@ -921,10 +928,8 @@ class Plan:
         """One mr_conv1d3_winograd_f32 launch (csrc/conv1d_wino.hip: F(2,3), 4 instead of 6 multiplies per output pair) - or, for m = 4 or
         7 taps, one mr_conv1d_cooktoom_f32 launch (F(m, taps): m + taps - 1 multiplies per m outputs) - in place of a k x 1 / 1 x k
         stride-1 mr_conv2d_f32 launch."""
-        lib = self.lib
         if view is None:
-            n, _, hs, ws = srcs[0].shape
-            src_channels = [int(s_.shape[1]) for s_ in srcs]
+            n, hs, ws, src_channels = self._dense_srcs(srcs)
             src_ptrs = [s_.data_ptr() for s_ in srcs]
         else:
             # strided source views (the k x 1 stride-(2,1) half of a ConvReLU2 pair as a stride-1 form over [even rows | odd rows]):
@@ -935,84 +940,58 @@ class Plan:
         taps = int(weight.shape[3] if axis == 0 else weight.shape[2])
         assert tuple(weight.shape[2:]) == ((1, taps) if axis == 0 else (taps, 1)) and cin == sum(src_channels), (name, weight.shape)
         general = (m, taps) != (2, 3)
-        sc = (ctypes.c_int32 * len(src_channels))(*src_channels)
-        w = weight.detach().to(torch.float32).contiguous().cpu()
-        if general:
-            nfl = lib.mr_cooktoom1d_packed_weight_floats(cout, sc, len(src_channels), mbw, m, taps)
-            assert nfl > 0, (name, m, taps, mbw)
-            packed = torch.empty(nfl, dtype=torch.float32)
-            _lib.check(lib.mr_cooktoom1d_pack_weights_f32(w.data_ptr(), cout, sc, len(src_channels), mbw, m, taps, packed.data_ptr()),
-                       "mr_cooktoom1d_pack_weights_f32")
+        if general:         # Cook-Toom F(m, taps): 8 x 16 m (along x) / 4 m x 32 (along y) outputs per workgroup
+            count, pack, params = "mr_cooktoom1d_packed_weight_floats", "mr_cooktoom1d_pack_weights_f32", (mbw, m, taps)
+            kind, arg, (rh, rw) = _lib.LAUNCH_COOKTOOM_1D, axis | (m << 4) | (taps << 8), ((8, 16 * m) if axis == 0 else (4 * m, 32))
+        else:               # F(2,3): 8 x 32 outputs per workgroup
+            count, pack, params = "mr_wino1d_packed_weight_floats", "mr_wino1d_pack_weights_f32", (mbw,)
+            kind, arg, (rh, rw) = _lib.LAUNCH_WINO_1D, axis, (8, 32)
+        packed = pack_weights(count, pack, weight, cout, _int32s(src_channels), len(src_channels), *params)
+        if dst_split:            # (2, n, cout, hs, ws / 2): even columns, odd columns - the two sources of the 1 x k stride-(1,2) half
+            assert general and axis == 1 and out.is_contiguous() and tuple(out.shape) == (2, n, cout, hs, ws // 2), (name, tuple(out.shape))
         else:
-            nfl = lib.mr_wino1d_packed_weight_floats(cout, sc, len(src_channels), mbw)
-            packed = torch.empty(nfl, dtype=torch.float32)
-            _lib.check(lib.mr_wino1d_pack_weights_f32(w.data_ptr(), cout, sc, len(src_channels), mbw, packed.data_ptr()), "mr_wino1d_pack_weights_f32")
-        d = WinoDesc()
-        for i in range(len(src_ptrs)):
-            d.src[i], d.src_channels[i] = src_ptrs[i], src_channels[i]
-            if view is None and "keyframe" in self.buf and srcs[i] is self.buf["keyframe"]:
-                self._input_srcs.append((d, i, "keyframe"))
-        d.num_src, d.batch, d.height, d.width = len(src_ptrs), n, hs, ws
+            assert out.is_contiguous() and tuple(out.shape) == (n, cout, hs, ws)
+        d = self._wino_desc(src_ptrs, src_channels, n, hs, ws, out, cout, packed, bias, act, p0, mbw)
+        d.dst_split_columns = int(dst_split)
         if view is not None:
             assert general, name
             d.src_row_pitch, d.src_plane_floats = int(view["row_pitch"]), int(view["plane"])
-        if dst_split:            # (2, n, cout, hs, ws / 2): even columns, odd columns - the two sources of the 1 x k stride-(1,2) half
-            assert general and axis == 1 and out.is_contiguous() and tuple(out.shape) == (2, n, cout, hs, ws // 2), (name, tuple(out.shape))
-            d.dst_split_columns = 1
-        else:
-            assert out.is_contiguous() and tuple(out.shape) == (n, cout, hs, ws)
-        d.dst, d.out_channels = out.data_ptr(), cout
-        d.packed_weights = self._dev(packed).data_ptr()
-        d.bias = self._dev(bias).data_ptr() if bias is not None else None
-        d.activation, d.act_p0, d.cout_blocks_per_wave = act, p0, mbw
-        lds = lib.mr_conv1d_cooktoom_lds_bytes(ctypes.byref(d), axis, m, taps) if general else lib.mr_conv1d3_winograd_lds_bytes(ctypes.byref(d))
-        if lds < 0:
-            _lib.check(int(lds), f"plan {name} winograd-1d")
+        lds = self._check_lds(self.lib.mr_conv1d_cooktoom_lds_bytes(ctypes.byref(d), axis, m, taps) if general else
+                              self.lib.mr_conv1d3_winograd_lds_bytes(ctypes.byref(d)), f"plan {name} winograd-1d")
         ref = n * hs * ws * cout * cin * taps
-        rh, rw = ((8, 16 * m) if axis == 0 else (4 * m, 32)) if general else (8, 32)
-        wgs = math.ceil(hs / rh) * math.ceil(ws / rw) * n * math.ceil(cout / (16 * mbw))
         kk = (1, taps) if axis == 0 else (taps, 1)
         # (ref_macs / ref_k: the reference's multiply-adds and filter of a stride-2 layer run as a stride-1 form over [even | odd] - the unified
         # filter has 2 * ceil(k / 2) >= k taps per input channel, of which the padded one is a zero weight)
-        self.conv_log.append(dict(name=name, macs=ref * (m + taps - 1) // (m * taps), ref_macs=ref if ref_macs is None else ref_macs, mb=mbw, nb=0, split_k=1, ck=8,
-                                  waves=8, kws=0, wgs=wgs,
-                                  lds=int(lds), cout=cout, cin=cin, k=kk if ref_k is None else ref_k, out=(hs, ws), batch=n, phases=1, winograd=mbw, wino_variant=0,
-                                  wino_axis=axis, wino_m=m, wino_taps=taps, stride2=ref_k is not None, bf16=0,
-                                  sig=sig or (("x", "y")[axis] + ("" if taps == 3 else str(taps)) + "_" + winograd_signature(cout, src_channels, hs, ws, n)),
-                                  spec=dict(src_shapes=[(n, c_, hs, ws) for c_ in src_channels], w_shape=(cout, cin) + kk,
-                                            stride=(1, 1) if ref_k is None else ((2, 1) if axis == 1 else (1, 2)), pad=(kk[0] // 2, kk[1] // 2),
-                                            grid=(hs, ws), in_mode=IN_DIRECT, tf=TF_NONE, act=act, p0=p0, p1=0.0, residual=False,
-                                            out_shape=tuple(out.shape), out_step=(1, 1), out_off=(0, 0), phases=None)))
-        self.keep += [d, out] + list(srcs)
-
-        if general:
-            def run(stream):
-                _lib.check(lib.mr_conv1d_cooktoom_f32(ctypes.byref(d), axis, m, taps, stream), name)
-            run.native = (_lib.LAUNCH_COOKTOOM_1D, d, axis | (m << 4) | (taps << 8))
-        else:
-            def run(stream):
-                _lib.check(lib.mr_conv1d3_winograd_f32(ctypes.byref(d), axis, stream), name)
-            run.native = (_lib.LAUNCH_WINO_1D, d, axis)
-        self.stages[stage].append((name, run))
+        self._log(name, macs=ref * (m + taps - 1) // (m * taps), ref_macs=ref if ref_macs is None else ref_macs, mb=mbw,
+                  wgs=math.ceil(hs / rh) * math.ceil(ws / rw) * n * math.ceil(cout / (16 * mbw)), lds=lds, cout=cout, cin=cin,
+                  k=kk if ref_k is None else ref_k, out=(hs, ws), batch=n, winograd=mbw, wino_variant=0, wino_axis=axis, wino_m=m, wino_taps=taps,
+                  stride2=ref_k is not None, sig=sig or (wino1d_prefix(axis, taps) + winograd_signature(cout, src_channels, hs, ws, n)),
+                  spec=_conv_spec(src_shapes=[(n, c_, hs, ws) for c_ in src_channels], w_shape=(cout, cin) + kk,
+                                  stride=(1, 1) if ref_k is None else ((2, 1) if axis == 1 else (1, 2)), pad=(kk[0] // 2, kk[1] // 2),
+                                  grid=(hs, ws), act=act, p0=p0, out_shape=tuple(out.shape)))
+        self._emit(stage, name, d, kind, arg, keep=[out] + list(srcs))
         return out
+
+    @staticmethod
+    def _b8_operands(srcs, out):
+        """Whether a layer reads or writes a B8 tensor (alloc_b8): it then runs on the B8 kernel (conv_b8)."""
+        return any(t.dtype == torch.bfloat16 for t in list(srcs) + [out])
 
     def same_conv(self, stage, name, srcs, wkey, bkey, out, *, stride=(1, 1), act=ACT_LEAKY_RELU, p0=LEAKY_SLOPE,
                   p1=0.0, in_mode=IN_DIRECT):
         """PadSameConv2d + Conv2d (+ activation): model/layers.py:241-252,329-335."""
         w = self.sd[wkey]
         hs, ws = srcs[0].shape[2], srcs[0].shape[3]
-        if in_mode == IN_UPSAMPLE2:
-            hin, win = 2 * hs, 2 * ws
-        elif in_mode == IN_MAXPOOL2:
-            hin, win = hs // 2, ws // 2
-        else:
-            hin, win = hs, ws
+        hin, win = {IN_UPSAMPLE2: (2 * hs, 2 * ws), IN_MAXPOOL2: (hs // 2, ws // 2)}.get(in_mode, (hs, ws))      # the conv's input plane
         kh, kw = w.shape[2], w.shape[3]
         pt, _ = same_pad(hin, kh, stride[0])
         pl, _ = same_pad(win, kw, stride[1])
         grid = (math.ceil(hin / stride[0]), math.ceil(win / stride[1]))
-        return self.conv(stage, name, srcs, w, self.sd[bkey] if bkey else None, out, stride=stride, pad=(pt, pl),
-                         grid=grid, act=act, p0=p0, p1=p1, in_mode=in_mode)
+        bias = self.sd[bkey] if bkey else None
+        if self._b8_operands(srcs, out):
+            assert in_mode == IN_DIRECT and p1 == 0.0, name
+            return self.conv_b8(stage, name, srcs, w, bias, out, stride=stride, pad=(pt, pl), grid=grid, act=act, p0=p0)
+        return self.conv(stage, name, srcs, w, bias, out, stride=stride, pad=(pt, pl), grid=grid, act=act, p0=p0, p1=p1, in_mode=in_mode)
 
     def conv_relu2(self, stage, name, srcs, prefix, mid, out, stride=1):
         """layers.ConvReLU2 (model/layers.py:308-314): k x 1 stride (s,1), then 1 x k stride (1,s)."""
@@ -1022,7 +1001,8 @@ class Plan:
                 srcs[0].shape[2] % 2 == 0 and srcs[0].shape[3] % 8 == 0 and tuple(wy.shape[2:]) == tuple(wx.shape[2:])[::-1]):
             code = choose_stride2(int(wy.shape[2]), int(wy.shape[0]), int(wy.shape[1]), int(out.shape[2]), int(out.shape[3]), int(out.shape[0]))
             if code:
-                return self._conv_relu2_stride2(stage, name, srcs[0], prefix, mid, out, code // 10, code % 10)
+                f = decode_form("s2k", code)
+                return self._conv_relu2_stride2(stage, name, srcs[0], prefix, mid, out, f.mbw, f.mbw_x)
         self.same_conv(stage, name + ".conv_y", srcs, prefix + ".conv_y.weight", prefix + ".conv_y.bias", mid,
                        stride=(stride, 1))
         return self.same_conv(stage, name + ".conv_x", [mid], prefix + ".conv_x.weight", prefix + ".conv_x.bias", out,
@@ -1065,61 +1045,32 @@ class Plan:
         wt = self.sd[prefix + ".conv2d_t.weight"]
         bias = self.sd[prefix + ".conv2d_t.bias"]
         h, w = srcs[0].shape[2], srcs[0].shape[3]
-        if self.winograd and self.bf16 == 0 and name not in self.schedule_override and tuple(out.shape[2:]) == (2 * h, 2 * w):
+        b8 = self._b8_operands(srcs, out)
+        if not b8 and self.winograd and self.bf16 == 0 and name not in self.schedule_override and tuple(out.shape[2:]) == (2 * h, 2 * w):
             code = choose_winograd_t(int(wt.shape[1]), [int(s_.shape[1]) for s_ in srcs], h, w, int(srcs[0].shape[0]))
-            if code:
-                return self._refine_winograd(stage, name, srcs, wt, bias, out, code % 10, code // 10)
+            if code:        # one mr_convt4x4s2_winograd_f32 launch (csrc/convt_wino.hip: F(2x2,2x2), 9 instead of 16 multiplies per 2x2 parity tile)
+                form = decode_form("t_", code)
+                n, hs, ws, src_channels = self._dense_srcs(srcs)
+                cin, cout = int(wt.shape[0]), int(wt.shape[1])
+                assert cin == sum(src_channels) and tuple(wt.shape[2:]) == (4, 4), (name, wt.shape, src_channels)
+                mbw, tail = form.mbw, form.variant == 2   # tail: 32 a + (1..16) output channels, the tail group by 16-row workgroups (convt_rb_tail)
+                assert not tail or (mbw == 1 and 0 < cout % 32 <= 16), (name, cout)
+                entries = ("mr_wino_t_packed_weight_floats_tail", "mr_wino_t_pack_weights_tail_f32") if tail else ("mr_wino_t_packed_weight_floats", "mr_wino_t_pack_weights_f32")
+                packed = pack_weights(*entries, wt, cout, _int32s(src_channels), len(src_channels), *(() if tail else (mbw,)))
+                assert out.is_contiguous() and tuple(out.shape) == (n, cout, 2 * hs, 2 * ws)
+                d = self._wino_desc([s_.data_ptr() for s_ in srcs], src_channels, n, hs, ws, out, cout, packed, bias, ACT_LEAKY_RELU, LEAKY_SLOPE, mbw, form.variant)
+                lds = self._check_lds(self.lib.mr_convt4x4s2_winograd_lds_bytes(ctypes.byref(d)), f"plan {name} winograd-t")
+                ref = n * hs * ws * cout * cin * 16
+                self._log(name, macs=ref * 9 // 16, ref_macs=ref, mb=mbw, wgs=math.ceil(hs / 8) * math.ceil(ws / 32) * n * 4 * math.ceil(cout / (32 * mbw)),
+                          lds=lds, cout=cout, cin=cin, k=(2, 2), out=(hs, ws), batch=n, phases=4, winograd=mbw, wino_variant=form.variant,
+                          sig="t_" + winograd_signature(cout, src_channels, hs, ws, n),
+                          spec=_conv_spec(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 2, 2), grid=(hs, ws), act=ACT_LEAKY_RELU,
+                                          p0=LEAKY_SLOPE, out_shape=tuple(out.shape), out_step=(2, 2)))
+                self._emit(stage, name, d, _lib.LAUNCH_WINO_T, keep=[out] + list(srcs))
+                return out
         phases = [(wp, pt, pl, py, px) for (py, px), (wp, pt, pl) in transposed_phase_weights(wt).items()]
-        return self.conv(stage, name, srcs, None, bias, out, stride=(1, 1), grid=(h, w), act=ACT_LEAKY_RELU,
-                         p0=LEAKY_SLOPE, out_step=(2, 2), phases=phases)
-
-    def _refine_winograd(self, stage, name, srcs, wt, bias, out, mbw, variant):
-        """One mr_convt4x4s2_winograd_f32 launch (csrc/convt_wino.hip: F(2x2,2x2), 9 instead of 16 multiplies per 2x2 parity tile) in
-        place of the four-phase mr_conv2d_f32 launch of a Refine layer."""
-        lib = self.lib
-        n, _, hs, ws = srcs[0].shape
-        src_channels = [int(s_.shape[1]) for s_ in srcs]
-        cin, cout = int(wt.shape[0]), int(wt.shape[1])
-        assert cin == sum(src_channels) and tuple(wt.shape[2:]) == (4, 4), (name, wt.shape, src_channels)
-        sc = (ctypes.c_int32 * len(src_channels))(*src_channels)
-        w = wt.detach().to(torch.float32).contiguous().cpu()
-        if variant == 2:       # 32 a + (1..16) output channels: the tail group by 16-row workgroups (csrc/convt_wino.hip: convt_rb_tail)
-            assert mbw == 1 and 0 < cout % 32 <= 16, (name, cout)
-            nfl = lib.mr_wino_t_packed_weight_floats_tail(cout, sc, len(src_channels))
-            packed = torch.empty(nfl, dtype=torch.float32)
-            _lib.check(lib.mr_wino_t_pack_weights_tail_f32(w.data_ptr(), cout, sc, len(src_channels), packed.data_ptr()), "mr_wino_t_pack_weights_tail_f32")
-        else:
-            nfl = lib.mr_wino_t_packed_weight_floats(cout, sc, len(src_channels), mbw)
-            packed = torch.empty(nfl, dtype=torch.float32)
-            _lib.check(lib.mr_wino_t_pack_weights_f32(w.data_ptr(), cout, sc, len(src_channels), mbw, packed.data_ptr()), "mr_wino_t_pack_weights_f32")
-        d = WinoDesc()
-        for i, s_ in enumerate(srcs):
-            assert s_.is_contiguous() and tuple(s_.shape[2:]) == (hs, ws) and s_.shape[0] == n
-            d.src[i], d.src_channels[i] = s_.data_ptr(), src_channels[i]
-        d.num_src, d.batch, d.height, d.width = len(srcs), n, hs, ws
-        assert out.is_contiguous() and tuple(out.shape) == (n, cout, 2 * hs, 2 * ws)
-        d.dst, d.out_channels = out.data_ptr(), cout
-        d.packed_weights = self._dev(packed).data_ptr()
-        d.bias = self._dev(bias).data_ptr() if bias is not None else None
-        d.activation, d.act_p0, d.cout_blocks_per_wave, d.variant = ACT_LEAKY_RELU, LEAKY_SLOPE, mbw, variant
-        lds = lib.mr_convt4x4s2_winograd_lds_bytes(ctypes.byref(d))
-        if lds < 0:
-            _lib.check(int(lds), f"plan {name} winograd-t")
-        ref = n * hs * ws * cout * cin * 16
-        wgs = math.ceil(hs / 8) * math.ceil(ws / 32) * n * 4 * math.ceil(cout / (32 * mbw))
-        self.conv_log.append(dict(name=name, macs=ref * 9 // 16, ref_macs=ref, mb=mbw, nb=0, split_k=1, ck=8, waves=8, kws=0, wgs=wgs, lds=int(lds),
-                                  cout=cout, cin=cin, k=(2, 2), out=(hs, ws), batch=n, phases=4, winograd=mbw, wino_variant=variant, bf16=0,
-                                  sig="t_" + winograd_signature(cout, src_channels, hs, ws, n),
-                                  spec=dict(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 2, 2), stride=(1, 1), pad=(0, 0),
-                                            grid=(hs, ws), in_mode=IN_DIRECT, tf=TF_NONE, act=ACT_LEAKY_RELU, p0=LEAKY_SLOPE, p1=0.0, residual=False,
-                                            out_shape=tuple(out.shape), out_step=(2, 2), out_off=(0, 0), phases=None)))
-        self.keep += [d, out] + list(srcs)
-
-        def run(stream):
-            _lib.check(lib.mr_convt4x4s2_winograd_f32(ctypes.byref(d), stream), name)
-        run.native = (_lib.LAUNCH_WINO_T, d, 0)
-        self.stages[stage].append((name, run))
-        return out
+        return (self.conv_b8 if b8 else self.conv)(stage, name, srcs, None, bias, out, grid=(h, w), act=ACT_LEAKY_RELU, p0=LEAKY_SLOPE,
+                                                    out_step=(2, 2), phases=phases)
 
     def upconv(self, stage, name, srcs, wkey, bkey, out):
         """layers.Upconv (model/layers.py:349-356) phase-decomposed on the low-resolution input: the 4 output parities as the 4
@@ -1127,57 +1078,32 @@ class Plan:
         input staged by the direct dwordx4 LDS-DMA path instead of the upsampling dword reads."""
         h, w = srcs[0].shape[2], srcs[0].shape[3]
         cout, cin = self.sd[wkey].shape[:2]
-        if self.winograd and self.bf16 == 0 and name not in self.schedule_override and w % 4 == 0 and tuple(out.shape[2:]) == (2 * h, 2 * w):
+        bias = self.sd[bkey] if bkey else None
+        b8 = self._b8_operands(srcs, out)
+        if not b8 and self.winograd and self.bf16 == 0 and name not in self.schedule_override and w % 4 == 0 and tuple(out.shape[2:]) == (2 * h, 2 * w):
             ukey = "u_" + winograd_signature(int(cout), [int(s_.shape[1]) for s_ in srcs], h, w, int(srcs[0].shape[0]))
-            mbw = WINOGRAD[ukey] if ukey in WINOGRAD else (nearest_form("u_", int(cout), int(cin), h * w, int(srcs[0].shape[0]),
-                                                                        valid=lambda c: c <= math.ceil(int(cout) / 16)) or 0)
-            if mbw:        # measured table (tools/bench_wino1d.py --emit): the 4-multiply kernel, 16 * mbw output channels per workgroup
-                return self._upconv_winograd(stage, name, srcs, self.sd[wkey], self.sd[bkey] if bkey else None, out, mbw)
+            code = WINOGRAD[ukey] if ukey in WINOGRAD else (nearest_form("u_", int(cout), int(cin), h * w, int(srcs[0].shape[0]),
+                                                                         valid=lambda c: decode_form("u_", c).mbw <= math.ceil(int(cout) / 16)) or 0)
+            if code:       # measured table (tools/bench_wino1d.py --emit): one mr_upconv2x2_winograd_f32 launch (csrc/conv1d_wino.hip: 4 multiplies per
+                # 2x2 output block instead of the 9 of the four parity phases / the 16 of the reference), 16 * mbw output channels per workgroup
+                weight, mbw = self.sd[wkey], decode_form("u_", code).mbw
+                n, hs, ws, src_channels = self._dense_srcs(srcs)
+                assert tuple(weight.shape[2:]) == (2, 2) and cin == sum(src_channels), (name, weight.shape)
+                packed = pack_weights("mr_wino1d_packed_weight_floats", "mr_upconv_pack_weights_f32", weight, cout, _int32s(src_channels), len(src_channels), mbw)
+                assert out.is_contiguous() and tuple(out.shape) == (n, cout, 2 * hs, 2 * ws)
+                d = self._wino_desc([s_.data_ptr() for s_ in srcs], src_channels, n, hs, ws, out, cout, packed, bias, ACT_NONE, 0.0, mbw)
+                lds = self._check_lds(self.lib.mr_conv1d3_winograd_lds_bytes(ctypes.byref(d)), f"plan {name} upconv-winograd")
+                ref = n * 4 * hs * ws * cout * cin * 4
+                self._log(name, macs=ref // 4, ref_macs=ref, mb=mbw, wgs=math.ceil(hs / 8) * math.ceil(ws / 32) * n * math.ceil(cout / (16 * mbw)), lds=lds,
+                          cout=cout, cin=cin, k=(2, 2), out=(hs, ws), batch=n, phases=4, winograd=mbw, wino_variant=0, upconv=True,
+                          sig="u_" + winograd_signature(cout, src_channels, hs, ws, n),
+                          spec=_conv_spec(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 2, 2), grid=(hs, ws), out_shape=tuple(out.shape),
+                                          out_step=(2, 2)))
+                self._emit(stage, name, d, _lib.LAUNCH_UPCONV, keep=[out] + list(srcs))
+                return out
         phases = [(wp, 0, 0, py, px) for (py, px), wp in upconv_phase_weights(self.sd[wkey]).items()]
-        return self.conv(stage, name, srcs, None, self.sd[bkey] if bkey else None, out, stride=(1, 1), grid=(h, w), act=ACT_NONE,
-                         out_step=(2, 2), phases=phases, ref_macs=srcs[0].shape[0] * 4 * h * w * cout * cin * 4)
-
-    def _upconv_winograd(self, stage, name, srcs, weight, bias, out, mbw):
-        """One mr_upconv2x2_winograd_f32 launch (csrc/conv1d_wino.hip: 4 multiplies per 2x2 output block instead of the 9 of the four
-        parity phases / the 16 of the reference) for a layers.Upconv."""
-        lib = self.lib
-        n, _, hs, ws = srcs[0].shape
-        src_channels = [int(s_.shape[1]) for s_ in srcs]
-        cout, cin = int(weight.shape[0]), int(weight.shape[1])
-        assert tuple(weight.shape[2:]) == (2, 2) and cin == sum(src_channels), (name, weight.shape)
-        sc = (ctypes.c_int32 * len(src_channels))(*src_channels)
-        w = weight.detach().to(torch.float32).contiguous().cpu()
-        nfl = lib.mr_wino1d_packed_weight_floats(cout, sc, len(src_channels), mbw)
-        packed = torch.empty(nfl, dtype=torch.float32)
-        _lib.check(lib.mr_upconv_pack_weights_f32(w.data_ptr(), cout, sc, len(src_channels), mbw, packed.data_ptr()), "mr_upconv_pack_weights_f32")
-        d = WinoDesc()
-        for i, s_ in enumerate(srcs):
-            assert s_.is_contiguous() and tuple(s_.shape[2:]) == (hs, ws) and s_.shape[0] == n
-            d.src[i], d.src_channels[i] = s_.data_ptr(), src_channels[i]
-        d.num_src, d.batch, d.height, d.width = len(srcs), n, hs, ws
-        assert out.is_contiguous() and tuple(out.shape) == (n, cout, 2 * hs, 2 * ws)
-        d.dst, d.out_channels = out.data_ptr(), cout
-        d.packed_weights = self._dev(packed).data_ptr()
-        d.bias = self._dev(bias).data_ptr() if bias is not None else None
-        d.activation, d.act_p0, d.cout_blocks_per_wave = ACT_NONE, 0.0, mbw
-        lds = lib.mr_conv1d3_winograd_lds_bytes(ctypes.byref(d))
-        if lds < 0:
-            _lib.check(int(lds), f"plan {name} upconv-winograd")
-        ref = n * 4 * hs * ws * cout * cin * 4
-        wgs = math.ceil(hs / 8) * math.ceil(ws / 32) * n * math.ceil(cout / (16 * mbw))
-        self.conv_log.append(dict(name=name, macs=ref // 4, ref_macs=ref, mb=mbw, nb=0, split_k=1, ck=8, waves=8, kws=0, wgs=wgs, lds=int(lds),
-                                  cout=cout, cin=cin, k=(2, 2), out=(hs, ws), batch=n, phases=4, winograd=mbw, wino_variant=0, upconv=True, bf16=0,
-                                  sig="u_" + winograd_signature(cout, src_channels, hs, ws, n),
-                                  spec=dict(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 2, 2), stride=(1, 1), pad=(0, 0),
-                                            grid=(hs, ws), in_mode=IN_DIRECT, tf=TF_NONE, act=ACT_NONE, p0=0.0, p1=0.0, residual=False,
-                                            out_shape=tuple(out.shape), out_step=(2, 2), out_off=(0, 0), phases=None)))
-        self.keep += [d, out] + list(srcs)
-
-        def run(stream):
-            _lib.check(lib.mr_upconv2x2_winograd_f32(ctypes.byref(d), stream), name)
-        run.native = (_lib.LAUNCH_UPCONV, d, 0)
-        self.stages[stage].append((name, run))
-        return out
+        return (self.conv_b8 if b8 else self.conv)(stage, name, srcs, None, bias, out, grid=(h, w), act=ACT_NONE, out_step=(2, 2), phases=phases,
+                                                    ref_macs=srcs[0].shape[0] * 4 * h * w * cout * cin * 4)
 
     # ------------------------------------------------------------------ bf16 MFMA path with B8 activation storage (csrc/conv_b8.hip)
     def alloc_b8(self, name, n, c, h, w):
@@ -1202,7 +1128,6 @@ class Plan:
         cb16 = (cout + 15) // 16
         mb = cb16 if cb16 <= 4 else (4 if cb16 % 4 == 0 else (3 if cb16 % 3 == 0 else 4))
         groups = math.ceil(cb16 / mb)
-        import os
         # 16 x 32 pixel tiles first for the 2-D filters (7 LDS fragment reads per 12 MFMAs instead of 5 per 6: the 3x3 layers of 512x1024
         # gain 7-13 %, the k x 1 / 1 x k layers lose 20-30 %: r04_s4); MR_B8_NB4=0: A/B aid.  (>= 3 output blocks with 4 pixel blocks spill
         # next to the fp32 staging registers.)
@@ -1227,7 +1152,6 @@ class Plan:
                 out_step=(1, 1), phases=None, ref_macs=None):
         """Append one mr_conv2d_b8 launch.  srcs: activations (B8 or dense fp32 NCHW) concatenated on channels; out: B8 or fp32 NCHW.
         phases: optional list of 4 (weight, pad_top, pad_left, out_off_h, out_off_w) run in one launch."""
-        lib = self.lib
         infos = [self._act_info(s_) for s_ in srcs]
         n, hs, ws = infos[0][1], infos[0][3], infos[0][4]
         assert all(i[1] == n and i[3] == hs and i[4] == ws for i in infos) and all(s_.is_contiguous() for s_ in srcs), name
@@ -1245,11 +1169,9 @@ class Plan:
                        self.b8_schedule(cout, out_h, out_w, kh, kw, stride[0], stride[1], n, len(plist), f32_source=f32_source))
         mb, nb, waves = sched8[:3]
         d = B8ConvDesc()
-        sc = (ctypes.c_int32 * len(srcs))(*src_channels)
+        sc = _int32s(src_channels)
         for i, s_ in enumerate(srcs):
             d.src[i], d.src_channels[i], d.src_layout[i] = s_.data_ptr(), src_channels[i], infos[i][0]
-            if "keyframe" in self.buf and s_ is self.buf["keyframe"]:
-                self._input_srcs.append((d, i, "keyframe"))
         d.num_src, d.batch, d.src_h, d.src_w = len(srcs), n, hs, ws
         d.kh, d.kw, d.stride_h, d.stride_w = kh, kw, stride[0], stride[1]
         d.out_h, d.out_w = out_h, out_w
@@ -1260,68 +1182,21 @@ class Plan:
         d.cout_blocks_per_wg, d.pixel_blocks_per_wave, d.waves_per_wg = mb, nb, waves
         d.num_phases = len(plist)
         for i, (wp, pt, pl, oh_, ow_) in enumerate(plist):
-            wc = wp.detach().to(torch.float32).contiguous().cpu()
-            pk, pkw = int(wc.shape[2]), int(wc.shape[3])
-            nbytes = lib.mr_b8_packed_weight_bytes(cout, sc, len(srcs), pk, pkw, mb)
-            assert nbytes > 0, (name, mb)
-            packed = torch.empty(nbytes, dtype=torch.uint8)
-            _lib.check(lib.mr_b8_pack_weights(wc.data_ptr(), cout, sc, len(srcs), pk, pkw, mb, packed.data_ptr()), "mr_b8_pack_weights")
-            dev_w = packed.to(self.device)
+            pk, pkw = int(wp.shape[2]), int(wp.shape[3])
+            dev_w = pack_weights("mr_b8_packed_weight_bytes", "mr_b8_pack_weights", wp, cout, sc, len(srcs), pk, pkw, mb, dtype=torch.uint8).to(self.device)
             self.keep.append(dev_w)
             d.phase_weights[i] = dev_w.data_ptr()
             d.phase_kh[i], d.phase_kw[i] = pk, pkw
             d.phase_pad_top[i], d.phase_pad_left[i], d.phase_out_off_h[i], d.phase_out_off_w[i] = pt, pl, oh_, ow_
-        lds = lib.mr_conv2d_b8_lds_bytes(ctypes.byref(d))
-        if lds < 0:
-            _lib.check(int(lds), f"plan {name} b8 sched={(mb, nb, waves)}")
-        taps = sum(int(p[0].shape[2]) * int(p[0].shape[3]) for p in plist)
-        macs = n * out_h * out_w * cout * cin * taps
-        th = waves * nb // 2
-        wgs = math.ceil(out_h / th) * math.ceil(out_w / 32) * math.ceil(((cout + 15) // 16) / mb) * n * len(plist)
-        self.conv_log.append(dict(name=name, macs=macs, ref_macs=macs if ref_macs is None else ref_macs, mb=mb, nb=nb, split_k=1, ck=32, waves=waves, kws=0,
-                                  wgs=wgs, lds=int(lds), cout=cout, cin=cin, k=(kh, kw), out=(out_h, out_w), batch=n, phases=len(plist), bf16=1, b8=True,
-                                  sig=sig, f32_source=f32_source,
-                                  spec=dict(src_shapes=[(i[1], i[2], i[3], i[4]) for i in infos], src_layouts=[i[0] for i in infos], w_shape=(cout, cin, kh, kw),
-                                            stride=tuple(stride), pad=tuple(pad), grid=(out_h, out_w), act=act, p0=p0, out_layout=olay,
-                                            out_step=tuple(out_step))))
-        self.keep += [d, out, sc] + list(srcs)
-
-        def run(stream):
-            _lib.check(lib.mr_conv2d_b8(ctypes.byref(d), stream), name)
-        run.native = (_lib.LAUNCH_CONV_B8, d, 0)
-        self.stages[stage].append((name, run))
+        lds = self._check_lds(self.lib.mr_conv2d_b8_lds_bytes(ctypes.byref(d)), f"plan {name} b8 sched={(mb, nb, waves)}")
+        macs = n * out_h * out_w * cout * cin * sum(int(p[0].shape[2]) * int(p[0].shape[3]) for p in plist)
+        self._log(name, macs=macs, ref_macs=ref_macs, mb=mb, nb=nb, ck=32, waves=waves,
+                  wgs=math.ceil(out_h / (waves * nb // 2)) * math.ceil(out_w / 32) * math.ceil(((cout + 15) // 16) / mb) * n * len(plist), lds=lds,
+                  cout=cout, cin=cin, k=(kh, kw), out=(out_h, out_w), batch=n, phases=len(plist), bf16=1, b8=True, f32_source=f32_source, sig=sig,
+                  spec=dict(src_shapes=[(i[1], i[2], i[3], i[4]) for i in infos], src_layouts=[i[0] for i in infos], w_shape=(cout, cin, kh, kw),
+                            stride=tuple(stride), pad=tuple(pad), grid=(out_h, out_w), act=act, p0=p0, out_layout=olay, out_step=tuple(out_step)))
+        self._emit(stage, name, d, _lib.LAUNCH_CONV_B8, keep=[out, sc] + list(srcs))
         return out
-
-    def same_conv_b8(self, stage, name, srcs, wkey, bkey, out, *, stride=(1, 1), act=ACT_LEAKY_RELU, p0=LEAKY_SLOPE):
-        """PadSameConv2d + Conv2d (+ activation), model/layers.py:241-252,329-335, on the B8 kernel."""
-        w = self.sd[wkey]
-        _, _, _, hs, ws = self._act_info(srcs[0])
-        kh, kw = w.shape[2], w.shape[3]
-        pt, _ = same_pad(hs, kh, stride[0])
-        pl, _ = same_pad(ws, kw, stride[1])
-        grid = (math.ceil(hs / stride[0]), math.ceil(ws / stride[1]))
-        return self.conv_b8(stage, name, srcs, w, self.sd[bkey] if bkey else None, out, stride=stride, pad=(pt, pl), grid=grid, act=act, p0=p0)
-
-    def conv_relu2_b8(self, stage, name, srcs, prefix, mid, out, stride=1):
-        """layers.ConvReLU2 (model/layers.py:308-314): k x 1 stride (s,1), then 1 x k stride (1,s)."""
-        self.same_conv_b8(stage, name + ".conv_y", srcs, prefix + ".conv_y.weight", prefix + ".conv_y.bias", mid, stride=(stride, 1))
-        return self.same_conv_b8(stage, name + ".conv_x", [mid], prefix + ".conv_x.weight", prefix + ".conv_x.bias", out, stride=(1, stride))
-
-    def refine_b8(self, stage, name, srcs, prefix, out):
-        """layers.Refine (model/layers.py:389-397): the four output parities as the four phases of one launch."""
-        wt = self.sd[prefix + ".conv2d_t.weight"]
-        _, _, _, h, w = self._act_info(srcs[0])
-        phases = [(wp, pt, pl, py, px) for (py, px), (wp, pt, pl) in transposed_phase_weights(wt).items()]
-        return self.conv_b8(stage, name, srcs, None, self.sd[prefix + ".conv2d_t.bias"], out, grid=(h, w), act=ACT_LEAKY_RELU, p0=LEAKY_SLOPE,
-                            out_step=(2, 2), phases=phases)
-
-    def upconv_b8(self, stage, name, srcs, wkey, bkey, out):
-        """layers.Upconv (model/layers.py:349-356) phase-decomposed on the low-resolution input (upconv_phase_weights)."""
-        _, n, _, h, w = self._act_info(srcs[0])
-        cout, cin = self.sd[wkey].shape[:2]
-        phases = [(wp, 0, 0, py, px) for (py, px), wp in upconv_phase_weights(self.sd[wkey]).items()]
-        return self.conv_b8(stage, name, srcs, None, self.sd[bkey] if bkey else None, out, grid=(h, w), act=ACT_NONE, out_step=(2, 2), phases=phases,
-                            ref_macs=n * 4 * h * w * cout * cin * 4)
 
     def add(self, stage, name, fn):
         self.stages[stage].append((name, fn))
@@ -1399,32 +1274,21 @@ class Plan:
         kinv, proj, depths = self.buf["kinv"], self.buf["proj"], self.buf["depths"]
         cv_ref = self.ref(cv)
 
-        self._sfcv_b8_ptrs = None          # bf16 MFMA mode: pointer array of the B8 copies of the single-frame volumes (see _build_mask_depth_b8)
+        self._sfcv_b8_ptrs = None          # B8 storage: pointer array of the B8 copies of the single-frame volumes (sfcv_b8)
 
         def run_cv(stream):
             pix = self.buf["pix_depths"].data_ptr() if self.pix_depths_on else None     # data_dict["cv_depths"], :181-182
-            if self._sfcv_b8_ptrs is not None and self.lean_outputs:
-                _lib.check(lib.mr_cost_volume_b8_lean_f32(self.input_ptr["keyframe"], frame_ptrs, F, kinv.data_ptr(), proj.data_ptr(),
-                                                          depths.data_ptr(), B, D, H, W, self.alpha, self.cw, self.cv_mode, pix,
-                                                          cv_ref.ptr(), sfcv_ptrs, self._sfcv_b8_ptrs, stream), "mr_cost_volume_b8_lean_f32")
-            elif self._sfcv_b8_ptrs is not None:
-                _lib.check(lib.mr_cost_volume_b8_f32(self.input_ptr["keyframe"], frame_ptrs, F, kinv.data_ptr(), proj.data_ptr(),
-                                                     depths.data_ptr(), B, D, H, W, self.alpha, self.cw, self.cv_mode, pix,
-                                                     cv_ref.ptr(), sfcv_ptrs, self._sfcv_b8_ptrs, stream), "mr_cost_volume_b8_f32")
+            mult = 1 if self.sfcv_mult_mask else 0
+            if self._sfcv_b8_ptrs is not None:         # B8 storage: the single-frame volumes written a second time, in B8 (sfcv_b8)
+                fn, args = (lib.mr_cost_volume_b8_lean_f32 if self.lean_outputs else lib.mr_cost_volume_b8_f32), (cv_ref.ptr(), sfcv_ptrs, self._sfcv_b8_ptrs)
             elif self.cv_patch_size == 3 and self.cv_separable and self.sfcv_mult_mask:
-                _lib.check(lib.mr_cost_volume_relaxed_f32(self.input_ptr["keyframe"], frame_ptrs, F, kinv.data_ptr(), proj.data_ptr(),
-                                                          depths.data_ptr(), B, D, H, W, self.alpha, self.cw, self.cv_mode, pix,
-                                                          cv_ref.ptr(), sfcv_ptrs, stream), "mr_cost_volume_relaxed_f32")
+                fn, args = lib.mr_cost_volume_relaxed_f32, (cv_ref.ptr(), sfcv_ptrs)
             elif self.cv_patch_size == 3:
-                _lib.check(lib.mr_cost_volume_mode_f32(self.input_ptr["keyframe"], frame_ptrs, F, kinv.data_ptr(), proj.data_ptr(),
-                                                       depths.data_ptr(), B, D, H, W, self.alpha, self.cw, self.cv_mode, pix,
-                                                       1 if self.sfcv_mult_mask else 0,
-                                                       cv_ref.ptr(), sfcv_ptrs, stream), "mr_cost_volume_mode_f32")
+                fn, args = lib.mr_cost_volume_mode_f32, (mult, cv_ref.ptr(), sfcv_ptrs)
             else:
-                _lib.check(lib.mr_cost_volume_patch_f32(self.input_ptr["keyframe"], frame_ptrs, F, kinv.data_ptr(), proj.data_ptr(),
-                                                        depths.data_ptr(), B, D, H, W, self.alpha, self.cw, self.cv_mode, pix,
-                                                        1 if self.sfcv_mult_mask else 0, self.cv_patch_size,
-                                                        cv_ref.ptr(), sfcv_ptrs, stream), "mr_cost_volume_patch_f32")
+                fn, args = lib.mr_cost_volume_patch_f32, (mult, self.cv_patch_size, cv_ref.ptr(), sfcv_ptrs)
+            _lib.check(fn(self.input_ptr["keyframe"], frame_ptrs, F, kinv.data_ptr(), proj.data_ptr(), depths.data_ptr(), B, D, H, W, self.alpha,
+                          self.cw, self.cv_mode, pix, *args, stream), fn.__name__)
         if self.no_cv:                     # :682-686: zero volumes, never written (the in-place mask multiply keeps 0)
             sfcv.zero_()
             cv.zero_()
@@ -1433,10 +1297,13 @@ class Plan:
         with_mask = self.pretrain_mode in (0, 2)
         with_depth = self.pretrain_mode != 2
         self.feats = feats
-        if (self.b8 and self.pretrain_mode == 0 and not self.no_cv and not self.simple_mask and self.mask_use_cv and self.mask_use_feats and
-                self.one_channel_kernels):
-            return self._build_mask_depth_b8(feats, sfcv, cv, kf)
-        self.b8 = False                    # the option variants keep the fp32-storage path
+        # bf16 MFMA mode, full model: the activations BETWEEN the convolutions of the mask and depth nets are stored in B8 (alloc_b8; every
+        # layer that reads or writes one runs on conv_b8).  Dense fp32 stay: what the path hands out (single-frame / fused volumes, image
+        # features, `cv_mask`, the four depth scales) and the maps the HBM-bound one-channel kernels read (classifier input, the four head
+        # inputs).  The option variants keep fp32 storage.
+        b8 = self.b8 = (self.b8 and self.pretrain_mode == 0 and not self.no_cv and not self.simple_mask and self.mask_use_cv and
+                        self.mask_use_feats and self.one_channel_kernels)
+        store = self.alloc_b8 if b8 else self.alloc        # an activation between two convolutions
 
         # ---------------- MaskModule (monorec_model.py:345-385), frames batched as F*B ----------------
         am = "att_module"
@@ -1457,49 +1324,71 @@ class Plan:
         elif not self.mask_use_cv:           # :352-353 `sfcv * 0`: every frame is the same zero input, so one pass stands for all
             x = self.alloc("mask.zero_input", B, D, H, W).zero_()
             FM = 1
+        elif b8 and D in (32, 48, 64) and self.cv_patch_size == 3 and self.sfcv_mult_mask:
+            # B8: the fusion kernel of the cost volume writes every single-frame volume a second time in B8 (free: it is VALU-bound), so the
+            # first mask-encoder layer reads 2 bytes per element by LDS-DMA instead of staging 4-byte planes through registers
+            x = self.alloc_b8("sfcv_b8", F * B, D, H, W)
+            per_frame = B * (D // 8) * H * W * 16
+            self._sfcv_b8_ptrs = (ctypes.c_void_p * F)(*[x.data_ptr() + f * per_frame for f in range(F)])
+            self.keep.append(self._sfcv_b8_ptrs)
+        # nn.MaxPool2d(2) of the next stage and the maximum over the frames (B8: on planes of 8 channels)
+        pool_max, frame_max = ((lib.mr_pool2x2_framemax_b8, lib.mr_max_over_frames_b8) if b8 else
+                               (lib.mr_pool2x2_framemax_f32, lib.mr_max_over_frames_f32))
         cvf = []
         for i in range(5 if with_mask else 0):
             hi, wi = H >> i, W >> i
             i0, i1 = (0, 1) if i == 0 else (1, 2)       # index 0 of stages 1-4 is the MaxPool
-            a = self.alloc(f"mask.enc{i}.a", FM * B, enc_ch[i], hi, wi)
-            xo = self.alloc(f"mask.enc{i}.x", FM * B, enc_ch[i], hi, wi)
+            a = store(f"mask.enc{i}.a", FM * B, enc_ch[i], hi, wi)
+            xo = store(f"mask.enc{i}.x", FM * B, enc_ch[i], hi, wi)
             self.same_conv(st, f"mask.enc{i}.0", first_srcs if (i == 0 and first_srcs) else [x], f"{am}.enc.{i}.{i0}.conv.weight",
                            f"{am}.enc.{i}.{i0}.conv.bias", a)
             self.same_conv(st, f"mask.enc{i}.1", [a], f"{am}.enc.{i}.{i1}.conv.weight", f"{am}.enc.{i}.{i1}.conv.bias", xo)
-            m = self.alloc(f"mask.cvf{i}", B, enc_ch[i], hi, wi)
+            m = store(f"mask.cvf{i}", B, enc_ch[i], hi, wi)
             cvf.append(m)
+            planes = B * ((enc_ch[i] + 7) // 8 if b8 else enc_ch[i])
             if i < 4:
-                # nn.MaxPool2d(2) of the next stage (its own HBM-bound pass: the conv then stages by LDS-DMA) and the
-                # maximum over the frames, both from one read of this stage's output
-                xp = self.alloc(f"mask.enc{i + 1}.pool", FM * B, enc_ch[i], hi // 2, wi // 2)
+                # the pooling of the next stage (its own HBM-bound pass: the conv then stages by LDS-DMA) and the maximum over the frames,
+                # both from one read of this stage's output
+                xp = store(f"mask.enc{i + 1}.pool", FM * B, enc_ch[i], hi // 2, wi // 2)
 
-                def run_pool_max(stream, src=xo, dst=xp, mx=m, planes=B * enc_ch[i], hh_=hi, ww_=wi):
-                    _lib.check(lib.mr_pool2x2_framemax_f32(src.data_ptr(), dst.data_ptr(), mx.data_ptr(), FM, planes, hh_, ww_,
-                                                           stream), "mr_pool2x2_framemax_f32")
+                def run_pool_max(stream, src=xo, dst=xp, mx=m, planes=planes, hh_=hi, ww_=wi):
+                    _lib.check(pool_max(src.data_ptr(), dst.data_ptr(), mx.data_ptr(), FM, planes, hh_, ww_, stream), pool_max.__name__)
                 self.add(st, f"mask.poolmax{i}", run_pool_max)
                 x = xp
             else:
-                def run_max(stream, src=xo, dst=m, count=B * enc_ch[i] * hi * wi):
-                    _lib.check(lib.mr_max_over_frames_f32(src.data_ptr(), dst.data_ptr(), FM, count, stream),
-                               "mr_max_over_frames_f32")
+                def run_max(stream, src=xo, dst=m, count=planes * hi * wi):
+                    _lib.check(frame_max(src.data_ptr(), dst.data_ptr(), FM, count, stream), frame_max.__name__)
                 self.add(st, f"mask.max{i}", run_max)
         st = "main"
-        mfeats = feats if self.mask_use_feats else [self.alloc(f"mask.zero_feat{i}", *feats[i].shape).zero_() for i in range(4)]   # :354-355
+        dfeats = list(feats)               # the image features as the decoders read them
+        if b8 and self.b8_feature_copies:
+            # B8: each image feature (fp32 output of the ResNet trunk) is read by TWO decoder layers: one conversion launch per feature map and
+            # both readers take the B8 copy by LDS-DMA instead of staging 4-byte planes through registers (round 6: depth.dec3 157 us of which
+            # 148 are that staging path, profiles/r06_c5bf16_b8_ablation.txt).  Same round-to-nearest-even as the staging path: bit-identical.
+            for i in range(4):
+                dfeats[i] = self.alloc_b8(f"feat{i}_b8", B, int(feats[i].shape[1]), int(feats[i].shape[2]), int(feats[i].shape[3]))
+
+                def run_fb(stream, src=self.ref(feats[i]), dst=dfeats[i], c_=int(feats[i].shape[1]), hw_=int(feats[i].shape[2] * feats[i].shape[3])):
+                    _lib.check(lib.mr_f32_nchw_to_b8(src.ptr(), dst.data_ptr(), B, c_, hw_, stream), "mr_f32_nchw_to_b8")
+                self.add(st, f"feat{i}.to_b8", run_fb)
+        mfeats = dfeats if self.mask_use_feats else [self.alloc(f"mask.zero_feat{i}", *feats[i].shape).zero_() for i in range(4)]   # :354-355
         x_srcs = [cvf[4], mfeats[3]] if with_mask else None                          # :372
         for i in range(4 if with_mask else 0):
             hi, wi = H >> (3 - i), W >> (3 - i)
             up_ch = sd[f"{am}.dec.{i}.0.conv.weight"].shape[0]
-            dec_ch = {i: sd[f"{am}.dec.{i}.1.conv.weight"].shape[0]}
-            u = self.alloc(f"mask.dec{i}.up", B, up_ch, hi, wi)
+            dec_ch = sd[f"{am}.dec.{i}.1.conv.weight"].shape[0]
+            u = store(f"mask.dec{i}.up", B, up_ch, hi, wi)
             self.upconv(st, f"mask.dec{i}.0", x_srcs, f"{am}.dec.{i}.0.conv.weight", f"{am}.dec.{i}.0.conv.bias", u)   # layers.py:349-356
             cat = [cvf[3 - i], u] if i == 3 else [cvf[3 - i], mfeats[2 - i], u]      # :374-380
-            a = self.alloc(f"mask.dec{i}.a", B, dec_ch[i], hi, wi)
-            xo = self.alloc(f"mask.dec{i}.x", B, dec_ch[i], hi, wi)
+            a = store(f"mask.dec{i}.a", B, dec_ch, hi, wi)
+            # (the last decoder map feeds the classifier kernel, csrc/heads.hip, which reads dense fp32)
+            xo = (self.alloc if i == 3 else store)(f"mask.dec{i}.x", B, dec_ch, hi, wi)
             self.same_conv(st, f"mask.dec{i}.1", cat, f"{am}.dec.{i}.1.conv.weight", f"{am}.dec.{i}.1.conv.bias", a)
             self.same_conv(st, f"mask.dec{i}.2", [a], f"{am}.dec.{i}.2.conv.weight", f"{am}.dec.{i}.2.conv.bias", xo)
             x_srcs = [xo]
         cv_mask = self.alloc("cv_mask", B, 1, H, W)
         mask_applied = False
+        cvb = None                         # B8: the masked volume the depth net reads, written by the classifier kernel
         if with_mask and self.one_channel_kernels:
             # classifier (1x1 conv -> 1 channel, sigmoid, :340-343) and - in the full model - the mask multiply of :713 in one
             # HBM-bound launch (csrc/heads.hip) instead of a 1-of-16-rows MFMA launch + mr_apply_mask_f32
@@ -1509,11 +1398,17 @@ class Plan:
             mask_applied = with_depth and self.pretrain_mode == 0
             cvp = cv_ref if mask_applied else None
             mask_ref = self.ref(cv_mask)
+            if b8 and D % 16 == 0:
+                cvb = self.alloc_b8("cost_volume_b8", B, D, H, W)
 
             def run_classifier(stream, feat=feat, cw_=cw_, cb_=cb_, cvp=cvp):
-                _lib.check(lib.mr_mask_classifier_f32(feat.data_ptr(), cw_.data_ptr(), cb_.data_ptr(), B, int(feat.shape[1]), H * W,
-                                                      mask_ref.ptr(), cvp.ptr() if cvp is not None else None, D, stream),
-                           "mr_mask_classifier_f32")
+                if cvb is not None:
+                    _lib.check(lib.mr_mask_classifier_b8_f32(feat.data_ptr(), cw_.data_ptr(), cb_.data_ptr(), B, int(feat.shape[1]), H * W,
+                                                             mask_ref.ptr(), cvp.ptr(), D, cvb.data_ptr(), stream), "mr_mask_classifier_b8_f32")
+                else:
+                    _lib.check(lib.mr_mask_classifier_f32(feat.data_ptr(), cw_.data_ptr(), cb_.data_ptr(), B, int(feat.shape[1]), H * W,
+                                                          mask_ref.ptr(), cvp.ptr() if cvp is not None else None, D, stream),
+                               "mr_mask_classifier_f32")
             self.add(st, "mask.classifier", run_classifier)
             self.aux_log.append(dict(name="mask.classifier", ref_macs=B * H * W * int(feat.shape[1])))
         elif with_mask:
@@ -1521,7 +1416,6 @@ class Plan:
                            act=ACT_SIGMOID)
         else:
             cv_mask.zero_()                # pretrain_mode 1, eval (:708); pretrain_mode 3: the model copies data_dict["mvobj_mask"] in (:711)
-        self.feats = feats
         self.preds = None
         if not with_depth:                 # pretrain_mode 2 (:693, :712, :723-724): mask only
             return
@@ -1542,16 +1436,16 @@ class Plan:
         dch = [int(sd[f"{dm}.dec.0.conv2d_t.weight"].shape[1]), int(sd[f"{dm}.dec.1.0.conv2d_t.weight"].shape[1]),
                int(sd[f"{dm}.dec.2.0.conv2d_t.weight"].shape[1]), int(sd[f"{dm}.dec.3.conv2d_t.weight"].shape[1]),
                int(sd[f"{dm}.dec.4.0.conv_y.weight"].shape[0]), int(sd[f"{dm}.dec.4.2.weight"].shape[0])]
-        x_srcs = [cv, kf]                                                            # :531
+        x_srcs = [cv if cvb is None else cvb, kf]                                    # :531
         dfe = []
         hh, ww = H, W
         for i, (ch, _, s) in enumerate(enc_spec):
             h2, w2 = hh // s, ww // s
-            mid0 = self.alloc(f"depth.enc{i}.0.mid", B, ch, h2, ww)
-            o0 = self.alloc(f"depth.enc{i}.0.out", B, ch, h2, w2)
+            mid0 = store(f"depth.enc{i}.0.mid", B, ch, h2, ww)
+            o0 = store(f"depth.enc{i}.0.out", B, ch, h2, w2)
             self.conv_relu2(st, f"depth.enc{i}.0", x_srcs, f"{dm}.enc.{i}.0", mid0, o0, stride=s)
-            mid1 = self.alloc(f"depth.enc{i}.1.mid", B, ch, h2, w2)
-            o1 = self.alloc(f"depth.enc{i}.1.out", B, ch, h2, w2)
+            mid1 = store(f"depth.enc{i}.1.mid", B, ch, h2, w2)
+            o1 = store(f"depth.enc{i}.1.out", B, ch, h2, w2)
             self.conv_relu2(st, f"depth.enc{i}.1", [o0], f"{dm}.enc.{i}.1", mid1, o1)
             dfe.append(o1)
             x_srcs, hh, ww = [o1], h2, w2
@@ -1561,8 +1455,7 @@ class Plan:
         heads = []                         # (predictor index, input, output): launched together behind the decoder
 
         def head(idx, src, scale_slot):
-            hh_, ww_ = src.shape[2], src.shape[3]
-            p = self.alloc(f"pred{scale_slot}", B, 1, hh_, ww_)
+            p = self.alloc(f"pred{scale_slot}", B, 1, src.shape[2], src.shape[3])
             if self.one_channel_kernels:
                 heads.append((idx, src, p))
             else:
@@ -1570,25 +1463,26 @@ class Plan:
                                p, act=ACT_ABS_TANH_AFFINE, p0=lo, p1=hi_)            # :556 + :717
             preds[scale_slot] = p
 
+        # (the head inputs r0, x1, x2, x4 are dense fp32 in both storage modes: the head kernel reads them)
         r0 = self.alloc("depth.dec0", B, dch[0], H // 8, W // 8)
         self.refine(st, "depth.dec0", [dfe[4]], f"{dm}.dec.0", r0)
         head(0, r0, 3)
-        r1 = self.alloc("depth.dec1.t", B, dch[1], H // 4, W // 4)
-        self.refine(st, "depth.dec1.0", [dfe[3], feats[2], r0], f"{dm}.dec.1.0", r1)  # :545
-        m1 = self.alloc("depth.dec1.mid", B, dch[1], H // 4, W // 4)
+        r1 = store("depth.dec1.t", B, dch[1], H // 4, W // 4)
+        self.refine(st, "depth.dec1.0", [dfe[3], dfeats[2], r0], f"{dm}.dec.1.0", r1)  # :545
+        m1 = store("depth.dec1.mid", B, dch[1], H // 4, W // 4)
         x1 = self.alloc("depth.dec1", B, dch[1], H // 4, W // 4)
         self.conv_relu2(st, "depth.dec1.1", [r1], f"{dm}.dec.1.1", m1, x1)
         head(1, x1, 2)
-        r2 = self.alloc("depth.dec2.t", B, dch[2], H // 2, W // 2)
-        self.refine(st, "depth.dec2.0", [dfe[2], feats[1], x1], f"{dm}.dec.2.0", r2)
-        m2 = self.alloc("depth.dec2.mid", B, dch[2], H // 2, W // 2)
+        r2 = store("depth.dec2.t", B, dch[2], H // 2, W // 2)
+        self.refine(st, "depth.dec2.0", [dfe[2], dfeats[1], x1], f"{dm}.dec.2.0", r2)
+        m2 = store("depth.dec2.mid", B, dch[2], H // 2, W // 2)
         x2 = self.alloc("depth.dec2", B, dch[2], H // 2, W // 2)
         self.conv_relu2(st, "depth.dec2.1", [r2], f"{dm}.dec.2.1", m2, x2)
         head(2, x2, 1)
-        x3 = self.alloc("depth.dec3", B, dch[3], H, W)
-        self.refine(st, "depth.dec3", [dfe[1], feats[0], x2], f"{dm}.dec.3", x3)
-        m4 = self.alloc("depth.dec4.mid", B, dch[4], H, W)
-        x4a = self.alloc("depth.dec4.a", B, dch[4], H, W)
+        x3 = store("depth.dec3", B, dch[3], H, W)
+        self.refine(st, "depth.dec3", [dfe[1], dfeats[0], x2], f"{dm}.dec.3", x3)
+        m4 = store("depth.dec4.mid", B, dch[4], H, W)
+        x4a = store("depth.dec4.a", B, dch[4], H, W)
         self.conv_relu2(st, "depth.dec4.0", [dfe[0], x3], f"{dm}.dec.4.0", m4, x4a)   # :543
         x4 = self.alloc("depth.dec4", B, dch[5], H, W)
         self.same_conv(st, "depth.dec4.2", [x4a], f"{dm}.dec.4.2.weight", f"{dm}.dec.4.2.bias", x4)
@@ -1611,153 +1505,6 @@ class Plan:
             self.add(st, "depth.heads", run_heads)
             self.aux_log.append(dict(name="depth.heads", ref_macs=sum(int(s_.shape[0] * s_.shape[1] * s_.shape[2] * s_.shape[3]) * 9
                                                                        for _, s_, _ in heads)))
-        self.preds = preds
-
-    def _build_mask_depth_b8(self, feats, sfcv, cv, kf):
-        """MaskModule (monorec_model.py:345-385) and DepthModule (:526-557) of the full model in the bf16 MFMA mode with B8 activation
-        storage (csrc/conv_b8.hip).  Dense fp32 stay: what the path hands out (single-frame / fused volumes, image features, `cv_mask`,
-        the four depth scales) and the maps the HBM-bound one-channel kernels read (classifier input; the four head inputs)."""
-        B, H, W, F, D = self.B, self.H, self.W, self.F, self.D
-        sd, lib = self.sd, self.lib
-        am, dm = "att_module", "depth_module"
-        st = "cv"
-        enc_ch = (int(sd[f"{am}.enc.0.0.conv.weight"].shape[0]), 48, 64, 96, 96)
-        enc_ch = tuple(int(sd[f"{am}.enc.{i}.{0 if i == 0 else 1}.conv.weight"].shape[0]) for i in range(5))
-        x = sfcv.view(F * B, D, H, W)
-        if D in (32, 48, 64) and self.cv_patch_size == 3 and self.sfcv_mult_mask:
-            # the fusion kernel of the cost volume writes every single-frame volume a second time in B8 (free: it is VALU-bound), so the
-            # first mask-encoder layer reads 2 bytes per element by LDS-DMA instead of staging 4-byte planes through registers
-            xb = self.alloc_b8("sfcv_b8", F * B, D, H, W)
-            per_frame = B * (D // 8) * H * W * 16
-            ptrs = (ctypes.c_void_p * F)(*[xb.data_ptr() + f * per_frame for f in range(F)])
-            self.keep.append(ptrs)
-            self._sfcv_b8_ptrs = ptrs
-            x = xb
-        cvf = []
-        for i in range(5):
-            hi, wi = H >> i, W >> i
-            i0, i1 = (0, 1) if i == 0 else (1, 2)       # index 0 of stages 1-4 is the MaxPool
-            a = self.alloc_b8(f"mask.enc{i}.a", F * B, enc_ch[i], hi, wi)
-            xo = self.alloc_b8(f"mask.enc{i}.x", F * B, enc_ch[i], hi, wi)
-            self.same_conv_b8(st, f"mask.enc{i}.0", [x], f"{am}.enc.{i}.{i0}.conv.weight", f"{am}.enc.{i}.{i0}.conv.bias", a)
-            self.same_conv_b8(st, f"mask.enc{i}.1", [a], f"{am}.enc.{i}.{i1}.conv.weight", f"{am}.enc.{i}.{i1}.conv.bias", xo)
-            m = self.alloc_b8(f"mask.cvf{i}", B, enc_ch[i], hi, wi)
-            cvf.append(m)
-            planes = B * ((enc_ch[i] + 7) // 8)
-            if i < 4:
-                xp = self.alloc_b8(f"mask.enc{i + 1}.pool", F * B, enc_ch[i], hi // 2, wi // 2)
-
-                def run_pool_max(stream, src=xo, dst=xp, mx=m, planes=planes, hh_=hi, ww_=wi):
-                    _lib.check(lib.mr_pool2x2_framemax_b8(src.data_ptr(), dst.data_ptr(), mx.data_ptr(), F, planes, hh_, ww_, stream),
-                               "mr_pool2x2_framemax_b8")
-                self.add(st, f"mask.poolmax{i}", run_pool_max)
-                x = xp
-            else:
-                def run_max(stream, src=xo, dst=m, count=planes * hi * wi):
-                    _lib.check(lib.mr_max_over_frames_b8(src.data_ptr(), dst.data_ptr(), F, count, stream), "mr_max_over_frames_b8")
-                self.add(st, f"mask.max{i}", run_max)
-        st = "main"
-        # the image features (fp32 outputs of the ResNet trunk) are each read by TWO decoder layers: one conversion launch per feature map and
-        # both readers take the B8 copy by LDS-DMA instead of staging 4-byte planes through registers (round 6: depth.dec3 157 us of which 148
-        # are that staging path, profiles/r06_c5bf16_b8_ablation.txt).  Same round-to-nearest-even as the staging path: results bit-identical.
-        fsrc = list(feats)
-        if self.b8_feature_copies:
-            for i in range(4):
-                fb = self.alloc_b8(f"feat{i}_b8", B, int(feats[i].shape[1]), int(feats[i].shape[2]), int(feats[i].shape[3]))
-
-                def run_fb(stream, src=self.ref(feats[i]), dst=fb, c_=int(feats[i].shape[1]), hw_=int(feats[i].shape[2] * feats[i].shape[3])):
-                    _lib.check(lib.mr_f32_nchw_to_b8(src.ptr(), dst.data_ptr(), B, c_, hw_, stream), "mr_f32_nchw_to_b8")
-                self.add(st, f"feat{i}.to_b8", run_fb)
-                fsrc[i] = fb
-        feats_out, feats = feats, fsrc
-        x_srcs = [cvf[4], feats[3]]                                                  # :372
-        for i in range(4):
-            hi, wi = H >> (3 - i), W >> (3 - i)
-            up_ch = int(sd[f"{am}.dec.{i}.0.conv.weight"].shape[0])
-            dec_ch = int(sd[f"{am}.dec.{i}.1.conv.weight"].shape[0])
-            u = self.alloc_b8(f"mask.dec{i}.up", B, up_ch, hi, wi)
-            self.upconv_b8(st, f"mask.dec{i}.0", x_srcs, f"{am}.dec.{i}.0.conv.weight", f"{am}.dec.{i}.0.conv.bias", u)   # layers.py:349-356
-            cat = [cvf[3 - i], u] if i == 3 else [cvf[3 - i], feats[2 - i], u]       # :374-380
-            a = self.alloc_b8(f"mask.dec{i}.a", B, dec_ch, hi, wi)
-            # the last decoder map feeds the classifier kernel (csrc/heads.hip), which reads dense fp32
-            xo = self.alloc(f"mask.dec{i}.x", B, dec_ch, hi, wi) if i == 3 else self.alloc_b8(f"mask.dec{i}.x", B, dec_ch, hi, wi)
-            self.same_conv_b8(st, f"mask.dec{i}.1", cat, f"{am}.dec.{i}.1.conv.weight", f"{am}.dec.{i}.1.conv.bias", a)
-            self.same_conv_b8(st, f"mask.dec{i}.2", [a], f"{am}.dec.{i}.2.conv.weight", f"{am}.dec.{i}.2.conv.bias", xo)
-            x_srcs = [xo]
-        cv_mask = self.alloc("cv_mask", B, 1, H, W)
-        feat = x_srcs[0]
-        cw_ = self._dev(sd[f"{am}.classifier.0.weight"].reshape(-1))
-        cb_ = self._dev(sd[f"{am}.classifier.0.bias"].reshape(-1))
-        cv_ref, mask_ref = self.ref(cv), self.ref(cv_mask)
-        cvb = self.alloc_b8("cost_volume_b8", B, D, H, W) if D % 16 == 0 else None     # the masked volume for the depth net, B8 copy
-
-        def run_classifier(stream, feat=feat, cw_=cw_, cb_=cb_):
-            if cvb is not None:
-                _lib.check(lib.mr_mask_classifier_b8_f32(feat.data_ptr(), cw_.data_ptr(), cb_.data_ptr(), B, int(feat.shape[1]), H * W,
-                                                         mask_ref.ptr(), cv_ref.ptr(), D, cvb.data_ptr(), stream), "mr_mask_classifier_b8_f32")
-            else:
-                _lib.check(lib.mr_mask_classifier_f32(feat.data_ptr(), cw_.data_ptr(), cb_.data_ptr(), B, int(feat.shape[1]), H * W,
-                                                      mask_ref.ptr(), cv_ref.ptr(), D, stream), "mr_mask_classifier_f32")
-        self.add(st, "mask.classifier", run_classifier)
-        self.aux_log.append(dict(name="mask.classifier", ref_macs=B * H * W * int(feat.shape[1])))
-
-        # ---------------- DepthModule ----------------
-        enc_spec = tuple((int(sd[f"{dm}.enc.{i}.0.conv_y.weight"].shape[0]), k, s_)
-                         for i, (k, s_) in enumerate(((7, 1), (7, 2), (5, 2), (5, 2), (3, 2))))
-        dch = [int(sd[f"{dm}.dec.0.conv2d_t.weight"].shape[1]), int(sd[f"{dm}.dec.1.0.conv2d_t.weight"].shape[1]),
-               int(sd[f"{dm}.dec.2.0.conv2d_t.weight"].shape[1]), int(sd[f"{dm}.dec.3.conv2d_t.weight"].shape[1]),
-               int(sd[f"{dm}.dec.4.0.conv_y.weight"].shape[0]), int(sd[f"{dm}.dec.4.2.weight"].shape[0])]
-        x_srcs = [cv if cvb is None else cvb, kf]                                    # :531
-        dfe = []
-        hh, ww = H, W
-        for i, (ch, _, s_) in enumerate(enc_spec):
-            h2, w2 = hh // s_, ww // s_
-            mid0 = self.alloc_b8(f"depth.enc{i}.0.mid", B, ch, h2, ww)
-            o0 = self.alloc_b8(f"depth.enc{i}.0.out", B, ch, h2, w2)
-            self.conv_relu2_b8(st, f"depth.enc{i}.0", x_srcs, f"{dm}.enc.{i}.0", mid0, o0, stride=s_)
-            mid1 = self.alloc_b8(f"depth.enc{i}.1.mid", B, ch, h2, w2)
-            o1 = self.alloc_b8(f"depth.enc{i}.1.out", B, ch, h2, w2)
-            self.conv_relu2_b8(st, f"depth.enc{i}.1", [o0], f"{dm}.enc.{i}.1", mid1, o1)
-            dfe.append(o1)
-            x_srcs, hh, ww = [o1], h2, w2
-        lo, hi_ = self.inv_depth_min_max[1], self.inv_depth_min_max[0]
-        # the maps the depth heads read (csrc/heads.hip) stay dense fp32: r0, x1, x2, x4
-        r0 = self.alloc("depth.dec0", B, dch[0], H // 8, W // 8)
-        self.refine_b8(st, "depth.dec0", [dfe[4]], f"{dm}.dec.0", r0)
-        r1 = self.alloc_b8("depth.dec1.t", B, dch[1], H // 4, W // 4)
-        self.refine_b8(st, "depth.dec1.0", [dfe[3], feats[2], r0], f"{dm}.dec.1.0", r1)  # :545
-        m1 = self.alloc_b8("depth.dec1.mid", B, dch[1], H // 4, W // 4)
-        x1 = self.alloc("depth.dec1", B, dch[1], H // 4, W // 4)
-        self.conv_relu2_b8(st, "depth.dec1.1", [r1], f"{dm}.dec.1.1", m1, x1)
-        r2 = self.alloc_b8("depth.dec2.t", B, dch[2], H // 2, W // 2)
-        self.refine_b8(st, "depth.dec2.0", [dfe[2], feats[1], x1], f"{dm}.dec.2.0", r2)
-        m2 = self.alloc_b8("depth.dec2.mid", B, dch[2], H // 2, W // 2)
-        x2 = self.alloc("depth.dec2", B, dch[2], H // 2, W // 2)
-        self.conv_relu2_b8(st, "depth.dec2.1", [r2], f"{dm}.dec.2.1", m2, x2)
-        x3 = self.alloc_b8("depth.dec3", B, dch[3], H, W)
-        self.refine_b8(st, "depth.dec3", [dfe[1], feats[0], x2], f"{dm}.dec.3", x3)
-        m4 = self.alloc_b8("depth.dec4.mid", B, dch[4], H, W)
-        x4a = self.alloc_b8("depth.dec4.a", B, dch[4], H, W)
-        self.conv_relu2_b8(st, "depth.dec4.0", [dfe[0], x3], f"{dm}.dec.4.0", m4, x4a)   # :543
-        x4 = self.alloc("depth.dec4", B, dch[5], H, W)
-        self.same_conv_b8(st, "depth.dec4.2", [x4a], f"{dm}.dec.4.2.weight", f"{dm}.dec.4.2.bias", x4)
-        heads = [(0, r0, 3), (1, x1, 2), (2, x2, 1), (3, x4, 0)]
-        preds = [None] * 4
-        descs = (HeadDesc * len(heads))()
-        for i, (idx, src, slot) in enumerate(heads):
-            p = self.alloc(f"pred{slot}", B, 1, int(src.shape[2]), int(src.shape[3]))
-            preds[slot] = p
-            w_ = self._dev(sd[f"{dm}.predictors.{idx}.1.weight"])
-            b_ = self._dev(sd[f"{dm}.predictors.{idx}.1.bias"].reshape(-1))
-            descs[i].src, descs[i].weight, descs[i].bias, descs[i].dst = src.data_ptr(), w_.data_ptr(), b_.data_ptr(), p.data_ptr()
-            descs[i].batch, descs[i].channels, descs[i].height, descs[i].width = [int(v) for v in src.shape]
-            self.keep += [src, p]
-        self.keep.append(descs)
-
-        def run_heads(stream, descs=descs, n=len(heads)):
-            _lib.check(lib.mr_depth_heads_f32(descs, n, lo, hi_, stream), "mr_depth_heads_f32")
-        self.add(st, "depth.heads", run_heads)
-        self.aux_log.append(dict(name="depth.heads", ref_macs=sum(int(s_.shape[0] * s_.shape[1] * s_.shape[2] * s_.shape[3]) * 9 for _, s_, _ in heads)))
         self.preds = preds
 
     # ------------------------------------------------------------------ inputs

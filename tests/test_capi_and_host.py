@@ -922,6 +922,28 @@ def test_rule_path_agrees_with_the_tables_it_is_derived_from():
     assert n == len(engine.TUNED) and tile >= 0.3 * n, (tile, n)
 
 
+def test_nearest_signature_rules_follow_in_place_table_edits(monkeypatch):
+    """tools/tune_pipeline.py rewrites engine.TUNED[sig] in place (same length): nearest_schedules / nearest_form must read the edited
+    content, not a parse cached on the table's length."""
+    key = next(iter(engine.TUNED))
+    m = engine._SIG_RE.match(key)
+    cis = [int(c) for c in m.group(2).split("+")]
+    mode = {"": 0, "_bf16": 1, "_bf16x3": 2}[m.group(12) or ""]
+    args = (int(m.group(1)), cis, int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(6)), int(m.group(7)), int(m.group(8)),
+            int(m.group(9)), int(m.group(10)), mode, m.group(11) == "u")
+    assert engine.nearest_schedules(*args, limit=1) == [tuple(engine.TUNED[key])]      # distance 0: the entry itself
+    edited = (3, 1, 1, 16, 4, 0)
+    assert tuple(engine.TUNED[key]) != edited
+    monkeypatch.setitem(engine.TUNED, key, edited)
+    assert engine.nearest_schedules(*args, limit=1) == [edited]
+    wkey, code = next((k, v) for k, v in engine.WINOGRAD.items() if k.startswith("co"))
+    w = engine._WSIG_RE.match(wkey)
+    wargs = ("", int(w.group(2)), sum(int(c) for c in w.group(3).split("+")), int(w.group(4)) * int(w.group(5)), int(w.group(6)))
+    assert engine.nearest_form(*wargs) == code
+    monkeypatch.setitem(engine.WINOGRAD, wkey, 12 if code != 12 else 11)
+    assert engine.nearest_form(*wargs) == (12 if code != 12 else 11)
+
+
 def test_f2_table_documents_its_coverage():
     """`hip_exact_convs="f2"`: tuned_winograd_f2.json holds MEASURED F(2,.) choices only for the c2 / c3 keys whose
     main-table entry is a larger form; every other such key falls back to a rule (variant 11 for a 3x3 layer, the direct kernel for a 1-D

@@ -123,9 +123,10 @@ def test_conv_b8_matches_torch_on_bf16_rounded_operands(hip_lib, case):
 
 @pytest.mark.parametrize("layer", ["refine", "upconv"])
 @pytest.mark.parametrize("olay", [0, 1])
-def test_b8_transposed_and_upsampling_layers(hip_lib, layer, olay):
+def test_refine_and_upconv_run_on_the_b8_kernel_for_b8_operands(hip_lib, layer, olay):
     """layers.Refine (ConvTranspose2d(4, 2) + LeakyReLU + crop, model/layers.py:389-397) and layers.Upconv (nearest x2 -> pad (0,1,0,1) ->
-    conv 2x2, :349-356) as four-phase B8 launches, against the reference formulation on the CPU."""
+    conv 2x2, :349-356) built by Plan.refine / Plan.upconv on a B8 source: one four-phase B8 launch each, against the reference formulation
+    on the CPU."""
     g = torch.Generator().manual_seed(41 if layer == "refine" else 42)
     n, (h, w) = 2, (12, 40)
     srcs_c, lays = ((24, 16, 40), (1, 0, 0)) if layer == "refine" else ((40, 24), (1, 0))
@@ -163,9 +164,11 @@ def test_b8_transposed_and_upsampling_layers(hip_lib, layer, olay):
     else:
         out = torch.full((n, cout, 2 * h, 2 * w), float("nan"), device=DEV)
     if layer == "refine":
-        plan.refine_b8("main", "t", dsrcs, "p", out)
+        plan.refine("main", "t", dsrcs, "p", out)
     else:
-        plan.upconv_b8("main", "t", dsrcs, "p.weight", "p.bias", out)
+        plan.upconv("main", "t", dsrcs, "p.weight", "p.bias", out)
+    assert [(name, fn.native[0]) for name, fn in plan.stages["main"]] == [("t", _lib.LAUNCH_CONV_B8)]
+    assert plan.conv_log[-1]["b8"] and plan.conv_log[-1]["phases"] == 4
     plan.finalize()
     plan.run_stage("main", _stream())
     torch.cuda.synchronize()

@@ -49,9 +49,9 @@ def build(c, sched, g):
     out = plan.alloc_b8("o", n, cout, oh, ow) if spec["out_layout"] else torch.empty(n, cout, oh, ow, device=DEV)
     try:
         if four and upconv:
-            plan.upconv_b8("main", "t", srcs, "t.weight", "t.bias", out)
+            plan.upconv("main", "t", srcs, "t.weight", "t.bias", out)
         elif four:
-            plan.refine_b8("main", "t", srcs, "t", out)
+            plan.refine("main", "t", srcs, "t", out)
         else:
             wt = torch.randn(cout, cin, kh, kw, generator=g) * (1.0 / (kh * kw * cin) ** 0.5)
             plan.conv_b8("main", "t", srcs, wt, torch.zeros(cout), out, stride=spec["stride"], pad=spec["pad"], grid=spec["grid"], act=spec["act"], p0=spec["p0"],
