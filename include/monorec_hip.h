@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 20
+#define MR_ABI_VERSION 21
 
 #define MR_COMPUTE_F32  0
 #define MR_COMPUTE_BF16 1
@@ -666,6 +666,17 @@ int mr_preprocess_image_u8_f32(const uint8_t* src, int32_t src_h, int32_t src_w,
                                const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
                                const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize,
                                int32_t max_tile_rows, float* dst, void* stream);
+
+/* The same launch with a photometric response table between the resize and the division: TUMMonoVODataset.preprocess_image
+ * (tum_mono_vo_dataset.py:84-100), dst = lut256[8-bit result of the resize] / 255 - .5.  lut256: 256 floats in device memory
+ * (the inverse response of the sequence, invert_pcalib, :247-254), held in the LDS during the launch.  A 1-channel source is
+ * resized once and written to the three planes (`convert('RGB')` first gives the same bytes).
+ * lut256 == NULL: MR_ERR_BAD_ARGUMENT. */
+int mr_preprocess_image_u8_lut_f32(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels,
+                                   int64_t row_stride_bytes, const int32_t* box, int32_t out_h, int32_t out_w,
+                                   const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
+                                   const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize,
+                                   int32_t max_tile_rows, const float* lut256, float* dst, void* stream);
 
 /* Sparse lidar ground truth, preprocess_depth_annotated_lidar (kitti_odometry_dataset.py:184-211): the 16-bit depth PNG
  * (depth * 256, 0 = no return) -> inverse depth 256 / value scattered to the nearest cell of the (out_h, out_w) grid of

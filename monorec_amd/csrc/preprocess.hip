@@ -15,6 +15,7 @@ namespace {
 
 constexpr int PRECISION_BITS = 32 - 8 - 2;
 constexpr int PT_H = 16, PT_W = 64;
+constexpr int PRE_THREADS = 1024;           // per 16 x 64 output tile
 
 struct PreArgs {
     const unsigned char* src;
@@ -24,6 +25,7 @@ struct PreArgs {
     const int* hb; const int* hk; int hks;   // bounds (first, count) per output column, coefficients [out_w][hks]
     const int* vb; const int* vk; int vks;
     int max_rows;                            // LDS rows per tile
+    const float* lut;                        // 256-entry response table (LUT kernel only)
     float* dst;
 };
 
@@ -32,15 +34,26 @@ __device__ __forceinline__ unsigned char clip8(int acc) {
     return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
 }
 
-__global__ __launch_bounds__(256) void preprocess_kernel(const PreArgs a) {
-    extern __shared__ unsigned char tmp[];                 // [rows][PT_W][channels] horizontal-pass output
+// LUT: tum_mono_vo_dataset.py:92-94 - the 8-bit result of the resize indexes the inverse response table of the sequence
+// before the division.  The table sits in the first KiB of the LDS, loaded once per workgroup.
+// 1024 threads per tile: a 480x640 output is only 300 tiles, about one per CU, so the time of a launch is the chain of dependent
+// loads (bounds -> coefficients, pixels) a thread walks for its share of the tile; 16 waves per tile walk a quarter of what 4 did
+// (measured: 10.8 -> 6.9 us at 1024x1280 -> 480x640 grey; dword loads of the source rows, per lane or staged through the LDS, were
+// slower than these byte loads: DESIGN 4.8).
+template <bool LUT>
+__global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(const PreArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    float* lut = reinterpret_cast<float*>(lds);
+    unsigned char* tmp = lds + (LUT ? 256 * sizeof(float) : 0);   // [rows][PT_W][channels] horizontal-pass output
+    constexpr int T = PRE_THREADS;
+    if (LUT && threadIdx.x < 256) lut[threadIdx.x] = a.lut[threadIdx.x];
     const int ox0 = blockIdx.x * PT_W, oy0 = blockIdx.y * PT_H;
     const int oy_last = min(oy0 + PT_H, a.out_h) - 1;
     const int r_first = a.vb[2 * oy0];
     const int r_end = a.vb[2 * oy_last] + a.vb[2 * oy_last + 1];
     const int rows = r_end - r_first, C = a.channels;
     const int cols = min(PT_W, a.out_w - ox0);
-    for (int e = threadIdx.x; e < rows * cols; e += 256) {
+    for (int e = threadIdx.x; e < rows * cols; e += T) {
         const int r = e / cols, xx = e - r * cols;
         const int first = a.hb[2 * (ox0 + xx)], n = a.hb[2 * (ox0 + xx) + 1];
         const int* k = a.hk + (long long)(ox0 + xx) * a.hks;
@@ -53,7 +66,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreArgs a) {
     }
     __syncthreads();
     const long long plane = (long long)a.out_h * a.out_w;
-    for (int e = threadIdx.x; e < PT_H * cols; e += 256) {
+    for (int e = threadIdx.x; e < PT_H * cols; e += T) {
         const int yy = e / cols, xx = e - yy * cols;
         const int oy = oy0 + yy;
         if (oy >= a.out_h) continue;
@@ -63,7 +76,8 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const PreArgs a) {
         for (int c = 0; c < C; ++c) {
             int acc = 1 << (PRECISION_BITS - 1);
             for (int t = 0; t < n; ++t) acc += (int)tmp[((first + t) * PT_W + xx) * C + c] * k[t];
-            v[c] = (float)clip8(acc) / 255.0f - 0.5f;      // kitti_odometry_dataset.py:128
+            const unsigned char u = clip8(acc);
+            v[c] = (LUT ? lut[u] : (float)u) / 255.0f - 0.5f;   // kitti_odometry_dataset.py:128, tum_mono_vo_dataset.py:93-94
         }
         const long long o = (long long)oy * a.out_w + ox0 + xx;
         if (C == 1) { a.dst[o] = v[0]; a.dst[plane + o] = v[0]; a.dst[2 * plane + o] = v[0]; }     // :130
@@ -175,25 +189,47 @@ extern "C" int mr_resample_coeffs_bilinear(int32_t in_size, int32_t in0, int32_t
     return 0;
 }
 
-extern "C" int mr_preprocess_image_u8_f32(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels,
-                                          int64_t row_stride_bytes, const int32_t* box, int32_t out_h, int32_t out_w,
-                                          const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
-                                          const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize,
-                                          int32_t max_tile_rows, float* dst, void* stream) {
-    if (!src || !box || !hbounds || !hcoeffs || !vbounds || !vcoeffs || !dst) return MR_ERR_BAD_ARGUMENT;
+namespace {
+
+int launch_preprocess(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels, int64_t row_stride_bytes,
+                      const int32_t* box, int32_t out_h, int32_t out_w, const int32_t* hbounds, const int32_t* hcoeffs,
+                      int32_t hksize, const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize, int32_t max_tile_rows,
+                      const float* lut256, bool with_lut, float* dst, void* stream) {
+    if (!src || !box || !hbounds || !hcoeffs || !vbounds || !vcoeffs || !dst || (with_lut && !lut256)) return MR_ERR_BAD_ARGUMENT;
     if ((channels != 1 && channels != 3) || out_h < 1 || out_w < 1 || hksize < 1 || vksize < 1 || max_tile_rows < 1) return MR_ERR_BAD_ARGUMENT;
     if (box[0] < 0 || box[1] < 0 || box[2] > src_w || box[3] > src_h || box[2] <= box[0] || box[3] <= box[1]) return MR_ERR_BAD_ARGUMENT;
     if (row_stride_bytes < (int64_t)src_w * channels) return MR_ERR_BAD_ARGUMENT;
-    const size_t lds = (size_t)max_tile_rows * PT_W * channels;
+    const size_t lds = (size_t)max_tile_rows * PT_W * channels + (with_lut ? 256 * sizeof(float) : 0);
     if (lds > 64 * 1024) return MR_ERR_LDS_BUDGET;
     PreArgs a;
     a.src = src; a.row_stride = row_stride_bytes; a.channels = channels; a.x0 = box[0]; a.y0 = box[1];
     a.out_h = out_h; a.out_w = out_w;
     a.hb = hbounds; a.hk = hcoeffs; a.hks = hksize; a.vb = vbounds; a.vk = vcoeffs; a.vks = vksize;
-    a.max_rows = max_tile_rows; a.dst = dst;
+    a.max_rows = max_tile_rows; a.lut = lut256; a.dst = dst;
     dim3 grid((out_w + PT_W - 1) / PT_W, (out_h + PT_H - 1) / PT_H);
-    hipLaunchKernelGGL(preprocess_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
+    if (with_lut) hipLaunchKernelGGL(preprocess_kernel<true>, grid, dim3(PRE_THREADS), lds, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL(preprocess_kernel<false>, grid, dim3(PRE_THREADS), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int mr_preprocess_image_u8_f32(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels,
+                                          int64_t row_stride_bytes, const int32_t* box, int32_t out_h, int32_t out_w,
+                                          const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
+                                          const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize,
+                                          int32_t max_tile_rows, float* dst, void* stream) {
+    return launch_preprocess(src, src_h, src_w, channels, row_stride_bytes, box, out_h, out_w, hbounds, hcoeffs, hksize,
+                             vbounds, vcoeffs, vksize, max_tile_rows, nullptr, false, dst, stream);
+}
+
+extern "C" int mr_preprocess_image_u8_lut_f32(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels,
+                                              int64_t row_stride_bytes, const int32_t* box, int32_t out_h, int32_t out_w,
+                                              const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
+                                              const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize,
+                                              int32_t max_tile_rows, const float* lut256, float* dst, void* stream) {
+    return launch_preprocess(src, src_h, src_w, channels, row_stride_bytes, box, out_h, out_w, hbounds, hcoeffs, hksize,
+                             vbounds, vcoeffs, vksize, max_tile_rows, lut256, true, dst, stream);
 }
 
 extern "C" int mr_lidar_inverse_depth_u16_f32(const uint16_t* depth_png, int32_t src_h, int32_t src_w, const int32_t* box,

@@ -67,9 +67,11 @@ def _axis_tables(lib, in_size, out_size):
 
 class ImagePreprocessor:
     """`preprocess_image` (kitti_odometry_dataset.py:120-134) for one source image size: crop box (as `Image.crop`
-    rounds it), Pillow-exact bilinear resize to `target_image_size`, `/255 - .5`, CHW - one launch per image."""
+    rounds it), Pillow-exact bilinear resize to `target_image_size`, `/255 - .5`, CHW - one launch per image.
+    `lut` (256 floats): the 8-bit result of the resize indexes this table before the division - the inverse photometric
+    response of a TUM-MonoVO sequence (tum_mono_vo_dataset.py:92-94), uploaded once, applied in the same launch."""
 
-    def __init__(self, orig_size, target_image_size, crop_box=None, device="cuda:0"):
+    def __init__(self, orig_size, target_image_size, crop_box=None, device="cuda:0", lut=None):
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -87,6 +89,12 @@ class ImagePreprocessor:
         up = lambda a: torch.from_numpy(a).to(self.device)
         self.hb, self.hk, self.vb, self.vk = up(hb), up(hk), up(vb), up(vk)
         self._box_c = (ctypes.c_int32 * 4)(*self.box)
+        self.lut = None
+        if lut is not None:
+            table = torch.as_tensor(np.asarray(lut.cpu() if torch.is_tensor(lut) else lut, dtype=np.float32)).reshape(-1)
+            if table.numel() != 256:
+                raise ValueError("lut: expected 256 values (one per 8-bit intensity)")
+            self.lut = table.contiguous().to(self.device)
         self._staging = {}          # channels -> ring of (pinned host buffer, device buffer, copy-done event)
         self._ring_pos = 0
 
@@ -122,10 +130,14 @@ class ImagePreprocessor:
         image = image.contiguous()
         if out is None:
             out = torch.empty(3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.mr_preprocess_image_u8_f32(
-            image.data_ptr(), self.orig_h, self.orig_w, channels, self.orig_w * channels, self._box_c, self.out_h, self.out_w,
-            self.hb.data_ptr(), self.hk.data_ptr(), self.hks, self.vb.data_ptr(), self.vk.data_ptr(), self.vks,
-            self.max_rows, out.data_ptr(), torch.cuda.current_stream().cuda_stream), "mr_preprocess_image_u8_f32")
+        args = (image.data_ptr(), self.orig_h, self.orig_w, channels, self.orig_w * channels, self._box_c, self.out_h, self.out_w,
+                self.hb.data_ptr(), self.hk.data_ptr(), self.hks, self.vb.data_ptr(), self.vk.data_ptr(), self.vks, self.max_rows)
+        stream = torch.cuda.current_stream().cuda_stream
+        if self.lut is None:
+            _lib.check(self.lib.mr_preprocess_image_u8_f32(*args, out.data_ptr(), stream), "mr_preprocess_image_u8_f32")
+        else:
+            _lib.check(self.lib.mr_preprocess_image_u8_lut_f32(*args, self.lut.data_ptr(), out.data_ptr(), stream),
+                       "mr_preprocess_image_u8_lut_f32")
         return out
 
 

@@ -269,13 +269,24 @@ def collate(samples):
 class DeviceLoader:
     """Sequential batches of a device-side dataset: the iteration contract of the reference's `KittiOdometryDataloader`
     (data_loader/data_loaders.py:9-13, `shuffle=False`): yields `(data, target)` with a leading batch dimension, the last
-    batch may be smaller.  `rank` / `world_size` shard whole batches round-robin (monorec_amd.distributed.shard_batches)."""
+    batch may be smaller.  `rank` / `world_size` shard whole batches round-robin (monorec_amd.distributed.shard_batches).
+    `start` / `end` / `every_nth` select the window of the reference's `DS_Wrapper` (utils/util.py:148-163, what
+    create_pointcloud.py:32 puts around its dataset): item i is `dataset[i * every_nth + start]`, `end == -1` means the
+    dataset's length; the defaults are the whole dataset."""
 
-    def __init__(self, dataset, batch_size=1, rank=0, world_size=1):
+    def __init__(self, dataset, batch_size=1, rank=0, world_size=1, start=0, end=-1, every_nth=1):
         self.dataset, self.batch_size, self.rank, self.world_size = dataset, int(batch_size), int(rank), int(world_size)
+        self.start, self.every_nth = int(start), int(every_nth)
+        self.end = int(end)
+        if self.every_nth < 1:
+            raise ValueError("every_nth must be at least 1")
+
+    def _items(self):
+        span = (len(self.dataset) if self.end == -1 else self.end) - self.start
+        return max(0, span // self.every_nth + (1 if span % self.every_nth != 0 else 0))         # utils/util.py:163
 
     def _batches(self):
-        n = len(self.dataset)
+        n = self._items()
         starts = list(range(0, n, self.batch_size))
         return [(s, min(s + self.batch_size, n)) for s in starts][self.rank::self.world_size]
 
@@ -284,7 +295,7 @@ class DeviceLoader:
 
     def __iter__(self):
         for lo, hi in self._batches():
-            yield collate([self.dataset[i] for i in range(lo, hi)])
+            yield collate([self.dataset[i * self.every_nth + self.start] for i in range(lo, hi)])
 
 
 class KittiOdometryDataloader(DeviceLoader):

@@ -10,7 +10,12 @@
   * the 1/depth, range / roi / dropout tests, back-projection, pose multiply, colours and the ordered boolean-mask
     compaction are one kernel (`mr_pointcloud_append_f32`), optionally with the 5-mask vote and `depth *= mask`
     of create_pointcloud.py:90-92 fused in (`static_masks=`).
-There is no CPU fallback: CPU tensors raise."""
+There is no CPU fallback: CPU tensors raise.
+
+`run(config)` is the whole of `create_pointcloud.py` for a config of that script's shape (configs/test/pointcloud_monorec.json,
+pointcloud_monorec_tmvo.json) with the data source on the device too:
+
+    python -m monorec_amd.pointcloud --config configs/test/pointcloud_monorec_tmvo.json"""
 import ctypes
 from array import array
 
@@ -153,3 +158,87 @@ class PointcloudBuilder:
             self.ply.add_depthmap(k["depth"], k["keyframe"], k["intrinsics"], k["pose"], static_masks=masks,
                                   min_hits=self.min_hits)
             del self._buf[0]
+
+
+DEVICE_DATASETS = ("KittiOdometryDataset", "TUMMonoVODataset", "TUMMonoVOMultiDataset")
+
+
+def _dataset_class(name):
+    """`config.initialize('data_set', module_data)` (create_pointcloud.py:32) resolved to the device-side classes."""
+    if name not in DEVICE_DATASETS:
+        raise ValueError(f"monorec_amd.pointcloud: no device data source for data_set.type {name!r} (available: {', '.join(DEVICE_DATASETS)})")
+    if name == "KittiOdometryDataset":
+        from .kitti import KittiOdometryDataset
+        return KittiOdometryDataset
+    from . import tum_mono_vo
+    return getattr(tum_mono_vo, name)
+
+
+def run(config, model=None, dataset=None, out=None, dropout=.75, device="cuda:0"):
+    """create_pointcloud.py:16-105 for a config dict of that script's shape: `data_set.type/args` -> device dataset, windowed by
+    `start` / `end` (DS_Wrapper), batch size 1 -> `arch.args` -> MonoRecModel -> PointcloudBuilder (static masks, 5-keyframe vote)
+    -> PLYSaver(`min_d`, `max_d`, `roi`, dropout) -> `output_dir/file_name`.  `model` / `dataset`: use these instead of building them
+    from the config; `out`: a path or a binary file object instead of `output_dir/file_name`; `dropout`: the random thinning the
+    script hard-wires to .75 (:52).  Returns the number of records written."""
+    import os
+    from .kitti import DeviceLoader
+    if dataset is None:
+        dataset_class = _dataset_class(config["data_set"]["type"])
+    if model is None and config["arch"]["type"] != "MonoRecModel":
+        raise ValueError(f"monorec_amd.pointcloud: arch.type {config['arch']['type']!r} is not MonoRecModel")
+    if model is None:
+        from .model import MonoRecModel
+        model = MonoRecModel(**config["arch"]["args"]).to(device)
+    device = next(model.parameters()).device
+    if dataset is None:
+        dataset = dataset_class(**dict(config["data_set"]["args"], device=device))
+    model.eval()
+    loader = DeviceLoader(dataset, batch_size=1, start=config.get("start", 0), end=config.get("end", -1))
+    height, width = dataset.target_image_size
+    saver = PLYSaver(height, width, min_d=config.get("min_d", 3), max_d=config.get("max_d", 30), batch_size=loader.batch_size,
+                     roi=config.get("roi", None), dropout=dropout)
+    saver.to(device)
+    builder = PointcloudBuilder(saver, mask_fill=32, buffer_length=5, min_hits=1, use_mask=config.get("use_mask", True))
+    with torch.no_grad():
+        for data, _ in loader:
+            result = model(data)
+            # the datasets keep the 4x4 matrices on the host for the model's pose algebra; the saver multiplies on the device
+            builder.add(dict(data, keyframe_pose=data["keyframe_pose"].to(device),
+                             keyframe_intrinsics=data["keyframe_intrinsics"].to(device)), result)
+    if out is None:
+        output_dir = config.get("output_dir", "saved")
+        os.makedirs(output_dir, exist_ok=True)
+        out = os.path.join(output_dir, config.get("file_name", "pc.ply"))
+    if hasattr(out, "write"):
+        saver.save(out)
+    else:
+        with open(out, "wb") as f:
+            saver.save(f)
+    return len(saver.data) // 6
+
+
+def main(argv=None):
+    """The command line of create_pointcloud.py:108-119 (utils/parse_config.py:21-32: with --resume the config.json beside the
+    checkpoint is read first and --config updates it)."""
+    import argparse
+    import json
+    import os
+    parser = argparse.ArgumentParser(description="MonoRec point cloud on the device (create_pointcloud.py)")
+    parser.add_argument("-c", "--config", default=None, type=str, help="config file path")
+    parser.add_argument("-r", "--resume", default=None, type=str, help="checkpoint; its folder's config.json is the base config")
+    parser.add_argument("-d", "--device", default="cuda:0", type=str, help="torch device (default: cuda:0)")
+    args = parser.parse_args(argv)
+    if args.resume is None and args.config is None:
+        parser.error("a configuration file is needed: --config FILE")
+    config = {}
+    if args.resume is not None:
+        with open(os.path.join(os.path.dirname(os.path.abspath(args.resume)), "config.json")) as f:
+            config = json.load(f)
+    if args.config is not None:
+        with open(args.config) as f:
+            config.update(json.load(f))
+    print(f"{run(config, device=args.device)} points written")
+
+
+if __name__ == "__main__":
+    main()

@@ -354,3 +354,59 @@ KITTI_OPTION_CASES = {
     "mvobj": dict(frame_count=2, lidar_depth=True, return_mvobj_mask=1, return_stereo=True),
 }
 
+
+
+def make_tmvo_tree(root, height=40, width=56, channels=1, images=12, dropped=(3, 7, 11), model_name=None, seed=5):
+    """Write a small TUM-MonoVO-shaped sequence folder (the layout the reference's TUMMonoVODataset reads): images/%05d.jpg,
+    times.txt (`id time exposure` per image), result.txt (`time tx ty tz qx qy qz qw` for every image not in `dropped`: frames the
+    tracker lost, so rows and file numbers differ), pcalib.txt (the response 255 (i/255)^0.6: its inverse is not the identity) and
+    camera.txt (relative intrinsics, after `model_name` when given).  The images come from a seeded integer generator - blocks, a
+    per-frame shift and noise, no drawing or filtering calls - and are stored losslessly: PNG bytes under the .jpg names (Pillow
+    identifies the format by content), so every machine decodes the same pixels.  Quaternions are deliberately not of unit norm."""
+    import os
+    import numpy as np
+    from PIL import Image
+    rng = np.random.RandomState(seed)
+    root = str(root)
+    os.makedirs(os.path.join(root, "images"), exist_ok=True)
+    shape = (height // 8 + 2, width // 8 + 2) + ((3,) if channels == 3 else ())
+    blocks = np.repeat(np.repeat(rng.randint(0, 256, size=shape), 8, axis=0), 8, axis=1)
+    stamps = [f"{1461161054.25 + 0.05 * i:.6f}" for i in range(images)]
+    for i in range(images):
+        shift = i % 8
+        img = blocks[shift // 2:shift // 2 + height, shift:shift + width] + rng.randint(-24, 25, size=(height, width) + shape[2:])
+        img = np.clip(img, 0, 255).astype(np.uint8)
+        img[height // 3, :] = 255                                           # a saturated and a black line: the clipping paths
+        img[:, width // 4] = 0
+        Image.fromarray(img).save(os.path.join(root, "images", f"{i:05d}.jpg"), format="PNG")
+    with open(os.path.join(root, "times.txt"), "w") as f:
+        for i in range(images):
+            f.write(f"{i:05d} {stamps[i]} {10.0 + 0.25 * (i % 4):.4f}\n")
+    with open(os.path.join(root, "result.txt"), "w") as f:
+        for i in range(images):
+            if i in dropped:
+                continue
+            a = 0.015 * i
+            q = np.array([0.02 * np.sin(0.3 * i), np.sin(a / 2), -0.01 * np.cos(0.2 * i), np.cos(a / 2)]) * (0.7 + 0.15 * (i % 5))
+            t = np.array([0.004 * i, -0.002 * i, 0.27 * i])
+            f.write(stamps[i] + " " + " ".join(f"{v:.9f}" for v in np.concatenate([t, q])) + "\n")
+    with open(os.path.join(root, "pcalib.txt"), "w") as f:
+        f.write(" ".join(f"{255.0 * (i / 255.0) ** 0.6:.6f}" for i in range(256)) + "\n")
+    with open(os.path.join(root, "camera.txt"), "w") as f:
+        numbers = "0.535719308 0.669566858 0.493248545 0.500408664"
+        f.write((f"{model_name} {numbers} 0 0 0 0\n" if model_name else f"{numbers} 0.897966326\n"))
+        f.write(f"{width} {height}\ncrop\n{width} {height}\n")
+    return root
+
+
+# option matrix of the TUM-MonoVO sample assembly shared by tools/make_golden_tmvo.py (writes the reference's values) and the tests:
+# name -> (make_tmvo_tree keywords, dataset keywords)
+TMVO_CASES = {
+    # 40x56 -> 24x32: source too wide, columns dropped; the frame_count / scale_factor of configs/test/pointcloud_monorec_tmvo.json
+    "wide_f4": (dict(height=40, width=56, seed=5), dict(frame_count=4, scale_factor=3, target_image_size=(24, 32))),
+    # 48x40 -> 24x32: rows dropped, the branch of the real 1024x1280 -> 480x640 geometry; camera.txt starts with the model's name
+    "tall_dilated": (dict(height=48, width=40, model_name="RadTan", seed=6),
+                     dict(frame_count=2, dilation=2, max_length=3, target_image_size=(24, 32))),
+    # RGB source: three channels through the table
+    "rgb": (dict(height=36, width=52, channels=3, images=7, dropped=(2,), seed=7), dict(frame_count=2, target_image_size=(24, 32))),
+}
