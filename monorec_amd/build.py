@@ -41,6 +41,9 @@ SOURCES = [
 # instantiations of conv1d_wino.hip, which no table entry ever selected, stay in the DIAGNOSTIC library only.
 DIAGNOSTIC_ONLY_SOURCES = []
 
+# what a translation unit may include: every csrc/*.h and the C ABI - editing one of them rebuilds all sources
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(HERE, "..", "include", "monorec_hip.h")]
+
 
 def _hipcc():
     exe = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -72,11 +75,10 @@ def _run_all(cmds, verbose=False):
 
 def build(force=False, verbose=False):
     if not force and os.path.exists(LIB_PATH) and not _stale(
-            LIB_PATH, [os.path.join(CSRC, s) for s, _ in SOURCES] + [os.path.join(CSRC, "conv_layout.h"), os.path.join(CSRC, "cooktoom_1d.h"), __file__,
-                                                                       os.path.join(HERE, "..", "include", "monorec_hip.h")]):
+            LIB_PATH, [os.path.join(CSRC, s) for s, _ in SOURCES] + HEADERS + [__file__]):
         return LIB_PATH                     # prebuilt library travels with the snapshot; nothing to do
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "conv_layout.h"), os.path.join(CSRC, "cooktoom_1d.h"), os.path.join(HERE, "..", "include", "monorec_hip.h"), __file__]
+    headers = HEADERS + [__file__]
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     objs, cmds = [], []
@@ -116,21 +118,20 @@ def build_timeline(verbose=False):
     objdir = os.path.join(HERE, "build")
     flags = dict(SOURCES)
     objs, cmds = [], []
-    hdrs = [os.path.join(CSRC, "conv_layout.h"), os.path.join(CSRC, "cooktoom_1d.h"), os.path.join(HERE, "..", "include", "monorec_hip.h")]
     for src, _ in SOURCES:
         if src not in DIAGNOSTIC:
             objs.append(os.path.join(objdir, src.replace(".hip", ".o")))
             continue
         o = os.path.join(objdir, src.replace(".hip", "_diag.o"))
         s = os.path.join(CSRC, src)
-        if _stale(o, [s] + hdrs):
+        if _stale(o, [s] + HEADERS):
             cmds.append([hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", DIAGNOSTIC[src], "-DMR_DIAGNOSTIC_LIBRARY", "-c", s, "-o", o] + flags[src])
         objs.append(o)
     _run_all(cmds, verbose)
     for src, extra in DIAGNOSTIC_ONLY_SOURCES:
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         s = os.path.join(CSRC, src)
-        if _stale(o, [s, os.path.join(CSRC, "conv_layout.h"), os.path.join(CSRC, "cooktoom_1d.h"), os.path.join(HERE, "..", "include", "monorec_hip.h")]):
+        if _stale(o, [s] + HEADERS):
             cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-DMR_DIAGNOSTIC_LIBRARY", "-c", s, "-o", o] + extra
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)

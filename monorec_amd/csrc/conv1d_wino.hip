@@ -20,14 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
-#include <atomic>
 
 #include "../../include/monorec_hip.h"
-#include "cooktoom_1d.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "lds_dma.h"
+#include "wino_host.h"
 
 namespace {
 
@@ -59,48 +55,6 @@ struct W1KArgs {
     int dst_split;                      // axis 1: the destination is (2, batch, Cout, H, W / 2) - even columns, odd columns
     long long dst_half;                 // floats of one parity half of such a destination
 };
-
-// LDS-DMA through inline asm (see conv_mfma.hip: the builtins make hipcc drain vmcnt before every sweep)
-__device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-// One aligned 8-byte LDS read that stays one: left to itself hipcc drops the halves a caller does not use and re-pairs the rest into ds_read2_b32 -
-// two dword accesses with the 32-bank rule (volatile keeps the access whole; the explicit LDS address space keeps it a ds_ instruction)
-__device__ __forceinline__ f32x2 lds_pair(const float* p) {
-    return *(const volatile __attribute__((address_space(3))) f32x2*)(__attribute__((address_space(3))) const float*)p;
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ i32x4 make_srd(const void* base, int bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// none / ReLU / LeakyReLU as ONE branch-free form, max(x, lo) with lo = x (none), 0 (ReLU: -inf -> 0 and no -0.0, like torch.relu),
-// x * p0 (LeakyReLU, 0 <= p0 <= 1 - the host side rejects other slopes); lo's selector is wave-uniform: as a
-// switch the compiler emitted scalar branches around every stored element of the epilogue (round 4: 200-450 branches per workgroup)
-__device__ __forceinline__ float act1(float v, int act, float p0) {
-    const unsigned keep = act == MR_ACT_RELU ? 0u : ~0u;          // (an AND, not a select: a uniform select made hipcc clone the store loops)
-    const float lo = __uint_as_float(__float_as_uint(v * (act == MR_ACT_LEAKY_RELU ? p0 : 1.f)) & keep);
-    return fmaxf(v, lo);
-}
 
 template <int AXIS, int MBW>
 __global__ __launch_bounds__(512) void conv1d3_wino_kernel(const W1KArgs a) {
@@ -200,8 +154,8 @@ __global__ __launch_bounds__(512) void conv1d3_wino_kernel(const W1KArgs a) {
             const int cout = (grp * MBW + m) * 16 + (lane >> 4) * 4 + r;
             if (cout >= a.Cout) continue;
             const float bs = a.bias ? a.bias[cout] : 0.f;
-            const float y0 = act1(((acc[0][m][r] + acc[1][m][r]) + acc[2][m][r]) + bs, a.act, a.p0);
-            const float y1 = act1(((acc[1][m][r] - acc[2][m][r]) - acc[3][m][r]) + bs, a.act, a.p0);
+            const float y0 = act_max(((acc[0][m][r] + acc[1][m][r]) + acc[2][m][r]) + bs, a.act, a.p0);
+            const float y1 = act_max(((acc[1][m][r] - acc[2][m][r]) - acc[3][m][r]) + bs, a.act, a.p0);
             float* o = a.dst + ((long long)(b * a.Cout + cout) * H + oy) * W + ox;
             if (AXIS == 0) {
                 *(float2*)o = make_float2(y0, y1);             // W % 4 == 0 and ox even: both columns exist
@@ -388,7 +342,7 @@ __global__ __launch_bounds__(512) void conv1d_ct_kernel(const W1KArgs a) {
             for (int p = 0; p < N; ++p) mm[p] = acc[p][m][r];
             CtForm<M, R>::out(mm, y);
 #pragma unroll
-            for (int k = 0; k < M; ++k) y[k] = act1(y[k] + bs, a.act, a.p0);
+            for (int k = 0; k < M; ++k) y[k] = act_max(y[k] + bs, a.act, a.p0);
             if constexpr (AXIS == 0) {                         // W % 4 == 0 and ox a multiple of M: all M columns exist
                 float* o = a.dst + ((long long)(b * a.Cout + cout) * H + oy) * W + ox;
                 if constexpr (M == 4) *(f32x4*)o = (f32x4){y[0], y[1], y[2], y[3]};
@@ -514,14 +468,13 @@ __global__ __launch_bounds__(512) void upconv2x2_wino_kernel(const W1KArgs a) {
                 const float m00 = acc[nb][0][m][r], m01 = acc[nb][1][m][r], m10 = acc[nb][2][m][r], m11 = acc[nb][3][m][r];
                 const float o01 = m00 + m01;
                 float* o = a.dst + ((long long)(b * a.Cout + cout) * (2 * H) + 2 * iy) * OW + 2 * ix;
-                *(float2*)o = make_float2(act1(m00 + bs, a.act, a.p0), act1(o01 + bs, a.act, a.p0));
-                *(float2*)(o + OW) = make_float2(act1((m00 + m10) + bs, a.act, a.p0), act1((o01 + (m10 + m11)) + bs, a.act, a.p0));
+                *(float2*)o = make_float2(act_max(m00 + bs, a.act, a.p0), act_max(o01 + bs, a.act, a.p0));
+                *(float2*)(o + OW) = make_float2(act_max((m00 + m10) + bs, a.act, a.p0), act_max((o01 + (m10 + m11)) + bs, a.act, a.p0));
             }
     }
 }
 
 bool valid_mbw1(int m) { return m >= 1 && m <= 4; }
-int pad8(int c) { return (c + 7) & ~7; }
 
 struct W1Derived {
     W1KArgs k;
@@ -531,11 +484,8 @@ struct W1Derived {
 };
 
 int derive1(const mr_wino_desc* d, W1Derived* out, bool views = false) {
-    if (!d || d->num_src < 1 || d->num_src > MR_MAX_SOURCES || d->batch < 1 || d->height < 1 || d->width < 4 || !d->dst ||
-        !d->packed_weights || d->out_channels < 1)
-        return MR_ERR_BAD_ARGUMENT;
-    if (d->width % 4) return MR_ERR_UNSUPPORTED;              // 16-byte groups entirely inside or outside the image
-    if (!views && (d->src_row_pitch || d->src_plane_floats || d->dst_split_columns)) return MR_ERR_UNSUPPORTED;   // mr_conv1d_cooktoom_f32 only
+    if (const int rc = wino_check_shape(d)) return rc;
+    if (!views && wino_is_view(d)) return MR_ERR_UNSUPPORTED;
     if (d->src_row_pitch < 0 || d->src_plane_floats < 0) return MR_ERR_BAD_ARGUMENT;
     const int pitch = d->src_row_pitch ? d->src_row_pitch : d->width;
     const long long cplane = d->src_plane_floats ? d->src_plane_floats : (long long)d->height * d->width;
@@ -543,34 +493,17 @@ int derive1(const mr_wino_desc* d, W1Derived* out, bool views = false) {
     if (d->dst_split_columns && (d->width & 7)) return MR_ERR_UNSUPPORTED;       // each parity half must keep rows of a multiple of 4 columns
     if (d->residual) return MR_ERR_UNSUPPORTED;
     if (!valid_mbw1(d->cout_blocks_per_wave)) return MR_ERR_BAD_ARGUMENT;
-    if (d->activation != MR_ACT_NONE && d->activation != MR_ACT_RELU && d->activation != MR_ACT_LEAKY_RELU) return MR_ERR_UNSUPPORTED;
-    if (d->activation == MR_ACT_LEAKY_RELU && !(d->act_p0 >= 0.f && d->act_p0 <= 1.f)) return MR_ERR_UNSUPPORTED;   // the epilogue is max(x, x * slope)
+    if (const int rc = wino_check_activation(d)) return rc;
     W1KArgs& k = out->k;
-    memset(&k, 0, sizeof(k));
-    int nchunks = 0;
-    for (int s = 0; s < d->num_src; ++s) {
-        if (!d->src[s] || d->src_channels[s] < 1) return MR_ERR_BAD_ARGUMENT;
-        // bytes the launch may address from src[s]: the stored tensor, less what a view that starts (pitch - width) floats into it leaves behind
-        const long long bytes = ((long long)d->batch * d->src_channels[s] * cplane - (pitch - d->width)) * 4;
-        if (bytes >= (1ll << 31) || bytes <= 0) return MR_ERR_UNSUPPORTED;
-        k.src[s] = d->src[s];
-        k.src_bytes[s] = (int)bytes;
-        k.src_c[s] = d->src_channels[s];
-        k.src_cpad[s] = pad8(d->src_channels[s]);
-        nchunks += k.src_cpad[s] / WCK;
-    }
-    if ((long long)d->batch * d->out_channels * d->height * d->width * 4 >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
-    k.nsrc = d->num_src;
-    k.H = d->height; k.W = d->width;
+    int nchunks;
+    // bytes the launch may address from a source: the stored tensor, less what a view that starts (pitch - width) floats into it leaves behind
+    if (const int rc = wino_fill_args(d, WCK, cplane, pitch - d->width, k, nchunks)) return rc;
+    if (wino_dst_bytes(d) >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
     k.pitch = pitch; k.cplane = (int)cplane;
     k.dst_split = d->dst_split_columns ? 1 : 0;
     k.dst_half = (long long)d->batch * d->out_channels * d->height * (d->width / 2);
-    k.dst = d->dst; k.bias = d->bias;
-    k.act = d->activation; k.p0 = d->act_p0;
-    k.Cout = d->out_channels;
     k.tiles_x = (d->width + 31) / 32;
     k.nchunks = nchunks;
-    k.w = d->packed_weights;
     const int mbw = d->cout_blocks_per_wave;
     const int ufl = NPOS * 2 * mbw * 64;
     k.wgroup_stride = (long long)nchunks * ufl;
@@ -627,18 +560,7 @@ int derive_ct_form(const mr_wino_desc* d, W1Derived* out) {
 
 template <int AXIS, int MBW, int M, int R>
 int launch_ct(const W1Derived& dv, hipStream_t stream) {
-    static std::atomic<unsigned long long> attr_set{0};      // dynamic-LDS ceiling once per instantiation AND device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1d_ct_kernel<AXIS, MBW, M, R>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((conv1d_ct_kernel<AXIS, MBW, M, R>), dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
-    return (int)hipGetLastError();
+    return launch_lds_ceiling<conv1d_ct_kernel<AXIS, MBW, M, R>>(160 * 1024, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
 }
 
 template <int AXIS, int M, int R>
@@ -675,10 +597,8 @@ const double* form_g(int m, int r) { return m == 4 && r == 3 ? CtForm<4, 3>::g()
 
 extern "C" size_t mr_wino1d_packed_weight_floats(int32_t out_channels, const int32_t* src_channels, int32_t num_src, int32_t mbw) {
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mbw1(mbw) || out_channels < 1) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += pad8(src_channels[s]) / WCK;
     const int groups = (out_channels + 16 * mbw - 1) / (16 * mbw);
-    return (size_t)groups * nchunks * (NPOS * 2 * mbw * 64);
+    return (size_t)groups * wino_chunks(src_channels, num_src) * (NPOS * 2 * mbw * 64);
 }
 
 // weight: (out_channels, sum(src_channels), 3, 1) or (out_channels, sum(src_channels), 1, 3) fp32, nn.Conv2d layout - three taps per
@@ -689,32 +609,13 @@ extern "C" int mr_wino1d_pack_weights_f32(const float* weight, int32_t out_chann
                                           int32_t mbw, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mbw1(mbw) || out_channels < 1)
         return MR_ERR_BAD_ARGUMENT;
-    static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
-    const int groups = (out_channels + 16 * mbw - 1) / (16 * mbw);
-    size_t o = 0;
-    for (int g = 0; g < groups; ++g) {
-        int cin_off = 0;
-        for (int s = 0; s < num_src; ++s) {
-            const int cpad = pad8(src_channels[s]);
-            for (int c0 = 0; c0 < cpad; c0 += WCK)
-                for (int p = 0; p < NPOS; ++p)
-                    for (int c4 = 0; c4 < 2; ++c4)
-                        for (int mb = 0; mb < mbw; ++mb)
-                            for (int lane = 0; lane < 64; ++lane) {
-                                const int cout = (g * mbw + mb) * 16 + (lane & 15);
-                                const int cl = c0 + c4 * 4 + (lane >> 4);
-                                double u = 0.0;
-                                if (cout < out_channels && cl < src_channels[s]) {
-                                    const float* gw = weight + ((size_t)cout * cin_total + (cin_off + cl)) * 3;
-                                    for (int i = 0; i < 3; ++i) u += G[p][i] * (double)gw[i];
-                                }
-                                dst[o++] = (float)u;
-                            }
-            cin_off += src_channels[s];
-        }
-    }
+    const int cin_total = wino_sum_channels(src_channels, num_src);
+    wino_pack_stream(dst, 0, out_channels, mbw, NPOS, 0, src_channels, num_src, [=](int cout, int cin, int p) {
+        const float* gw = weight + ((size_t)cout * cin_total + cin) * 3;
+        double u = 0.0;
+        for (int i = 0; i < 3; ++i) u += WINO_G_2_3[p][i] * (double)gw[i];
+        return u;
+    });
     return 0;
 }
 
@@ -737,10 +638,8 @@ extern "C" int mr_conv1d3_winograd_f32(const mr_wino_desc* desc, int32_t axis, v
 extern "C" size_t mr_cooktoom1d_packed_weight_floats(int32_t out_channels, const int32_t* src_channels, int32_t num_src, int32_t mbw,
                                                      int32_t m, int32_t r) {
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_form(m, r) || !valid_ct_mbw(m, r, mbw) || out_channels < 1) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += pad8(src_channels[s]) / WCK;
     const int groups = (out_channels + 16 * mbw - 1) / (16 * mbw);
-    return (size_t)groups * nchunks * ct_u_stream(m + r - 1, mbw);
+    return (size_t)groups * wino_chunks(src_channels, num_src) * ct_u_stream(m + r - 1, mbw);
 }
 
 // weight: (out_channels, sum(src_channels), r, 1) or (.., 1, r) fp32, nn.Conv2d layout - r taps per (cout, cin) either way.  U = G g in
@@ -752,33 +651,14 @@ extern "C" int mr_cooktoom1d_pack_weights_f32(const float* weight, int32_t out_c
         return MR_ERR_BAD_ARGUMENT;
     const double* G = form_g(m, r);
     const int npos = m + r - 1;
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
-    const int groups = (out_channels + 16 * mbw - 1) / (16 * mbw);
-    size_t o = 0;
-    for (int g = 0; g < groups; ++g) {
-        int cin_off = 0;
-        for (int s = 0; s < num_src; ++s) {
-            const int cpad = pad8(src_channels[s]);
-            for (int c0 = 0; c0 < cpad; c0 += WCK) {
-                for (int p = 0; p < npos; ++p)
-                    for (int c4 = 0; c4 < 2; ++c4)
-                        for (int mb = 0; mb < mbw; ++mb)
-                            for (int lane = 0; lane < 64; ++lane) {
-                                const int cout = (g * mbw + mb) * 16 + (lane & 15);
-                                const int cl = c0 + c4 * 4 + (lane >> 4);
-                                double u = 0.0;
-                                if (cout < out_channels && cl < src_channels[s]) {
-                                    const float* gw = weight + ((size_t)cout * cin_total + (cin_off + cl)) * r;
-                                    for (int i = 0; i < r; ++i) u += G[p * r + i] * (double)gw[i];
-                                }
-                                dst[o++] = (float)u;
-                            }
-                for (int pad = npos * 2 * mbw * 64; pad < ct_u_stream(npos, mbw); ++pad) dst[o++] = 0.f;      // whole 1 KiB pieces per chunk (odd npos)
-            }
-            cin_off += src_channels[s];
-        }
-    }
+    const int cin_total = wino_sum_channels(src_channels, num_src);
+    const int pad = ct_u_stream(npos, mbw) - npos * 2 * mbw * 64;             // whole 1 KiB pieces per chunk (odd npos)
+    wino_pack_stream(dst, 0, out_channels, mbw, npos, pad, src_channels, num_src, [=](int cout, int cin, int p) {
+        const float* gw = weight + ((size_t)cout * cin_total + cin) * r;
+        double u = 0.0;
+        for (int i = 0; i < r; ++i) u += G[p * r + i] * (double)gw[i];
+        return u;
+    });
     return 0;
 }
 
@@ -798,32 +678,12 @@ extern "C" int mr_upconv_pack_weights_f32(const float* weight, int32_t out_chann
                                           int32_t mbw, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mbw1(mbw) || out_channels < 1)
         return MR_ERR_BAD_ARGUMENT;
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
-    const int groups = (out_channels + 16 * mbw - 1) / (16 * mbw);
-    size_t o = 0;
-    for (int g = 0; g < groups; ++g) {
-        int cin_off = 0;
-        for (int s = 0; s < num_src; ++s) {
-            const int cpad = pad8(src_channels[s]);
-            for (int c0 = 0; c0 < cpad; c0 += WCK)
-                for (int p = 0; p < NPOS; ++p)
-                    for (int c4 = 0; c4 < 2; ++c4)
-                        for (int mb = 0; mb < mbw; ++mb)
-                            for (int lane = 0; lane < 64; ++lane) {
-                                const int cout = (g * mbw + mb) * 16 + (lane & 15);
-                                const int cl = c0 + c4 * 4 + (lane >> 4);
-                                double u = 0.0;
-                                if (cout < out_channels && cl < src_channels[s]) {
-                                    const float* gw = weight + ((size_t)cout * cin_total + (cin_off + cl)) * 4;     // w00 w01 w10 w11
-                                    const double w00 = gw[0], w01 = gw[1], w10 = gw[2], w11 = gw[3];
-                                    u = p == 0 ? ((w00 + w01) + (w10 + w11)) : p == 1 ? (w01 + w11) : p == 2 ? (w10 + w11) : w11;
-                                }
-                                dst[o++] = (float)u;
-                            }
-            cin_off += src_channels[s];
-        }
-    }
+    const int cin_total = wino_sum_channels(src_channels, num_src);
+    wino_pack_stream(dst, 0, out_channels, mbw, NPOS, 0, src_channels, num_src, [=](int cout, int cin, int p) {
+        const float* gw = weight + ((size_t)cout * cin_total + cin) * 4;     // w00 w01 w10 w11
+        const double w00 = gw[0], w01 = gw[1], w10 = gw[2], w11 = gw[3];
+        return p == 0 ? ((w00 + w01) + (w10 + w11)) : p == 1 ? (w01 + w11) : p == 2 ? (w10 + w11) : w11;
+    });
     return 0;
 }
 

@@ -25,16 +25,14 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 #include <type_traits>
 
 #include "../../include/monorec_hip.h"
+#include "lds_dma.h"
+#include "wino_host.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #define B8_MAX_PPT 2          // tile positions staged per thread (ceil(IH * IW / (64 WV)))
 
@@ -73,32 +71,6 @@ struct B8Args {
 #else
 #define B8_DBG(bit) 0
 #endif
-
-__device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const void* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ i32x4 make_srd(const void* base, int bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000;
-    return r;
-}
 
 __device__ __forceinline__ float act1(float v, int act, float p0) {
     switch (act) {
@@ -680,17 +652,7 @@ int derive8(const mr_b8_conv_desc* d, B8Derived* out) {
 
 template <int MB, int NB, int WV, bool WRES, bool F32SRC>
 int launch8w(const B8Derived& dv, hipStream_t stream) {
-    static std::atomic<unsigned long long> attr_set{0};      // dynamic-LDS ceiling once per instantiation AND device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_b8_kernel<MB, NB, WV, WRES, F32SRC>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((conv_b8_kernel<MB, NB, WV, WRES, F32SRC>), dv.grid, dim3(WV * 64), dv.lds_bytes, stream, dv.k);
-    return (int)hipGetLastError();
+    return launch_lds_ceiling<conv_b8_kernel<MB, NB, WV, WRES, F32SRC>>(160 * 1024, dv.grid, dim3(WV * 64), dv.lds_bytes, stream, dv.k);
 }
 
 template <int MB, int NB, int WV>

@@ -147,12 +147,8 @@ __device__ __forceinline__ void kstep(f32x4 (&acc)[MB][NB], const float* __restr
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-// ---- LDS-DMA, issued through inline asm ------------------------------------------------------------------
-// hipcc treats an LDS-DMA builtin as a store that may alias every later ds_read and drains it (vmcnt(0))
-// before the MFMA sweep of the *other* pipeline buffer, which serialises load and compute.  Inline asm is
-// invisible to that pass; the kernel waits itself (dma_wait_all) right before the barrier that publishes the
-// buffer.  M0 (LDS base of the DMA) is saved/restored inside the statement; `s_nop 4` covers the
-// SALU/VALU-write -> VMEM-SGPR-read hazard the compiler does not pad for asm operands.
+// ---- LDS-DMA, issued through inline asm (why, and what the statements pad for: lds_dma.h) ------------------
+// This file keeps its own helpers: they pass the scalar operands as they are, without the readfirstlane of lds_dma.h.
 __device__ __forceinline__ void dma_buffer_dword(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
     unsigned keep;
     asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"

@@ -23,13 +23,10 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 
 #include "../../include/monorec_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+#include "lds_dma.h"
+#include "wino_host.h"
 
 namespace {
 
@@ -63,50 +60,6 @@ struct WinoKArgs {
                                         // (out_channels % 32 in 1..16), handled by 16-row workgroups (wino_rb_tail), or -1
     int tiles_y16;                      // 16-row tile rows of the image (tail workgroups)
 };
-
-// ---- LDS-DMA through inline asm (see conv_mfma.hip: the builtins make hipcc drain vmcnt before every sweep) -------------------
-// (the scalar operands go through readfirstlane: values derived from the wave index are uniform, but the compiler may hold them in
-// VGPRs, which the "s" constraints of the asm do not fix up)
-__device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-// One aligned 8-byte LDS read that stays one: left to itself hipcc drops the halves a caller does not use and re-pairs the rest into ds_read2_b32 -
-// two dword accesses with the 32-bank rule (volatile keeps the access whole; the explicit LDS address space keeps it a ds_ instruction)
-__device__ __forceinline__ f32x2 lds_pair(const float* p) {
-    return *(const volatile __attribute__((address_space(3))) f32x2*)(__attribute__((address_space(3))) const float*)p;
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ i32x4 make_srd(const void* base, int bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// none / ReLU / LeakyReLU as ONE branch-free form, max(x, lo) with lo = x (none), 0 (ReLU: -inf -> 0 and no -0.0, like torch.relu),
-// x * p0 (LeakyReLU, 0 <= p0 <= 1 - the host side rejects other slopes); lo's selector is wave-uniform: as a
-// switch the compiler emitted scalar branches around every stored element of the epilogue (round 4: 200-450 branches per workgroup)
-__device__ __forceinline__ float wino_activate(float v, int act, float p0) {
-    const unsigned keep = act == MR_ACT_RELU ? 0u : ~0u;          // (an AND, not a select: a uniform select made hipcc clone the store loops)
-    const float lo = __uint_as_float(__float_as_uint(v * (act == MR_ACT_LEAKY_RELU ? p0 : 1.f)) & keep);
-    return fmaxf(v, lo);
-}
 
 template <int MBW>
 __global__ __launch_bounds__(512) void conv3x3_wino_kernel(const WinoKArgs a) {
@@ -241,8 +194,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino_kernel(const WinoKArgs a) {
                     o.x += rv.x;
                     o.y += rv.y;
                 }
-                o.x = wino_activate(o.x, a.act, a.p0);
-                o.y = wino_activate(o.y, a.act, a.p0);
+                o.x = act_max(o.x, a.act, a.p0);
+                o.y = act_max(o.y, a.act, a.p0);
                 *(float2*)(a.dst + idx) = o;
             }
         }
@@ -377,8 +330,8 @@ __device__ __forceinline__ void wino_rb_tail(const WinoKArgs& a, float* lds) {
                 o.x += rv.x;
                 o.y += rv.y;
             }
-            o.x = wino_activate(o.x, a.act, a.p0);
-            o.y = wino_activate(o.y, a.act, a.p0);
+            o.x = act_max(o.x, a.act, a.p0);
+            o.y = act_max(o.y, a.act, a.p0);
             *(float2*)(a.dst + idx) = o;
         }
     }
@@ -518,15 +471,14 @@ __global__ __launch_bounds__(512, MBW == 1 ? 4 : 2) void conv3x3_wino_rb_kernel(
                     o.x += rv.x;
                     o.y += rv.y;
                 }
-                o.x = wino_activate(o.x, a.act, a.p0);
-                o.y = wino_activate(o.y, a.act, a.p0);
+                o.x = act_max(o.x, a.act, a.p0);
+                o.y = act_max(o.y, a.act, a.p0);
                 *(float2*)(a.dst + idx) = o;
             }
         }
 }
 
 bool valid_mbw(int m) { return m == 1 || m == 2; }
-int pad8(int c) { return (c + 7) & ~7; }
 
 struct WinoDerived {
     WinoKArgs k;
@@ -537,36 +489,17 @@ struct WinoDerived {
 };
 
 int wino_derive(const mr_wino_desc* d, WinoDerived* out) {
-    if (!d || d->num_src < 1 || d->num_src > MR_MAX_SOURCES || d->batch < 1 || d->height < 1 || d->width < 4 || !d->dst ||
-        !d->packed_weights || d->out_channels < 1)
-        return MR_ERR_BAD_ARGUMENT;
-    if (d->width % 4) return MR_ERR_UNSUPPORTED;              // 16-byte groups entirely inside or outside the image
+    if (const int rc = wino_check_shape(d)) return rc;
     if (!valid_mbw(d->cout_blocks_per_wave)) return MR_ERR_BAD_ARGUMENT;
-    if (d->activation != MR_ACT_NONE && d->activation != MR_ACT_RELU && d->activation != MR_ACT_LEAKY_RELU) return MR_ERR_UNSUPPORTED;
-    if (d->activation == MR_ACT_LEAKY_RELU && !(d->act_p0 >= 0.f && d->act_p0 <= 1.f)) return MR_ERR_UNSUPPORTED;   // the epilogue is max(x, x * slope)
-    if (d->src_row_pitch || d->src_plane_floats || d->dst_split_columns) return MR_ERR_UNSUPPORTED;      // strided views: mr_conv1d_cooktoom_f32 only
+    if (const int rc = wino_check_activation(d)) return rc;
+    if (wino_is_view(d)) return MR_ERR_UNSUPPORTED;
     WinoKArgs& k = out->k;
-    memset(&k, 0, sizeof(k));
-    int nchunks = 0;
-    for (int s = 0; s < d->num_src; ++s) {
-        if (!d->src[s] || d->src_channels[s] < 1) return MR_ERR_BAD_ARGUMENT;
-        const long long bytes = (long long)d->batch * d->src_channels[s] * d->height * d->width * 4;
-        if (bytes >= (1ll << 31)) return MR_ERR_UNSUPPORTED;
-        k.src[s] = d->src[s];
-        k.src_bytes[s] = (int)bytes;
-        k.src_c[s] = d->src_channels[s];
-        k.src_cpad[s] = pad8(d->src_channels[s]);
-        nchunks += k.src_cpad[s] / WCK;
-    }
-    if ((long long)d->batch * d->out_channels * d->height * d->width * 4 >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
-    k.nsrc = d->num_src;
-    k.H = d->height; k.W = d->width;
-    k.dst = d->dst; k.bias = d->bias; k.res = d->residual;
-    k.act = d->activation; k.p0 = d->act_p0;
-    k.Cout = d->out_channels;
+    int nchunks;
+    if (const int rc = wino_fill_args(d, WCK, (long long)d->height * d->width, 0, k, nchunks)) return rc;
+    if (wino_dst_bytes(d) >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
+    k.res = d->residual;
     k.tiles_x = (d->width + 31) / 32;
     k.nchunks = nchunks;
-    k.w = d->packed_weights;
     const int mbw = d->cout_blocks_per_wave;
     const int ufl = 16 * 2 * (2 * mbw) * 64;
     k.wgroup_stride = (long long)nchunks * ufl;
@@ -592,29 +525,28 @@ int wino_derive(const mr_wino_desc* d, WinoDerived* out) {
 
 template <int MBW, bool REGB>
 int wino_launch(const WinoDerived& dv, hipStream_t stream) {
-    static std::atomic<unsigned long long> attr_set{0};      // dynamic-LDS ceiling once per instantiation AND device
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    const void* fn = REGB ? reinterpret_cast<const void*>(&conv3x3_wino_rb_kernel<MBW>) : reinterpret_cast<const void*>(&conv3x3_wino_kernel<MBW>);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    if (REGB) hipLaunchKernelGGL(conv3x3_wino_rb_kernel<MBW>, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
-    else hipLaunchKernelGGL(conv3x3_wino_kernel<MBW>, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
-    return (int)hipGetLastError();
+    if (REGB) return launch_lds_ceiling<conv3x3_wino_rb_kernel<MBW>>(160 * 1024, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
+    return launch_lds_ceiling<conv3x3_wino_kernel<MBW>>(160 * 1024, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
+}
+
+// (cout, cin) filter of an (out_channels, cin_total, 3, 3) tensor -> U[pa][pb] = (G g G^T)[pa][pb], position p = 4 pa + pb
+auto wino_u22(const float* weight, int cin_total) {
+    return [=](int cout, int cin, int p) {
+        const float* gw = weight + ((size_t)cout * cin_total + cin) * 9;
+        const int pa = p >> 2, pb = p & 3;
+        double u = 0.0;
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) u += WINO_G_2_3[pa][i] * (double)gw[i * 3 + j] * WINO_G_2_3[pb][j];
+        return u;
+    };
 }
 
 }  // namespace
 
 extern "C" size_t mr_wino_packed_weight_floats(int32_t out_channels, const int32_t* src_channels, int32_t num_src, int32_t mbw) {
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mbw(mbw) || out_channels < 1) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += pad8(src_channels[s]) / WCK;
     const int groups = (out_channels + 32 * mbw - 1) / (32 * mbw);
-    return (size_t)groups * nchunks * (16 * 2 * (2 * mbw) * 64);
+    return (size_t)groups * wino_chunks(src_channels, num_src) * (16 * 2 * (2 * mbw) * 64);
 }
 
 // weight: (out_channels, sum(src_channels), 3, 3) fp32, nn.Conv2d layout.  U = G g G^T in double, rounded once to fp32; stream order
@@ -624,34 +556,7 @@ extern "C" int mr_wino_pack_weights_f32(const float* weight, int32_t out_channel
                                         int32_t mbw, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mbw(mbw) || out_channels < 1)
         return MR_ERR_BAD_ARGUMENT;
-    static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
-    const int groups = (out_channels + 32 * mbw - 1) / (32 * mbw);
-    size_t o = 0;
-    for (int g = 0; g < groups; ++g) {
-        int cin_off = 0;
-        for (int s = 0; s < num_src; ++s) {
-            const int cpad = pad8(src_channels[s]);
-            for (int c0 = 0; c0 < cpad; c0 += WCK)
-                for (int p = 0; p < 16; ++p)
-                    for (int c4 = 0; c4 < 2; ++c4)
-                        for (int mb = 0; mb < 2 * mbw; ++mb)
-                            for (int lane = 0; lane < 64; ++lane) {
-                                const int cout = g * 32 * mbw + mb * 16 + (lane & 15);
-                                const int cl = c0 + c4 * 4 + (lane >> 4);
-                                double u = 0.0;
-                                if (cout < out_channels && cl < src_channels[s]) {
-                                    const float* gw = weight + ((size_t)cout * cin_total + (cin_off + cl)) * 9;
-                                    const int pa = p >> 2, pb = p & 3;
-                                    for (int i = 0; i < 3; ++i)
-                                        for (int j = 0; j < 3; ++j) u += G[pa][i] * (double)gw[i * 3 + j] * G[pb][j];
-                                }
-                                dst[o++] = (float)u;
-                            }
-            cin_off += src_channels[s];
-        }
-    }
+    wino_pack_stream(dst, 0, out_channels, 2 * mbw, 16, 0, src_channels, num_src, wino_u22(weight, wino_sum_channels(src_channels, num_src)));
     return 0;
 }
 
@@ -661,43 +566,16 @@ extern "C" size_t mr_wino_packed_weight_floats_tail(int32_t out_channels, const 
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || out_channels < 1) return 0;
     const int rem = out_channels % 32;
     if (rem < 1 || rem > 16) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += pad8(src_channels[s]) / WCK;
+    const int nchunks = wino_chunks(src_channels, num_src);
     return (size_t)(out_channels / 32) * nchunks * (16 * 2 * 2 * 64) + (size_t)nchunks * U_FLOATS_T;
 }
 
 extern "C" int mr_wino_pack_weights_tail_f32(const float* weight, int32_t out_channels, const int32_t* src_channels, int32_t num_src, float* dst) {
     if (!weight || !dst || mr_wino_packed_weight_floats_tail(out_channels, src_channels, num_src) == 0) return MR_ERR_BAD_ARGUMENT;
-    static const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-    const int full = out_channels / 32;
-    if (full > 0) {                                      // the full groups: the standard stream of their 32 a channels, cin layout unchanged
-        // (weights of output channel c start at c * cin_total * 9, so the first 32 a channels are a prefix of the tensor)
-        const int rc = mr_wino_pack_weights_f32(weight, full * 32, src_channels, num_src, 1, dst);
-        if (rc != 0) return rc;
-    }
-    int cin_total = 0, nchunks = 0;
-    for (int s = 0; s < num_src; ++s) { cin_total += src_channels[s]; nchunks += pad8(src_channels[s]) / WCK; }
-    size_t o = (size_t)full * nchunks * (16 * 2 * 2 * 64);
-    int cin_off = 0;
-    for (int s = 0; s < num_src; ++s) {
-        const int cpad = pad8(src_channels[s]);
-        for (int c0 = 0; c0 < cpad; c0 += WCK)
-            for (int p = 0; p < 16; ++p)
-                for (int c4 = 0; c4 < 2; ++c4)
-                    for (int lane = 0; lane < 64; ++lane) {
-                        const int cout = full * 32 + (lane & 15);
-                        const int cl = c0 + c4 * 4 + (lane >> 4);
-                        double u = 0.0;
-                        if (cout < out_channels && cl < src_channels[s]) {
-                            const float* gw = weight + ((size_t)cout * cin_total + (cin_off + cl)) * 9;
-                            const int pa = p >> 2, pb = p & 3;
-                            for (int i = 0; i < 3; ++i)
-                                for (int j = 0; j < 3; ++j) u += G[pa][i] * (double)gw[i * 3 + j] * G[pb][j];
-                        }
-                        dst[o++] = (float)u;
-                    }
-        cin_off += src_channels[s];
-    }
+    const auto u = wino_u22(weight, wino_sum_channels(src_channels, num_src));
+    const int full = out_channels / 32 * 32;             // the full groups: the standard stream of their 32 a channels; then the tail's one block
+    const size_t o = wino_pack_stream(dst, 0, full, 2, 16, 0, src_channels, num_src, u);
+    wino_pack_stream(dst + o, full, out_channels, 1, 16, 0, src_channels, num_src, u);
     return 0;
 }
 

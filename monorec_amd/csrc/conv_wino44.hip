@@ -23,14 +23,11 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 #include <type_traits>
 
 #include "../../include/monorec_hip.h"
-#include "cooktoom_1d.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+#include "lds_dma.h"
+#include "wino_host.h"
 
 namespace {
 
@@ -70,43 +67,6 @@ struct W44KArgs {
 // because a run-time flag in a kernel at 254 registers changes what is measured (tried: 1352 -> 2896 us with the flag present and zero).
 // bits: 1 no input transform, 2 no MFMAs, 4 no patch reads, 8 no A reads, 16 no DMA, 32 every DMA instruction of a chunk in one burst behind the barrier
 #define W44_DBG(bit) (DBG & (bit))
-
-// LDS-DMA through inline asm (see conv_mfma.hip: the builtins make hipcc drain vmcnt before every sweep)
-__device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ i32x4 make_srd(const void* base, int bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// none / ReLU / LeakyReLU as ONE branch-free form, max(x, lo) with lo = x (none), 0 (ReLU: -inf -> 0 and no -0.0, like torch.relu),
-// x * p0 (LeakyReLU, 0 <= p0 <= 1 - the host side rejects other slopes); lo's selector is wave-uniform: as a
-// switch the compiler emitted scalar branches around every stored element of the epilogue (round 4: 200-450 branches per workgroup)
-__device__ __forceinline__ float act44(float v, int act, float p0) {
-    const unsigned keep = act == MR_ACT_RELU ? 0u : ~0u;          // (an AND, not a select: a uniform select made hipcc clone the store loops)
-    const float lo = __uint_as_float(__float_as_uint(v * (act == MR_ACT_LEAKY_RELU ? p0 : 1.f)) & keep);
-    return fmaxf(v, lo);
-}
 
 // Measured and not kept (tools/sessions/r04_s23.sh - s25.sh, c3 mask.enc0.0, 1353 us): the ablations add up almost exactly - MFMA 398 + patch
 // reads 371 + input transform 279 + DMA wait 231 + A reads 70 us - i.e. the eight waves of a workgroup hit the LDS, the VALU and the matrix
@@ -308,13 +268,11 @@ __global__ __launch_bounds__(512) void conv3x3_wino44_kernel(const W44KArgs a) {
             const long long idx = ((long long)(b * a.Cout + cout) * H + oy) * W + ox;      // W % 4 == 0 and ox % 4 == 0: all four columns exist
             f32x4 o = (f32x4){y[0] + bs, y[1] + bs, y[2] + bs, y[3] + bs};
             if (a.res) o += *(const f32x4*)(a.res + idx);
-            o.x = act44(o.x, a.act, a.p0); o.y = act44(o.y, a.act, a.p0); o.z = act44(o.z, a.act, a.p0); o.w = act44(o.w, a.act, a.p0);
+            o.x = act_max(o.x, a.act, a.p0); o.y = act_max(o.y, a.act, a.p0); o.z = act_max(o.z, a.act, a.p0); o.w = act_max(o.w, a.act, a.p0);
             *(f32x4*)(a.dst + idx) = o;
         }
     }
 }
-
-int pad8(int c) { return (c + 7) & ~7; }
 
 struct W44Derived {
     W44KArgs k;
@@ -323,35 +281,16 @@ struct W44Derived {
 };
 
 int derive44(const mr_wino_desc* d, W44Derived* out) {
-    if (!d || d->num_src < 1 || d->num_src > MR_MAX_SOURCES || d->batch < 1 || d->height < 1 || d->width < 4 || !d->dst ||
-        !d->packed_weights || d->out_channels < 1)
-        return MR_ERR_BAD_ARGUMENT;
-    if (d->width % 4) return MR_ERR_UNSUPPORTED;              // 16-byte groups entirely inside or outside the image
-    if (d->activation != MR_ACT_NONE && d->activation != MR_ACT_RELU && d->activation != MR_ACT_LEAKY_RELU) return MR_ERR_UNSUPPORTED;
-    if (d->activation == MR_ACT_LEAKY_RELU && !(d->act_p0 >= 0.f && d->act_p0 <= 1.f)) return MR_ERR_UNSUPPORTED;   // the epilogue is max(x, x * slope)
-    if (d->src_row_pitch || d->src_plane_floats || d->dst_split_columns) return MR_ERR_UNSUPPORTED;      // strided views: mr_conv1d_cooktoom_f32 only
+    if (const int rc = wino_check_shape(d)) return rc;
+    if (const int rc = wino_check_activation(d)) return rc;
+    if (wino_is_view(d)) return MR_ERR_UNSUPPORTED;
     W44KArgs& k = out->k;
-    memset(&k, 0, sizeof(k));
-    int nchunks = 0;
-    for (int s = 0; s < d->num_src; ++s) {
-        if (!d->src[s] || d->src_channels[s] < 1) return MR_ERR_BAD_ARGUMENT;
-        const long long bytes = (long long)d->batch * d->src_channels[s] * d->height * d->width * 4;
-        if (bytes >= (1ll << 31)) return MR_ERR_UNSUPPORTED;
-        k.src[s] = d->src[s];
-        k.src_bytes[s] = (int)bytes;
-        k.src_c[s] = d->src_channels[s];
-        k.src_cpad[s] = pad8(d->src_channels[s]);
-        nchunks += k.src_cpad[s] / WCK;
-    }
-    if ((long long)d->batch * d->out_channels * d->height * d->width * 4 >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
-    k.nsrc = d->num_src;
-    k.H = d->height; k.W = d->width;
-    k.dst = d->dst; k.bias = d->bias; k.res = d->residual;
-    k.act = d->activation; k.p0 = d->act_p0;
-    k.Cout = d->out_channels;
+    int nchunks;
+    if (const int rc = wino_fill_args(d, WCK, (long long)d->height * d->width, 0, k, nchunks)) return rc;
+    if (wino_dst_bytes(d) >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
+    k.res = d->residual;
     k.tiles_x = (d->width + RW - 1) / RW;
     k.nchunks = nchunks;
-    k.w = d->packed_weights;
     k.wgroup_stride = (long long)nchunks * U_FLOATS;
     const int groups = (d->out_channels + 31) / 32;
     if (d->batch >= 65536 || groups >= 65536) return MR_ERR_UNSUPPORTED;
@@ -364,9 +303,7 @@ int derive44(const mr_wino_desc* d, W44Derived* out) {
 
 extern "C" size_t mr_wino44_packed_weight_floats(int32_t out_channels, const int32_t* src_channels, int32_t num_src) {
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || out_channels < 1) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += pad8(src_channels[s]) / WCK;
-    return (size_t)((out_channels + 31) / 32) * nchunks * U_FLOATS;
+    return (size_t)((out_channels + 31) / 32) * wino_chunks(src_channels, num_src) * U_FLOATS;
 }
 
 // weight: (out_channels, sum(src_channels), 3, 3) fp32, nn.Conv2d layout.  U = G g G^T (6 x 6; G of F(4,3): cooktoom_1d.h) in double, rounded
@@ -375,8 +312,7 @@ extern "C" size_t mr_wino44_packed_weight_floats(int32_t out_channels, const int
 // operands of a transform column as three 8-byte words.
 extern "C" int mr_wino44_pack_weights_f32(const float* weight, int32_t out_channels, const int32_t* src_channels, int32_t num_src, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || out_channels < 1) return MR_ERR_BAD_ARGUMENT;
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
+    const int cin_total = wino_sum_channels(src_channels, num_src);
     const int groups = (out_channels + 31) / 32;
     size_t o = 0;
     for (int g = 0; g < groups; ++g) {
@@ -386,24 +322,14 @@ extern "C" int mr_wino44_pack_weights_f32(const float* weight, int32_t out_chann
             for (int c0 = 0; c0 < cpad; c0 += WCK)
                 for (int c4 = 0; c4 < 2; ++c4)
                     for (int mb = 0; mb < 2; ++mb)
-                        for (int pj_ = 0; pj_ < 6; ++pj_)
+                        for (int pj = 0; pj < 6; ++pj)
                             for (int lane = 0; lane < 64; ++lane)
-                                for (int pi_ = 0; pi_ < 6; ++pi_) {
-                                const int p = pi_ * 6 + pj_;
-                                const int cout = g * 32 + mb * 16 + (lane & 15);
-                                const int cl = c0 + c4 * 4 + (lane >> 4);
-                                double u = 0.0;
-                                if (cout < out_channels && cl < src_channels[s]) {
-                                    const float* gw = weight + ((size_t)cout * cin_total + (cin_off + cl)) * 9;
-                                    const int pi = p / 6, pj = p % 6;
-                                    for (int i = 0; i < 3; ++i) {
-                                        double row = 0.0;
-                                        for (int j = 0; j < 3; ++j) row += (double)gw[i * 3 + j] * CT_G_4_3[pj][j];
-                                        u += CT_G_4_3[pi][i] * row;
-                                    }
+                                for (int pi = 0; pi < 6; ++pi) {
+                                    const int cout = g * 32 + mb * 16 + (lane & 15);
+                                    const int cl = c0 + c4 * 4 + (lane >> 4);
+                                    const bool real = cout < out_channels && cl < src_channels[s];
+                                    dst[o++] = real ? (float)wino_u44(weight + ((size_t)cout * cin_total + (cin_off + cl)) * 9, pi, pj) : 0.f;
                                 }
-                                dst[o++] = (float)u;
-                            }
             cin_off += src_channels[s];
         }
     }
@@ -420,39 +346,23 @@ extern "C" int mr_conv3x3_winograd44_f32(const mr_wino_desc* desc, void* stream)
     W44Derived dv;
     const int rc = derive44(desc, &dv);
     if (rc != 0) return rc;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    auto launch = [&](auto kernel, std::atomic<unsigned long long>& attr_set) -> int {      // dynamic-LDS ceiling once per device and instantiation
-        if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return (int)e;
-            attr_set.fetch_or(bit, std::memory_order_release);
-        }
-        hipLaunchKernelGGL(kernel, dv.grid, dim3(512), dv.lds_bytes, (hipStream_t)stream, dv.k);
-        return 0;
-    };
-    static std::atomic<unsigned long long> set0{0};
+#define W44_LAUNCH(dbg) launch_lds_ceiling<conv3x3_wino44_kernel<dbg>>(160 * 1024, dv.grid, dim3(512), dv.lds_bytes, (hipStream_t)stream, dv.k)
 #ifdef MR_W44_ABLATE
     static const int dbg = [] { const char* e = getenv("MR_W44_DBG"); return e ? atoi(e) : 0; }();
-    static std::atomic<unsigned long long> setd[8];
-    int rc2 = -1000;
     switch (dbg) {
         case 0: break;
-        case 1: rc2 = launch(conv3x3_wino44_kernel<1>, setd[0]); break;
-        case 2: rc2 = launch(conv3x3_wino44_kernel<2>, setd[1]); break;
-        case 4: rc2 = launch(conv3x3_wino44_kernel<4>, setd[2]); break;
-        case 8: rc2 = launch(conv3x3_wino44_kernel<8>, setd[3]); break;
-        case 16: rc2 = launch(conv3x3_wino44_kernel<16>, setd[4]); break;
-        case 5: rc2 = launch(conv3x3_wino44_kernel<5>, setd[5]); break;
-        case 13: rc2 = launch(conv3x3_wino44_kernel<13>, setd[6]); break;
-        case 29: rc2 = launch(conv3x3_wino44_kernel<29>, setd[7]); break;
-        case 32: rc2 = launch(conv3x3_wino44_kernel<32>, setd[0]); break;
+        case 1: return W44_LAUNCH(1);
+        case 2: return W44_LAUNCH(2);
+        case 4: return W44_LAUNCH(4);
+        case 8: return W44_LAUNCH(8);
+        case 16: return W44_LAUNCH(16);
+        case 5: return W44_LAUNCH(5);
+        case 13: return W44_LAUNCH(13);
+        case 29: return W44_LAUNCH(29);
+        case 32: return W44_LAUNCH(32);
         default: return MR_ERR_BAD_ARGUMENT;
     }
-    if (rc2 != -1000) return rc2 != 0 ? rc2 : (int)hipGetLastError();
 #endif
-    const int rc3 = launch(conv3x3_wino44_kernel<0>, set0);
-    if (rc3 != 0) return rc3;
-    return (int)hipGetLastError();
+    return W44_LAUNCH(0);
+#undef W44_LAUNCH
 }

@@ -19,13 +19,10 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 
 #include "../../include/monorec_hip.h"
-#include "cooktoom_1d.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+#include "lds_dma.h"
+#include "wino_host.h"
 
 namespace {
 
@@ -55,41 +52,6 @@ struct W44SArgs {
     const float* w;
     long long wgroup_stride;            // packed floats per group of 32 output channels
 };
-
-// LDS-DMA through inline asm (see conv_mfma.hip: the builtins make hipcc drain vmcnt before every sweep)
-__device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ i32x4 make_srd(const void* base, int bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// none / ReLU / LeakyReLU (0 <= p0 <= 1) as max(x, lo), lo = x / 0 / x * p0 (see conv_wino44.hip)
-__device__ __forceinline__ float act44s(float v, int act, float p0) {
-    const unsigned keep = act == MR_ACT_RELU ? 0u : ~0u;
-    const float lo = __uint_as_float(__float_as_uint(v * (act == MR_ACT_LEAKY_RELU ? p0 : 1.f)) & keep);
-    return fmaxf(v, lo);
-}
 
 // HF = position half of the wave (template: the two halves run different transform code; one kernel, a wave-uniform branch at the top level)
 template <int HF>
@@ -249,7 +211,7 @@ __device__ __forceinline__ void w44s_body(const W44SArgs& a, float* lds, const i
             for (int c = 0; c < 4; ++c) o[c] = (yp[k * 4 + c] + xch[(r * 16 + k * 4 + c) * 64 + lane]) + bs;
             const long long idx = ((long long)(b * a.Cout + cout) * H + oy) * W + ox;      // W % 4 == 0 and ox % 4 == 0: all four columns exist
             if (a.res) o += *(const f32x4*)(a.res + idx);
-            o.x = act44s(o.x, a.act, a.p0); o.y = act44s(o.y, a.act, a.p0); o.z = act44s(o.z, a.act, a.p0); o.w = act44s(o.w, a.act, a.p0);
+            o.x = act_max(o.x, a.act, a.p0); o.y = act_max(o.y, a.act, a.p0); o.z = act_max(o.z, a.act, a.p0); o.w = act_max(o.w, a.act, a.p0);
             *(f32x4*)(a.dst + idx) = o;
         }
     }
@@ -266,8 +228,6 @@ __global__ __launch_bounds__(512, 4) void conv3x3_wino44s_kernel(const W44SArgs 
     else w44s_body<1>(a, lds, lane, wave, tb, cb);
 }
 
-int pad4(int c) { return (c + 3) & ~3; }
-
 struct W44SDerived {
     W44SArgs k;
     dim3 grid;
@@ -275,35 +235,16 @@ struct W44SDerived {
 };
 
 int derive44s(const mr_wino_desc* d, W44SDerived* out) {
-    if (!d || d->num_src < 1 || d->num_src > MR_MAX_SOURCES || d->batch < 1 || d->height < 1 || d->width < 4 || !d->dst ||
-        !d->packed_weights || d->out_channels < 1)
-        return MR_ERR_BAD_ARGUMENT;
-    if (d->width % 4) return MR_ERR_UNSUPPORTED;              // 16-byte groups entirely inside or outside the image
-    if (d->activation != MR_ACT_NONE && d->activation != MR_ACT_RELU && d->activation != MR_ACT_LEAKY_RELU) return MR_ERR_UNSUPPORTED;
-    if (d->activation == MR_ACT_LEAKY_RELU && !(d->act_p0 >= 0.f && d->act_p0 <= 1.f)) return MR_ERR_UNSUPPORTED;   // the epilogue is max(x, x * slope)
-    if (d->src_row_pitch || d->src_plane_floats || d->dst_split_columns) return MR_ERR_UNSUPPORTED;      // strided views: mr_conv1d_cooktoom_f32 only
+    if (const int rc = wino_check_shape(d)) return rc;
+    if (const int rc = wino_check_activation(d)) return rc;
+    if (wino_is_view(d)) return MR_ERR_UNSUPPORTED;
     W44SArgs& k = out->k;
-    memset(&k, 0, sizeof(k));
-    int nchunks = 0;
-    for (int s = 0; s < d->num_src; ++s) {
-        if (!d->src[s] || d->src_channels[s] < 1) return MR_ERR_BAD_ARGUMENT;
-        const long long bytes = (long long)d->batch * d->src_channels[s] * d->height * d->width * 4;
-        if (bytes >= (1ll << 31)) return MR_ERR_UNSUPPORTED;
-        k.src[s] = d->src[s];
-        k.src_bytes[s] = (int)bytes;
-        k.src_c[s] = d->src_channels[s];
-        k.src_cpad[s] = pad4(d->src_channels[s]);
-        nchunks += k.src_cpad[s] / SCK;
-    }
-    if ((long long)d->batch * d->out_channels * d->height * d->width * 4 >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
-    k.nsrc = d->num_src;
-    k.H = d->height; k.W = d->width;
-    k.dst = d->dst; k.bias = d->bias; k.res = d->residual;
-    k.act = d->activation; k.p0 = d->act_p0;
-    k.Cout = d->out_channels;
+    int nchunks;
+    if (const int rc = wino_fill_args(d, SCK, (long long)d->height * d->width, 0, k, nchunks)) return rc;
+    if (wino_dst_bytes(d) >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
+    k.res = d->residual;
     k.tiles_x = (d->width + RW - 1) / RW;
     k.nchunks = nchunks;
-    k.w = d->packed_weights;
     k.wgroup_stride = (long long)nchunks * U_FLOATS;
     const int groups = (d->out_channels + 31) / 32;
     if (d->batch >= 65536 || groups >= 65536) return MR_ERR_UNSUPPORTED;
@@ -317,9 +258,7 @@ int derive44s(const mr_wino_desc* d, W44SDerived* out) {
 
 extern "C" size_t mr_wino44s_packed_weight_floats(int32_t out_channels, const int32_t* src_channels, int32_t num_src) {
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || out_channels < 1) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += pad4(src_channels[s]) / SCK;
-    return (size_t)((out_channels + 31) / 32) * nchunks * U_FLOATS;
+    return (size_t)((out_channels + 31) / 32) * wino_chunks(src_channels, num_src, SCK) * U_FLOATS;
 }
 
 // weight: (out_channels, sum(src_channels), 3, 3) fp32, nn.Conv2d layout.  U = G g G^T (6 x 6; G of F(4,3): cooktoom_1d.h) in double, rounded
@@ -329,35 +268,26 @@ extern "C" size_t mr_wino44s_packed_weight_floats(int32_t out_channels, const in
 // 16-byte words.
 extern "C" int mr_wino44s_pack_weights_f32(const float* weight, int32_t out_channels, const int32_t* src_channels, int32_t num_src, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || out_channels < 1) return MR_ERR_BAD_ARGUMENT;
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
+    const int cin_total = wino_sum_channels(src_channels, num_src);
     const int groups = (out_channels + 31) / 32;
     size_t o = 0;
     for (int g = 0; g < groups; ++g) {
         int cin_off = 0;
         for (int s = 0; s < num_src; ++s) {
-            const int cpad = pad4(src_channels[s]);
+            const int cpad = mr_pad4(src_channels[s]);
             for (int c0 = 0; c0 < cpad; c0 += SCK)
                 for (int mb = 0; mb < 2; ++mb)
                     for (int hf = 0; hf < 2; ++hf)
                         for (int ii = 0; ii < 3; ++ii)
                             for (int jh = 0; jh < 2; ++jh)
-                            for (int lane = 0; lane < 64; ++lane)
-                                for (int e = 0; e < 4; ++e) {
-                                    const int pi = 3 * hf + ii, pj = 4 * jh + e;
-                                    const int cout = g * 32 + mb * 16 + (lane & 15);
-                                    const int cl = c0 + (lane >> 4);
-                                    double u = 0.0;
-                                    if (pj < 6 && cout < out_channels && cl < src_channels[s]) {
-                                        const float* gw = weight + ((size_t)cout * cin_total + (cin_off + cl)) * 9;
-                                        for (int i = 0; i < 3; ++i) {
-                                            double row = 0.0;
-                                            for (int j = 0; j < 3; ++j) row += (double)gw[i * 3 + j] * CT_G_4_3[pj][j];
-                                            u += CT_G_4_3[pi][i] * row;
-                                        }
+                                for (int lane = 0; lane < 64; ++lane)
+                                    for (int e = 0; e < 4; ++e) {
+                                        const int pi = 3 * hf + ii, pj = 4 * jh + e;
+                                        const int cout = g * 32 + mb * 16 + (lane & 15);
+                                        const int cl = c0 + (lane >> 4);
+                                        const bool real = pj < 6 && cout < out_channels && cl < src_channels[s];
+                                        dst[o++] = real ? (float)wino_u44(weight + ((size_t)cout * cin_total + (cin_off + cl)) * 9, pi, pj) : 0.f;
                                     }
-                                    dst[o++] = (float)u;
-                                }
             cin_off += src_channels[s];
         }
     }
@@ -374,15 +304,5 @@ extern "C" int mr_conv3x3_winograd44s_f32(const mr_wino_desc* desc, void* stream
     W44SDerived dv;
     const int rc = derive44s(desc, &dv);
     if (rc != 0) return rc;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    static std::atomic<unsigned long long> attr_set{0};          // dynamic-LDS ceiling once per device
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_wino44s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(conv3x3_wino44s_kernel, dv.grid, dim3(512), dv.lds_bytes, (hipStream_t)stream, dv.k);
-    return (int)hipGetLastError();
+    return launch_lds_ceiling<conv3x3_wino44s_kernel>(80 * 1024, dv.grid, dim3(512), dv.lds_bytes, (hipStream_t)stream, dv.k);   // 80 KB: two workgroups per CU
 }

@@ -18,14 +18,11 @@
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
-#include <atomic>
 #include <type_traits>
 
 #include "../../include/monorec_hip.h"
-#include "cooktoom_1d.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+#include "lds_dma.h"
+#include "wino_host.h"
 
 namespace {
 
@@ -57,50 +54,6 @@ struct W44WArgs {
     const float* w;
     long long wgroup_stride;            // packed floats per group of 32 output channels
 };
-
-__device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-// s_waitcnt vmcnt(N) takes an immediate: wait until at most `n` (wave-uniform) of this wave's VMEM instructions are outstanding (rounding down is safe)
-#define MR_VMCNT_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-__device__ __forceinline__ void dma_wait_upto(int n) {
-    switch (n < 32 ? n : (n < 48 ? 32 : 48)) {
-        MR_VMCNT_CASE(0) MR_VMCNT_CASE(1) MR_VMCNT_CASE(2) MR_VMCNT_CASE(3) MR_VMCNT_CASE(4) MR_VMCNT_CASE(5) MR_VMCNT_CASE(6) MR_VMCNT_CASE(7)
-        MR_VMCNT_CASE(8) MR_VMCNT_CASE(9) MR_VMCNT_CASE(10) MR_VMCNT_CASE(11) MR_VMCNT_CASE(12) MR_VMCNT_CASE(13) MR_VMCNT_CASE(14) MR_VMCNT_CASE(15)
-        MR_VMCNT_CASE(16) MR_VMCNT_CASE(17) MR_VMCNT_CASE(18) MR_VMCNT_CASE(19) MR_VMCNT_CASE(20) MR_VMCNT_CASE(21) MR_VMCNT_CASE(22) MR_VMCNT_CASE(23)
-        MR_VMCNT_CASE(24) MR_VMCNT_CASE(25) MR_VMCNT_CASE(26) MR_VMCNT_CASE(27) MR_VMCNT_CASE(28) MR_VMCNT_CASE(29) MR_VMCNT_CASE(30) MR_VMCNT_CASE(31)
-        MR_VMCNT_CASE(32) MR_VMCNT_CASE(48)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
-
-__device__ __forceinline__ i32x4 make_srd(const void* base, int bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-__device__ __forceinline__ float act44w(float v, int act, float p0) {          // none / ReLU / LeakyReLU (0 <= p0 <= 1) as max(x, lo), see conv_wino44.hip
-    const unsigned keep = act == MR_ACT_RELU ? 0u : ~0u;
-    const float lo = __uint_as_float(__float_as_uint(v * (act == MR_ACT_LEAKY_RELU ? p0 : 1.f)) & keep);
-    return fmaxf(v, lo);
-}
 
 // 72 accumulator sets are 288 registers and the AGPR file has 256: once a kernel needs AGPRs hipcc gives EVERY builtin MFMA an AGPR accumulator and
 // shuttles the sets that do not fit through v_accvgpr_read / _write around each use (104 moves in the first transform column of every quad, measured on
@@ -316,7 +269,7 @@ __device__ __forceinline__ void w44w_body(const W44WArgs& a, float* lds) {
                 const long long idx = ((long long)(b * a.Cout + cout) * H + oy) * W + ox;      // W % 4 == 0 and ox % 4 == 0: all four columns exist
                 f32x4 o = (f32x4){y[0] + bs, y[1] + bs, y[2] + bs, y[3] + bs};
                 if (a.res) o += *(const f32x4*)(a.res + idx);
-                o.x = act44w(o.x, a.act, a.p0); o.y = act44w(o.y, a.act, a.p0); o.z = act44w(o.z, a.act, a.p0); o.w = act44w(o.w, a.act, a.p0);
+                o.x = act_max(o.x, a.act, a.p0); o.y = act_max(o.y, a.act, a.p0); o.z = act_max(o.z, a.act, a.p0); o.w = act_max(o.w, a.act, a.p0);
                 *(f32x4*)(a.dst + idx) = o;
             }
         }
@@ -329,8 +282,6 @@ __global__ __launch_bounds__(256) void conv3x3_wino44w_kernel(const W44WArgs a) 
     else w44w_body<1>(a, lds);
 }
 
-int pad8(int c) { return (c + 7) & ~7; }
-
 struct W44WDerived {
     W44WArgs k;
     dim3 grid;
@@ -338,36 +289,17 @@ struct W44WDerived {
 };
 
 int derive44w(const mr_wino_desc* d, W44WDerived* out) {
-    if (!d || d->num_src < 1 || d->num_src > MR_MAX_SOURCES || d->batch < 1 || d->height < 1 || d->width < 4 || !d->dst ||
-        !d->packed_weights || d->out_channels < 1)
-        return MR_ERR_BAD_ARGUMENT;
-    if (d->width % 4) return MR_ERR_UNSUPPORTED;              // 16-byte groups entirely inside or outside the image
-    if (d->activation != MR_ACT_NONE && d->activation != MR_ACT_RELU && d->activation != MR_ACT_LEAKY_RELU) return MR_ERR_UNSUPPORTED;
-    if (d->activation == MR_ACT_LEAKY_RELU && !(d->act_p0 >= 0.f && d->act_p0 <= 1.f)) return MR_ERR_UNSUPPORTED;   // the epilogue is max(x, x * slope)
-    if (d->src_row_pitch || d->src_plane_floats || d->dst_split_columns) return MR_ERR_UNSUPPORTED;      // strided views: mr_conv1d_cooktoom_f32 only
+    if (const int rc = wino_check_shape(d)) return rc;
+    if (const int rc = wino_check_activation(d)) return rc;
+    if (wino_is_view(d)) return MR_ERR_UNSUPPORTED;
     W44WArgs& k = out->k;
-    memset(&k, 0, sizeof(k));
-    int nquads = 0;
-    for (int s = 0; s < d->num_src; ++s) {
-        if (!d->src[s] || d->src_channels[s] < 1) return MR_ERR_BAD_ARGUMENT;
-        const long long bytes = (long long)d->batch * d->src_channels[s] * d->height * d->width * 4;
-        if (bytes >= (1ll << 31)) return MR_ERR_UNSUPPORTED;
-        k.src[s] = d->src[s];
-        k.src_bytes[s] = (int)bytes;
-        k.src_c[s] = d->src_channels[s];
-        k.src_cpad[s] = pad8(d->src_channels[s]);
-        nquads += k.src_cpad[s] / 4;
-    }
-    if ((long long)d->batch * d->out_channels * d->height * d->width * 4 >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
-    k.nsrc = d->num_src;
-    k.H = d->height; k.W = d->width;
-    k.dst = d->dst; k.bias = d->bias; k.res = d->residual;
-    k.act = d->activation; k.p0 = d->act_p0;
-    k.Cout = d->out_channels;
+    int nchunks;
+    if (const int rc = wino_fill_args(d, 8, (long long)d->height * d->width, 0, k, nchunks)) return rc;
+    if (wino_dst_bytes(d) >= (1ll << 33)) return MR_ERR_UNSUPPORTED;
+    k.res = d->residual;
     k.tiles_x = (d->width + RW - 1) / RW;
-    k.nquads = nquads;
-    k.w = d->packed_weights;
-    k.wgroup_stride = (long long)nquads * UQ_FLOATS;
+    k.nquads = 2 * nchunks;                              // the stream of conv_wino44.hip, chunks of 8 channels, walked a quad at a time
+    k.wgroup_stride = (long long)k.nquads * UQ_FLOATS;
     const int groups = (d->out_channels + 31) / 32;
     if (d->batch >= 65536 || groups >= 65536) return MR_ERR_UNSUPPORTED;
     out->grid = dim3((unsigned)(k.tiles_x * ((d->height + RH - 1) / RH)), (unsigned)groups, (unsigned)d->batch);
@@ -387,15 +319,5 @@ extern "C" int mr_conv3x3_winograd44w_f32(const mr_wino_desc* desc, void* stream
     W44WDerived dv;
     const int rc = derive44w(desc, &dv);
     if (rc != 0) return rc;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    static std::atomic<unsigned long long> attr_set{0};      // dynamic-LDS ceiling once per device
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino44w_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(conv3x3_wino44w_kernel, dv.grid, dim3(256), dv.lds_bytes, (hipStream_t)stream, dv.k);
-    return (int)hipGetLastError();
+    return launch_lds_ceiling<conv3x3_wino44w_kernel>(160 * 1024, dv.grid, dim3(256), dv.lds_bytes, (hipStream_t)stream, dv.k);
 }

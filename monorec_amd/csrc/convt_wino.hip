@@ -16,12 +16,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
-#include <atomic>
 
 #include "../../include/monorec_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+#include "lds_dma.h"
+#include "wino_host.h"
 
 namespace {
 
@@ -51,49 +49,6 @@ struct WinoTKArgs {
     int tail_grp;                       // variant 2: index of the 16-channel tail group (out_channels % 32 in 1..16) or -1, see convt_rb_tail
     int tiles_y16;
 };
-
-__device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-__device__ __forceinline__ void dma_global_x1(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ i32x4 make_srd(const void* base, int bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000;
-    return r;
-}
-
-// none / ReLU / LeakyReLU as ONE branch-free form, max(x, lo) with lo = x (none), 0 (ReLU: -inf -> 0 and no -0.0, like torch.relu),
-// x * p0 (LeakyReLU, 0 <= p0 <= 1 - the host side rejects other slopes); lo's selector is wave-uniform: as a
-// switch the compiler emitted scalar branches around every stored element of the epilogue (round 4: 200-450 branches per workgroup)
-__device__ __forceinline__ float act_t(float v, int act, float p0) {
-    const unsigned keep = act == MR_ACT_RELU ? 0u : ~0u;          // (an AND, not a select: a uniform select made hipcc clone the store loops)
-    const float lo = __uint_as_float(__float_as_uint(v * (act == MR_ACT_LEAKY_RELU ? p0 : 1.f)) & keep);
-    return fmaxf(v, lo);
-}
 
 template <int MBW>
 __global__ __launch_bounds__(512) void convt4x4_wino_kernel(const WinoTKArgs a) {
@@ -224,8 +179,8 @@ __global__ __launch_bounds__(512) void convt4x4_wino_kernel(const WinoTKArgs a) 
                 const int yo = yb + i;
                 if (yo >= H) continue;
                 float* o = a.dst + ((long long)(b * a.Cout + cout) * (2 * H) + (2 * yo + py)) * OW + 2 * xo + px;
-                o[0] = act_t(y[i][0] + bs, a.act, a.p0);
-                if (xo + 1 < W) o[2] = act_t(y[i][1] + bs, a.act, a.p0);
+                o[0] = act_max(y[i][0] + bs, a.act, a.p0);
+                if (xo + 1 < W) o[2] = act_max(y[i][1] + bs, a.act, a.p0);
             }
         }
 }
@@ -350,8 +305,8 @@ __device__ __forceinline__ void convt_rb_tail(const WinoTKArgs& a, float* lds) {
             const int yo = yb + i;
             if (yo >= H) continue;
             float* o = a.dst + ((long long)(b * a.Cout + cout) * (2 * H) + (2 * yo + py)) * OW + 2 * xo + px;
-            o[0] = act_t(y[i][0] + bs, a.act, a.p0);
-            if (xo + 1 < W) o[2] = act_t(y[i][1] + bs, a.act, a.p0);
+            o[0] = act_max(y[i][0] + bs, a.act, a.p0);
+            if (xo + 1 < W) o[2] = act_max(y[i][1] + bs, a.act, a.p0);
         }
     }
 }
@@ -486,14 +441,13 @@ __global__ __launch_bounds__(512) void convt4x4_wino_rb_kernel(const WinoTKArgs 
                 const int yo = yb + i;
                 if (yo >= H) continue;
                 float* o = a.dst + ((long long)(b * a.Cout + cout) * (2 * H) + (2 * yo + py)) * OW + 2 * xo + px;
-                o[0] = act_t(y[i][0] + bs, a.act, a.p0);
-                if (xo + 1 < W) o[2] = act_t(y[i][1] + bs, a.act, a.p0);
+                o[0] = act_max(y[i][0] + bs, a.act, a.p0);
+                if (xo + 1 < W) o[2] = act_max(y[i][1] + bs, a.act, a.p0);
             }
         }
 }
 
 bool valid_mbw_t(int m) { return m == 1 || m == 2 || m == 4; }
-int pad8(int c) { return (c + 7) & ~7; }
 
 struct WinoTDerived {
     WinoTKArgs k;
@@ -504,42 +458,24 @@ struct WinoTDerived {
 };
 
 int derive_t(const mr_wino_desc* d, WinoTDerived* out) {
-    if (!d || d->num_src < 1 || d->num_src > MR_MAX_SOURCES || d->batch < 1 || d->height < 1 || d->width < 4 || !d->dst ||
-        !d->packed_weights || d->out_channels < 1 || d->residual)
-        return MR_ERR_BAD_ARGUMENT;
-    if (d->width % 4) return MR_ERR_UNSUPPORTED;
+    if (d && d->residual) return MR_ERR_BAD_ARGUMENT;        // no residual input in this epilogue
+    if (const int rc = wino_check_shape(d)) return rc;
     if (!valid_mbw_t(d->cout_blocks_per_wave)) return MR_ERR_BAD_ARGUMENT;
-    if (d->activation != MR_ACT_NONE && d->activation != MR_ACT_RELU && d->activation != MR_ACT_LEAKY_RELU) return MR_ERR_UNSUPPORTED;
-    if (d->activation == MR_ACT_LEAKY_RELU && !(d->act_p0 >= 0.f && d->act_p0 <= 1.f)) return MR_ERR_UNSUPPORTED;   // the epilogue is max(x, x * slope)
-    if (d->src_row_pitch || d->src_plane_floats || d->dst_split_columns) return MR_ERR_UNSUPPORTED;      // strided views: mr_conv1d_cooktoom_f32 only
+    if (const int rc = wino_check_activation(d)) return rc;
+    if (wino_is_view(d)) return MR_ERR_UNSUPPORTED;
     WinoTKArgs& k = out->k;
-    memset(&k, 0, sizeof(k));
-    int nchunks = 0;
-    for (int s = 0; s < d->num_src; ++s) {
-        if (!d->src[s] || d->src_channels[s] < 1) return MR_ERR_BAD_ARGUMENT;
-        const long long bytes = (long long)d->batch * d->src_channels[s] * d->height * d->width * 4;
-        if (bytes >= (1ll << 31)) return MR_ERR_UNSUPPORTED;
-        k.src[s] = d->src[s];
-        k.src_bytes[s] = (int)bytes;
-        k.src_c[s] = d->src_channels[s];
-        k.src_cpad[s] = pad8(d->src_channels[s]);
-        nchunks += k.src_cpad[s] / WCK;
-    }
-    k.nsrc = d->num_src;
-    k.H = d->height; k.W = d->width;
-    k.dst = d->dst; k.bias = d->bias;
-    k.act = d->activation; k.p0 = d->act_p0;
-    k.Cout = d->out_channels;
+    int nchunks;
+    if (const int rc = wino_fill_args(d, WCK, (long long)d->height * d->width, 0, k, nchunks)) return rc;
+    // (this entry has no 2^33-byte cap on the destination)
     k.tiles_x = (d->width + 31) / 32;
     k.nchunks = nchunks;
-    k.w = d->packed_weights;
     const int mbw = d->cout_blocks_per_wave;
     const int ufl = NPOS * 2 * (2 * mbw) * 64;
     const int groups = (d->out_channels + 32 * mbw - 1) / (32 * mbw);
     k.ngroups = groups;
     k.wgroup_stride = (long long)nchunks * ufl;
     k.wphase_stride = (long long)groups * nchunks * ufl;
-    if (d->batch * 4 >= 65536 || groups >= 65536) return MR_ERR_UNSUPPORTED;
+    if (d->batch * 4 >= 65536 || groups >= 65536) return MR_ERR_UNSUPPORTED;     // grid z = (batch, parity)
     out->grid = dim3((unsigned)(k.tiles_x * ((d->height + 7) / 8)), (unsigned)groups, (unsigned)(d->batch * 4));
     if (d->variant < 0 || d->variant > 2) return MR_ERR_BAD_ARGUMENT;
     out->regb = d->variant >= 1;
@@ -559,29 +495,30 @@ int derive_t(const mr_wino_desc* d, WinoTDerived* out) {
 
 template <int MBW, bool REGB>
 int launch_t(const WinoTDerived& dv, hipStream_t stream) {
-    static std::atomic<unsigned long long> attr_set{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    const void* fn = REGB ? reinterpret_cast<const void*>(&convt4x4_wino_rb_kernel<MBW>) : reinterpret_cast<const void*>(&convt4x4_wino_kernel<MBW>);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    if (REGB) hipLaunchKernelGGL(convt4x4_wino_rb_kernel<MBW>, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
-    else hipLaunchKernelGGL(convt4x4_wino_kernel<MBW>, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
-    return (int)hipGetLastError();
+    if (REGB) return launch_lds_ceiling<convt4x4_wino_rb_kernel<MBW>>(160 * 1024, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
+    return launch_lds_ceiling<convt4x4_wino_kernel<MBW>>(160 * 1024, dv.grid, dim3(512), dv.lds_bytes, stream, dv.k);
+}
+
+// (cout, cin) filter of the (cin_total, out_channels, 4, 4) tensor, output parity (py, px) -> U[pa][pb] = (G g G^T)[pa][pb], p = 3 pa + pb
+auto convt_u(const float* weight, int out_channels, int py, int px) {
+    return [=](int cout, int cin, int p) {
+        static const double G[3][2] = {{1.0, 0.0}, {1.0, 1.0}, {0.0, 1.0}};
+        static const int taps[2][2] = {{3, 1}, {2, 0}};
+        const float* gw = weight + ((size_t)cin * out_channels + cout) * 16;
+        const int pa = p / 3, pb = p % 3;
+        double u = 0.0;
+        for (int i = 0; i < 2; ++i)
+            for (int j = 0; j < 2; ++j) u += G[pa][i] * (double)gw[taps[py][i] * 4 + taps[px][j]] * G[pb][j];
+        return u;
+    };
 }
 
 }  // namespace
 
 extern "C" size_t mr_wino_t_packed_weight_floats(int32_t out_channels, const int32_t* src_channels, int32_t num_src, int32_t mbw) {
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mbw_t(mbw) || out_channels < 1) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += pad8(src_channels[s]) / WCK;
     const int groups = (out_channels + 32 * mbw - 1) / (32 * mbw);
-    return (size_t)4 * groups * nchunks * (NPOS * 2 * (2 * mbw) * 64);
+    return (size_t)4 * groups * wino_chunks(src_channels, num_src) * (NPOS * 2 * (2 * mbw) * 64);
 }
 
 // weight: the nn.ConvTranspose2d tensor (sum(src_channels), out_channels, 4, 4).  Parity (py, px) reads its kernel rows ky = {3, 1}
@@ -592,36 +529,8 @@ extern "C" int mr_wino_t_pack_weights_f32(const float* weight, int32_t out_chann
                                           int32_t mbw, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mbw_t(mbw) || out_channels < 1)
         return MR_ERR_BAD_ARGUMENT;
-    static const double G[3][2] = {{1.0, 0.0}, {1.0, 1.0}, {0.0, 1.0}};
-    static const int taps[2][2] = {{3, 1}, {2, 0}};
-    const int groups = (out_channels + 32 * mbw - 1) / (32 * mbw);
-    size_t o = 0;
-    for (int ph = 0; ph < 4; ++ph) {
-        const int py = ph >> 1, px = ph & 1;
-        for (int g = 0; g < groups; ++g) {
-            int cin_off = 0;
-            for (int s = 0; s < num_src; ++s) {
-                const int cpad = pad8(src_channels[s]);
-                for (int c0 = 0; c0 < cpad; c0 += WCK)
-                    for (int p = 0; p < NPOS; ++p)
-                        for (int c4 = 0; c4 < 2; ++c4)
-                            for (int mb = 0; mb < 2 * mbw; ++mb)
-                                for (int lane = 0; lane < 64; ++lane) {
-                                    const int cout = g * 32 * mbw + mb * 16 + (lane & 15);
-                                    const int cl = c0 + c4 * 4 + (lane >> 4);
-                                    double u = 0.0;
-                                    if (cout < out_channels && cl < src_channels[s]) {
-                                        const float* gw = weight + ((size_t)(cin_off + cl) * out_channels + cout) * 16;
-                                        const int pa = p / 3, pb = p % 3;
-                                        for (int i = 0; i < 2; ++i)
-                                            for (int j = 0; j < 2; ++j) u += G[pa][i] * (double)gw[taps[py][i] * 4 + taps[px][j]] * G[pb][j];
-                                    }
-                                    dst[o++] = (float)u;
-                                }
-                cin_off += src_channels[s];
-            }
-        }
-    }
+    for (int ph = 0; ph < 4; ++ph)
+        dst += wino_pack_stream(dst, 0, out_channels, 2 * mbw, NPOS, 0, src_channels, num_src, convt_u(weight, out_channels, ph >> 1, ph & 1));
     return 0;
 }
 
@@ -631,43 +540,17 @@ extern "C" size_t mr_wino_t_packed_weight_floats_tail(int32_t out_channels, cons
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || out_channels < 1) return 0;
     const int rem = out_channels % 32;
     if (rem < 1 || rem > 16) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += pad8(src_channels[s]) / WCK;
+    const int nchunks = wino_chunks(src_channels, num_src);
     return (size_t)4 * ((size_t)(out_channels / 32) * nchunks * (NPOS * 2 * 2 * 64) + (size_t)nchunks * U_FLOATS_TT);
 }
 
 extern "C" int mr_wino_t_pack_weights_tail_f32(const float* weight, int32_t out_channels, const int32_t* src_channels, int32_t num_src, float* dst) {
     if (!weight || !dst || mr_wino_t_packed_weight_floats_tail(out_channels, src_channels, num_src) == 0) return MR_ERR_BAD_ARGUMENT;
-    static const double G[3][2] = {{1.0, 0.0}, {1.0, 1.0}, {0.0, 1.0}};
-    static const int taps[2][2] = {{3, 1}, {2, 0}};
-    const int full = out_channels / 32;
-    size_t o = 0;
+    const int full = out_channels / 32 * 32;
     for (int ph = 0; ph < 4; ++ph) {
-        const int py = ph >> 1, px = ph & 1;
-        for (int g = 0; g <= full; ++g) {                    // g == full: the tail group (one block of 16 channels)
-            const int nblk = g < full ? 2 : 1;
-            int cin_off = 0;
-            for (int s = 0; s < num_src; ++s) {
-                const int cpad = pad8(src_channels[s]);
-                for (int c0 = 0; c0 < cpad; c0 += WCK)
-                    for (int p = 0; p < NPOS; ++p)
-                        for (int c4 = 0; c4 < 2; ++c4)
-                            for (int mb = 0; mb < nblk; ++mb)
-                                for (int lane = 0; lane < 64; ++lane) {
-                                    const int cout = g * 32 + mb * 16 + (lane & 15);
-                                    const int cl = c0 + c4 * 4 + (lane >> 4);
-                                    double u = 0.0;
-                                    if (cout < out_channels && cl < src_channels[s]) {
-                                        const float* gw = weight + ((size_t)(cin_off + cl) * out_channels + cout) * 16;
-                                        const int pa = p / 3, pb = p % 3;
-                                        for (int i = 0; i < 2; ++i)
-                                            for (int j = 0; j < 2; ++j) u += G[pa][i] * (double)gw[taps[py][i] * 4 + taps[px][j]] * G[pb][j];
-                                    }
-                                    dst[o++] = (float)u;
-                                }
-                cin_off += src_channels[s];
-            }
-        }
+        const auto u = convt_u(weight, out_channels, ph >> 1, ph & 1);
+        dst += wino_pack_stream(dst, 0, full, 2, NPOS, 0, src_channels, num_src, u);
+        dst += wino_pack_stream(dst, full, out_channels, 1, NPOS, 0, src_channels, num_src, u);      // the tail group: one block of 16 channels
     }
     return 0;
 }

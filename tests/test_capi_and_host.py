@@ -1472,3 +1472,57 @@ def test_b8_schedule_table_overrides_the_rule_per_launch_signature(monkeypatch):
         same_key = c0["sig"] + f"_f{int(c0['f32_source'])}" == key
         assert (c1["mb"], c1["nb"], c1["waves"]) == ((1, 1, 4) if same_key else (c0["mb"], c0["nb"], c0["waves"])), c0["name"]
     assert plan.launch_stamp() != base.launch_stamp()
+
+
+def _reduced_conv_descriptor_codes(lib):
+    """{entry point: [result per descriptor]} for the descriptors of test_reduced_conv_descriptor_errors, in `_REDUCED_CONV_BREAKS` order."""
+    ptr = 1 << 20                                                # never dereferenced: the *_lds_bytes entry points only derive
+    def desc(**broken):
+        d = _lib.WinoDesc()
+        d.src[0], d.src_channels[0], d.num_src = ptr, 8, 1
+        d.batch, d.height, d.width = 1, 8, 8
+        d.dst, d.out_channels, d.packed_weights = ptr, 16, ptr
+        d.activation, d.act_p0, d.cout_blocks_per_wave = _lib.ACT_LEAKY_RELU, 0.1, 1
+        for k, v in broken.items():
+            setattr(d, k, v)
+        return d
+    entries = {"w22": lib.mr_conv3x3_winograd_lds_bytes, "t22": lib.mr_convt4x4s2_winograd_lds_bytes, "f23": lib.mr_conv1d3_winograd_lds_bytes,
+               "ct43y": lambda d: lib.mr_conv1d_cooktoom_lds_bytes(d, 1, 4, 3), "w44": lib.mr_conv3x3_winograd44_lds_bytes,
+               "w44s": lib.mr_conv3x3_winograd44s_lds_bytes, "w44w": lib.mr_conv3x3_winograd44w_lds_bytes}
+    return {name: [int(fn(ctypes.byref(desc(**broken)))) for _, broken in _REDUCED_CONV_BREAKS] for name, fn in entries.items()}
+
+
+_REDUCED_CONV_BREAKS = [
+    ("valid", {}), ("null dst", dict(dst=None)), ("null packed_weights", dict(packed_weights=None)), ("width 6", dict(width=6)),
+    ("num_src 0", dict(num_src=0)), ("activation 7", dict(activation=7)), ("slope 1.5", dict(act_p0=1.5)), ("residual", dict(residual=1 << 20)),
+    ("src_row_pitch 16", dict(src_row_pitch=16)), ("dst_split_columns", dict(dst_split_columns=1)), ("9 blocks per wave", dict(cout_blocks_per_wave=9)),
+    ("variant 3", dict(variant=3)), ("batch 65536", dict(batch=65536)), ("batch 20000", dict(batch=20000)),
+    ("2^33-byte destination", dict(batch=16384, out_channels=1024, height=8, width=16)),
+    ("2^33-byte destination, batch 8192", dict(batch=8192, out_channels=2048, height=8, width=16))]
+
+
+def test_reduced_conv_descriptor_errors(hip_lib):
+    """What the derive functions of the reduced-multiply kernels (csrc/conv_wino*.hip, convt_wino.hip, conv1d_wino.hip; shared checks in
+    csrc/wino_host.h) answer to one valid tiny descriptor (batch 1, 8 -> 16 channels, 8 x 8) and to that descriptor with one field broken at a
+    time: the LDS size, or -1 MR_ERR_BAD_ARGUMENT / -2 MR_ERR_UNSUPPORTED.  The table was recorded from the library as it was BEFORE the
+    checks moved into the shared header, and it pins where the entry points differ on purpose: `residual` is a bad argument for the
+    transposed convolution, unsupported on the 1-D kernels and accepted by the 3x3 ones; a parity-split destination is accepted only by the
+    Cook-Toom entry (its row-pitch view fails there as a bad argument: the default plane does not hold 8 rows of pitch 16); batch 20000 passes
+    every grid cap but the transposed convolution's batch * 4; a destination of exactly 2^33 bytes (its source far below 2^31) is refused
+    by the 2^33 cap everywhere but there - at batch 16384 the transposed convolution still refuses, through batch * 4, so the same size at
+    batch 8192 follows, which it accepts."""
+    # columns: valid, dst, packed_weights, width 6, num_src, activation, slope, residual, row pitch, split, 9 blocks, variant 3, batch 65536, batch 20000,
+    # 2^33 bytes at batch 16384, 2^33 bytes at batch 8192
+    expected = {
+        "w22": [100352, -1, -1, -2, -1, -2, -2, 100352, -2, -2, -1, -1, -2, 100352, -2, -2],
+        "t22": [67072, -1, -1, -2, -1, -2, -2, -1, -2, -2, -1, -1, -2, -2, -2, 67072],
+        "f23": [30720, -1, -1, -2, -1, -2, -2, -2, -2, -2, -1, 30720, -2, 30720, -2, -2],
+        "ct43y": [52224, -1, -1, -2, -1, -2, -2, -2, -1, 52224, -1, 52224, -2, 52224, -2, -2],
+        "w44": [159744, -1, -1, -2, -1, -2, -2, 159744, -2, -2, 159744, 159744, -2, 159744, -2, -2],
+        "w44s": [73728, -1, -1, -2, -1, -2, -2, 73728, -2, -2, 73728, 73728, -2, 73728, -2, -2],
+        "w44w": [159744, -1, -1, -2, -1, -2, -2, 159744, -2, -2, 159744, 159744, -2, 159744, -2, -2],
+    }
+    got = _reduced_conv_descriptor_codes(hip_lib)
+    for name, row in expected.items():
+        assert got[name] == row, (name, [(b, g, e) for (b, _), g, e in zip(_REDUCED_CONV_BREAKS, got[name], row) if g != e])
+    assert sorted(got) == sorted(expected) and len(expected) == 7
