@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 21
+#define MR_ABI_VERSION 22
 
 #define MR_COMPUTE_F32  0
 #define MR_COMPUTE_BF16 1
@@ -677,6 +677,29 @@ int mr_preprocess_image_u8_lut_f32(const uint8_t* src, int32_t src_h, int32_t sr
                                    const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
                                    const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize,
                                    int32_t max_tile_rows, const float* lut256, float* dst, void* stream);
+
+/* ---- pre-decoded frame store (monorec_amd/frame_store.py): what the three launches above produce, kept as bytes on disk ----
+ *
+ * Write side.  The launch of mr_preprocess_image_u8_f32 (kitti_odometry_dataset.py:120-134) stopped after the resize: the 8-bit
+ * value of the vertical pass, before table, division and grey replication, to `channels` planes of out_h x out_w bytes, plane p
+ * at dst + p * plane_stride (plane_stride >= out_h * out_w bytes, else MR_ERR_BAD_ARGUMENT). */
+int mr_preprocess_image_u8_u8(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels,
+                              int64_t row_stride_bytes, const int32_t* box, int32_t out_h, int32_t out_w,
+                              const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
+                              const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize,
+                              int32_t max_tile_rows, uint8_t* dst, int64_t plane_stride, void* stream);
+
+/* Read side.  The rest of preprocess_image on stored bytes (kitti_odometry_dataset.py:120-134; with a table
+ * tum_mono_vo_dataset.py:92-94): src = `channels` (1 or 3) planes of h x w bytes in device memory, 16-byte aligned, plane p at
+ * src + p * plane_stride; dst (3, h, w) fp32 = (lut256 ? lut256[u] : u) / 255 - .5, a 1-plane source written to all three planes.
+ * lut256: 256 floats in device memory or NULL.  plane_stride % 16 != 0 or plane_stride < h * w: MR_ERR_BAD_ARGUMENT. */
+int mr_unpack_frame_u8_f32(const uint8_t* src, int32_t channels, int64_t plane_stride, int32_t h, int32_t w,
+                           const float* lut256, float* dst, void* stream);
+
+/* A stored sparse target back on its grid: the keyframe_depth of kitti_odometry_dataset.py:226-246 (annotated lidar :184-211,
+ * D(V)SO :156-182) kept as its non-zero cells.  dst (cells floats) is zero-filled, then dst[index[i]] = value[i] for i < n;
+ * indices are unique, one >= cells is skipped; n == 0 is valid (index / value may then be NULL). */
+int mr_scatter_sparse_f32(const uint32_t* index, const float* value, int64_t n, float* dst, int64_t cells, void* stream);
 
 /* Sparse lidar ground truth, preprocess_depth_annotated_lidar (kitti_odometry_dataset.py:184-211): the 16-bit depth PNG
  * (depth * 256, 0 = no return) -> inverse depth 256 / value scattered to the nearest cell of the (out_h, out_w) grid of

@@ -27,6 +27,7 @@ struct PreArgs {
     int max_rows;                            // LDS rows per tile
     const float* lut;                        // 256-entry response table (LUT kernel only)
     float* dst;
+    unsigned char* dst8; long long plane8;   // planar 8-bit destination and its plane stride in bytes (U8 kernel only)
 };
 
 __device__ __forceinline__ unsigned char clip8(int acc) {
@@ -40,7 +41,9 @@ __device__ __forceinline__ unsigned char clip8(int acc) {
 // loads (bounds -> coefficients, pixels) a thread walks for its share of the tile; 16 waves per tile walk a quarter of what 4 did
 // (measured: 10.8 -> 6.9 us at 1024x1280 -> 480x640 grey; dword loads of the source rows, per lane or staged through the LDS, were
 // slower than these byte loads: DESIGN 4.8).
-template <bool LUT>
+// U8: the frame store's form (monorec_amd/frame_store.py) - the 8-bit value of the vertical pass goes to `channels` planes as it is, before
+// table, division and grey replication; mr_unpack_frame_u8_f32 applies those to the stored bytes with the expression below.
+template <bool LUT, bool U8 = false>
 __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(const PreArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     float* lut = reinterpret_cast<float*>(lds);
@@ -72,14 +75,16 @@ __global__ __launch_bounds__(PRE_THREADS) void preprocess_kernel(const PreArgs a
         if (oy >= a.out_h) continue;
         const int first = a.vb[2 * oy] - r_first, n = a.vb[2 * oy + 1];
         const int* k = a.vk + (long long)oy * a.vks;
+        const long long o = (long long)oy * a.out_w + ox0 + xx;
         float v[3];
         for (int c = 0; c < C; ++c) {
             int acc = 1 << (PRECISION_BITS - 1);
             for (int t = 0; t < n; ++t) acc += (int)tmp[((first + t) * PT_W + xx) * C + c] * k[t];
             const unsigned char u = clip8(acc);
-            v[c] = (LUT ? lut[u] : (float)u) / 255.0f - 0.5f;   // kitti_odometry_dataset.py:128, tum_mono_vo_dataset.py:93-94
+            if (U8) a.dst8[c * a.plane8 + o] = u;
+            else v[c] = (LUT ? lut[u] : (float)u) / 255.0f - 0.5f;   // kitti_odometry_dataset.py:128, tum_mono_vo_dataset.py:93-94
         }
-        const long long o = (long long)oy * a.out_w + ox0 + xx;
+        if (U8) continue;
         if (C == 1) { a.dst[o] = v[0]; a.dst[plane + o] = v[0]; a.dst[2 * plane + o] = v[0]; }     // :130
         else { a.dst[o] = v[0]; a.dst[plane + o] = v[1]; a.dst[2 * plane + o] = v[2]; }            // :132
     }
@@ -144,6 +149,60 @@ __global__ __launch_bounds__(256) void dso_write_kernel(const unsigned short* __
     }
 }
 
+// ---- frame store read path (monorec_amd/frame_store.py): stored 8-bit planes -> the float32 frame preprocess_kernel writes --------
+// Streaming: a lane takes 16 bytes of one plane with one load and writes them as four float4 stores (to the three planes for a grey
+// record); the last h*w % 16 bytes of each plane go through the scalar tail.  The plane starts of the source are 16-byte aligned
+// (the store pads every plane); those of the fp32 destination are only 4-byte aligned when h*w % 4 != 0, hence `f4u`.
+typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+
+template <bool LUT>
+__device__ __forceinline__ float unpack_value(const float* lut, unsigned int u) {
+    return (LUT ? lut[u] : (float)u) / 255.0f - 0.5f;           // the expression of preprocess_kernel
+}
+
+template <bool LUT>
+__global__ __launch_bounds__(256) void unpack_frame_kernel(const unsigned char* __restrict__ src, int channels, long long plane_stride,
+                                                           long long n, const float* __restrict__ lut256, float* __restrict__ dst) {
+    __shared__ float lut[256];
+    if (LUT) { lut[threadIdx.x] = lut256[threadIdx.x]; __syncthreads(); }
+    const int c = blockIdx.y;
+    const unsigned char* p = src + c * plane_stride;
+    float* out = dst + c * n;
+    const long long chunks = n / 16;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < chunks; i += gridDim.x * 256ll) {
+        const uint4 q = *reinterpret_cast<const uint4*>(p + 16 * i);
+        const unsigned int w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            f4u v;
+            v.x = unpack_value<LUT>(lut, w[j] & 255u);
+            v.y = unpack_value<LUT>(lut, (w[j] >> 8) & 255u);
+            v.z = unpack_value<LUT>(lut, (w[j] >> 16) & 255u);
+            v.w = unpack_value<LUT>(lut, w[j] >> 24);
+            f4u* o = reinterpret_cast<f4u*>(out + 16 * i + 4 * j);
+            *o = v;
+            if (channels == 1) { *reinterpret_cast<f4u*>(out + n + 16 * i + 4 * j) = v; *reinterpret_cast<f4u*>(out + 2 * n + 16 * i + 4 * j) = v; }
+        }
+    }
+    if (blockIdx.x == 0) {
+        const long long i = chunks * 16 + threadIdx.x;
+        if (threadIdx.x < 16 && i < n) {
+            const float v = unpack_value<LUT>(lut, p[i]);
+            out[i] = v;
+            if (channels == 1) { out[n + i] = v; out[2 * n + i] = v; }
+        }
+    }
+}
+
+// ---- frame store targets: the non-zero cells of a sparse target (index, value) back into the zero-filled grid ---------------------
+__global__ __launch_bounds__(256) void scatter_sparse_kernel(const unsigned int* __restrict__ index, const float* __restrict__ value,
+                                                             long long n, float* __restrict__ dst, long long cells) {
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll) {
+        const unsigned int o = index[i];
+        if ((long long)o < cells) dst[o] = value[i];
+    }
+}
+
 double triangle(double x) {
     if (x < 0.0) x = -x;
     return x < 1.0 ? 1.0 - x : 0.0;
@@ -194,20 +253,22 @@ namespace {
 int launch_preprocess(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels, int64_t row_stride_bytes,
                       const int32_t* box, int32_t out_h, int32_t out_w, const int32_t* hbounds, const int32_t* hcoeffs,
                       int32_t hksize, const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize, int32_t max_tile_rows,
-                      const float* lut256, bool with_lut, float* dst, void* stream) {
-    if (!src || !box || !hbounds || !hcoeffs || !vbounds || !vcoeffs || !dst || (with_lut && !lut256)) return MR_ERR_BAD_ARGUMENT;
+                      const float* lut256, bool with_lut, float* dst, void* stream, uint8_t* dst8 = nullptr, int64_t plane8 = 0) {
+    if (!src || !box || !hbounds || !hcoeffs || !vbounds || !vcoeffs || (!dst && !dst8) || (with_lut && !lut256)) return MR_ERR_BAD_ARGUMENT;
     if ((channels != 1 && channels != 3) || out_h < 1 || out_w < 1 || hksize < 1 || vksize < 1 || max_tile_rows < 1) return MR_ERR_BAD_ARGUMENT;
     if (box[0] < 0 || box[1] < 0 || box[2] > src_w || box[3] > src_h || box[2] <= box[0] || box[3] <= box[1]) return MR_ERR_BAD_ARGUMENT;
     if (row_stride_bytes < (int64_t)src_w * channels) return MR_ERR_BAD_ARGUMENT;
+    if (dst8 && plane8 < (int64_t)out_h * out_w) return MR_ERR_BAD_ARGUMENT;
     const size_t lds = (size_t)max_tile_rows * PT_W * channels + (with_lut ? 256 * sizeof(float) : 0);
     if (lds > 64 * 1024) return MR_ERR_LDS_BUDGET;
     PreArgs a;
     a.src = src; a.row_stride = row_stride_bytes; a.channels = channels; a.x0 = box[0]; a.y0 = box[1];
     a.out_h = out_h; a.out_w = out_w;
     a.hb = hbounds; a.hk = hcoeffs; a.hks = hksize; a.vb = vbounds; a.vk = vcoeffs; a.vks = vksize;
-    a.max_rows = max_tile_rows; a.lut = lut256; a.dst = dst;
+    a.max_rows = max_tile_rows; a.lut = lut256; a.dst = dst; a.dst8 = dst8; a.plane8 = plane8;
     dim3 grid((out_w + PT_W - 1) / PT_W, (out_h + PT_H - 1) / PT_H);
-    if (with_lut) hipLaunchKernelGGL(preprocess_kernel<true>, grid, dim3(PRE_THREADS), lds, (hipStream_t)stream, a);
+    if (dst8) hipLaunchKernelGGL((preprocess_kernel<false, true>), grid, dim3(PRE_THREADS), lds, (hipStream_t)stream, a);
+    else if (with_lut) hipLaunchKernelGGL(preprocess_kernel<true>, grid, dim3(PRE_THREADS), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(preprocess_kernel<false>, grid, dim3(PRE_THREADS), lds, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
@@ -230,6 +291,40 @@ extern "C" int mr_preprocess_image_u8_lut_f32(const uint8_t* src, int32_t src_h,
                                               int32_t max_tile_rows, const float* lut256, float* dst, void* stream) {
     return launch_preprocess(src, src_h, src_w, channels, row_stride_bytes, box, out_h, out_w, hbounds, hcoeffs, hksize,
                              vbounds, vcoeffs, vksize, max_tile_rows, lut256, true, dst, stream);
+}
+
+extern "C" int mr_preprocess_image_u8_u8(const uint8_t* src, int32_t src_h, int32_t src_w, int32_t channels,
+                                         int64_t row_stride_bytes, const int32_t* box, int32_t out_h, int32_t out_w,
+                                         const int32_t* hbounds, const int32_t* hcoeffs, int32_t hksize,
+                                         const int32_t* vbounds, const int32_t* vcoeffs, int32_t vksize,
+                                         int32_t max_tile_rows, uint8_t* dst, int64_t plane_stride, void* stream) {
+    if (!dst) return MR_ERR_BAD_ARGUMENT;
+    return launch_preprocess(src, src_h, src_w, channels, row_stride_bytes, box, out_h, out_w, hbounds, hcoeffs, hksize,
+                             vbounds, vcoeffs, vksize, max_tile_rows, nullptr, false, nullptr, stream, dst, plane_stride);
+}
+
+extern "C" int mr_unpack_frame_u8_f32(const uint8_t* src, int32_t channels, int64_t plane_stride, int32_t h, int32_t w,
+                                      const float* lut256, float* dst, void* stream) {
+    if (!src || !dst || (channels != 1 && channels != 3) || h < 1 || w < 1) return MR_ERR_BAD_ARGUMENT;
+    const long long n = (long long)h * w;
+    if (plane_stride % 16 != 0 || plane_stride < n) return MR_ERR_BAD_ARGUMENT;
+    const long long blocks = (n / 16 + 255) / 256;
+    const dim3 grid((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks)), (unsigned)channels);
+    if (lut256) hipLaunchKernelGGL(unpack_frame_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, src, channels, (long long)plane_stride, n, lut256, dst);
+    else hipLaunchKernelGGL(unpack_frame_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, src, channels, (long long)plane_stride, n, lut256, dst);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_scatter_sparse_f32(const uint32_t* index, const float* value, int64_t n, float* dst, int64_t cells, void* stream) {
+    if (!dst || cells < 1 || n < 0 || (n > 0 && (!index || !value))) return MR_ERR_BAD_ARGUMENT;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(dst, 0, (size_t)cells * sizeof(float), st);
+    if (e != hipSuccess) return (int)e;
+    if (n == 0) return 0;
+    const long long blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(scatter_sparse_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, st, index, value, (long long)n, dst,
+                       (long long)cells);
+    return (int)hipGetLastError();
 }
 
 extern "C" int mr_lidar_inverse_depth_u16_f32(const uint16_t* depth_png, int32_t src_h, int32_t src_w, const int32_t* box,

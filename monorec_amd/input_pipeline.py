@@ -9,7 +9,8 @@ The reference decodes and resizes every image three times with `frame_count = 2`
 source frame of its neighbours); `FrameCache` keeps the preprocessed frames of the last few indices in HBM, so a
 sequential sweep decodes each PNG once and runs one resize launch per *new* frame.  PNG decoding stays on the host
 (PIL, as in the reference; `FrameCache(workers=N)` decodes ahead on N threads); everything after it runs on the device, bit-identical to Pillow's integer resampling.
-There is no CPU fallback for the resize."""
+There is no CPU fallback for the resize.  With a pre-decoded store (monorec_amd.frame_store) the decode and the resize are skipped:
+`FrameCache(store=)` uploads the stored 8-bit frame and runs one unpack launch."""
 import ctypes
 from collections import OrderedDict
 from concurrent.futures import ThreadPoolExecutor
@@ -95,11 +96,32 @@ class ImagePreprocessor:
             if table.numel() != 256:
                 raise ValueError("lut: expected 256 values (one per 8-bit intensity)")
             self.lut = table.contiguous().to(self.device)
-        self._staging = {}          # channels -> ring of (pinned host buffer, device buffer, copy-done event)
+        self._ring = None           # four (pinned host bytes, device bytes, copy-done event) slots, shared by images and store records
         self._ring_pos = 0
 
-    def __call__(self, image, out=None):
-        """image: uint8 (H, W, 3) or (H, W), numpy / CPU tensor (uploaded) or device tensor -> float32 (3, h, w) on the device."""
+    def _slot(self, nbytes):
+        """Next slot of the staging ring with room for `nbytes`, free for reuse: the upload that last used it has finished.  The ring is
+        allocated at the first use and again only when a larger item arrives (decoded images and store records share it)."""
+        if self._ring is None or self._ring[0][0].numel() < nbytes:
+            for _, _, ev in self._ring or ():
+                ev.synchronize()
+            self._ring = [(torch.empty(nbytes, dtype=torch.uint8).pin_memory(), torch.empty(nbytes, dtype=torch.uint8, device=self.device),
+                           torch.cuda.Event()) for _ in range(4)]
+        slot = self._ring[self._ring_pos % len(self._ring)]
+        self._ring_pos += 1
+        slot[2].synchronize()
+        return slot
+
+    def _upload(self, array):
+        """Host uint8 array -> the same shape on the device through the pinned ring, asynchronous."""
+        host, devbuf, ev = self._slot(array.size)
+        host.numpy()[:array.size].reshape(array.shape)[...] = array
+        devbuf[:array.size].copy_(host[:array.size], non_blocking=True)
+        ev.record(torch.cuda.current_stream(self.device))
+        return devbuf[:array.size].view(array.shape)
+
+    def _source(self, image):
+        """uint8 (H, W[, 3]) numpy / CPU tensor / device tensor -> (contiguous device tensor, channels)."""
         if torch.is_tensor(image) and not image.is_cuda:
             image = image.numpy()
         if isinstance(image, np.ndarray):
@@ -113,25 +135,19 @@ class ImagePreprocessor:
         if (image.shape[0], image.shape[1]) != (self.orig_h, self.orig_w) or channels not in (1, 3):
             raise ValueError(f"image of shape {tuple(image.shape)} does not match this preprocessor ({self.orig_h}x{self.orig_w})")
         if isinstance(image, np.ndarray):
-            # host image: through a small ring of pinned staging buffers (allocated once), asynchronous upload
-            ring = self._staging.get(channels)
-            if ring is None:
-                shape = (self.orig_h, self.orig_w) if channels == 1 else (self.orig_h, self.orig_w, channels)
-                ring = [(torch.empty(shape, dtype=torch.uint8).pin_memory(), torch.empty(shape, dtype=torch.uint8, device=self.device),
-                         torch.cuda.Event()) for _ in range(4)]
-                self._staging[channels] = ring
-            host, devbuf, ev = ring[self._ring_pos % len(ring)]
-            self._ring_pos += 1
-            ev.synchronize()                                   # the upload that last used this slot has finished
-            host.numpy()[...] = image
-            devbuf.copy_(host, non_blocking=True)
-            ev.record(torch.cuda.current_stream(self.device))
-            image = devbuf
-        image = image.contiguous()
+            image = self._upload(image)             # host image: pinned staging ring (allocated once), asynchronous upload
+        return image.contiguous(), channels
+
+    def _resize_args(self, image, channels):
+        return (image.data_ptr(), self.orig_h, self.orig_w, channels, self.orig_w * channels, self._box_c, self.out_h, self.out_w,
+                self.hb.data_ptr(), self.hk.data_ptr(), self.hks, self.vb.data_ptr(), self.vk.data_ptr(), self.vks, self.max_rows)
+
+    def __call__(self, image, out=None):
+        """image: uint8 (H, W, 3) or (H, W), numpy / CPU tensor (uploaded) or device tensor -> float32 (3, h, w) on the device."""
+        image, channels = self._source(image)
         if out is None:
             out = torch.empty(3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
-        args = (image.data_ptr(), self.orig_h, self.orig_w, channels, self.orig_w * channels, self._box_c, self.out_h, self.out_w,
-                self.hb.data_ptr(), self.hk.data_ptr(), self.hks, self.vb.data_ptr(), self.vk.data_ptr(), self.vks, self.max_rows)
+        args = self._resize_args(image, channels)
         stream = torch.cuda.current_stream().cuda_stream
         if self.lut is None:
             _lib.check(self.lib.mr_preprocess_image_u8_f32(*args, out.data_ptr(), stream), "mr_preprocess_image_u8_f32")
@@ -139,6 +155,49 @@ class ImagePreprocessor:
             _lib.check(self.lib.mr_preprocess_image_u8_lut_f32(*args, self.lut.data_ptr(), out.data_ptr(), stream),
                        "mr_preprocess_image_u8_lut_f32")
         return out
+
+    @property
+    def plane_stride(self):
+        """Bytes between the planes of a frame-store record of this target size: h * w rounded up to 16."""
+        return (self.out_h * self.out_w + 15) // 16 * 16
+
+    def resize_u8(self, image, out=None):
+        """The crop and resize of `__call__` alone: uint8 (channels, plane_stride) on the device, plane c = the 8-bit result of channel
+        c in its first h * w bytes (the padding is zero) - the record of monorec_amd.frame_store, before table, division and grey stacking."""
+        image, channels = self._source(image)
+        if out is None:
+            out = torch.zeros(channels, self.plane_stride, dtype=torch.uint8, device=self.device)
+        _lib.check(self.lib.mr_preprocess_image_u8_u8(*self._resize_args(image, channels), out.data_ptr(), self.plane_stride,
+                                                      torch.cuda.current_stream().cuda_stream), "mr_preprocess_image_u8_u8")
+        return out
+
+    def unpack(self, record, out=None):
+        """Frame-store record, uint8 (channels, plane_stride) on the host (a view of the mapped file) or on the device -> what `__call__`
+        returned for the image it was packed from: one copy into the pinned ring, asynchronous upload, one launch (table included)."""
+        channels, stride = int(record.shape[0]), int(record.shape[1])
+        if isinstance(record, np.ndarray):
+            record = self._upload(record)
+        if out is None:
+            out = torch.empty(3, self.out_h, self.out_w, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.mr_unpack_frame_u8_f32(record.data_ptr(), channels, stride, self.out_h, self.out_w,
+                                                   None if self.lut is None else self.lut.data_ptr(), out.data_ptr(),
+                                                   torch.cuda.current_stream().cuda_stream), "mr_unpack_frame_u8_f32")
+        return out
+
+
+def scatter_sparse(index_value, count, cells, device="cuda:0"):
+    """Frame-store target record back on its grid: `index_value` = `count` uint32 cell indices followed by `count` float32 values (raw
+    bytes, numpy uint8) -> float32 (cells,) on the device, zero where the record has no cell."""
+    lib = _lib.load()
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("monorec_amd.input_pipeline: a HIP device is required - there is no CPU fallback")
+    out = torch.empty(cells, dtype=torch.float32, device=device)
+    raw = torch.from_numpy(np.array(index_value, dtype=np.uint8)).to(device) if count else None
+    base = raw.data_ptr() if count else None
+    _lib.check(lib.mr_scatter_sparse_f32(base, base + 4 * count if count else None, count, out.data_ptr(), cells,
+                                         torch.cuda.current_stream().cuda_stream), "mr_scatter_sparse_f32")
+    return out
 
 
 def lidar_inverse_depth(depth_png, crop_box, target_image_size, device="cuda:0"):
@@ -198,12 +257,17 @@ class FrameCache:
     reference's `num_workers` data-loader processes (configs/evaluate/eval_monorec.json:33): whenever frame i is asked
     for, the decodes of i+1 .. i+lookahead are started, so a sequential sweep finds its next image already decoded.
     Only `load` runs on the threads; the device launches stay on the caller's thread and stream.  `index_range = (lo, hi)`
-    bounds the read-ahead (hi exclusive)."""
+    bounds the read-ahead (hi exclusive).
 
-    def __init__(self, load, preprocessor, capacity=8, workers=0, lookahead=None, index_range=None):
-        self.load, self.pre, self.capacity = load, preprocessor, capacity
+    `store`: a `frame_store.FrameStoreReader` of this camera.  A frame it holds is never decoded: its record (the 8-bit result of the
+    crop and resize) goes from the mapped file through the preprocessor's pinned ring to one unpack launch; a frame it does not hold
+    is decoded and resized as without a store."""
+
+    def __init__(self, load, preprocessor, capacity=8, workers=0, lookahead=None, index_range=None, store=None):
+        self.load, self.pre, self.capacity, self.store = load, preprocessor, capacity, store
         self._frames = OrderedDict()
         self.decoded = 0                       # number of images decoded + resized so far
+        self.unpacked = 0                      # number of frames taken from the store
         self.workers = int(workers)
         self.lookahead = int(lookahead if lookahead is not None else 2 * self.workers)
         self.index_range = index_range
@@ -222,16 +286,23 @@ class FrameCache:
                 continue
             if self.index_range is not None and not (self.index_range[0] <= j < self.index_range[1]):
                 continue
+            if self.store is not None and self.store.has(j):
+                continue
             self._decoding[j] = self._pool.submit(self._decode_host, j)
 
     def frame(self, index):
         if index in self._frames:
             self._frames.move_to_end(index)
             return self._frames[index]
-        fut = self._decoding.pop(index, None)
-        img = fut.result() if fut is not None else self._decode_host(index)
-        t = self.pre(img)
-        self.decoded += 1
+        record = self.store.frame(index) if self.store is not None else None
+        if record is not None:
+            t = self.pre.unpack(record)
+            self.unpacked += 1
+        else:
+            fut = self._decoding.pop(index, None)
+            img = fut.result() if fut is not None else self._decode_host(index)
+            t = self.pre(img)
+            self.decoded += 1
         self._frames[index] = t
         while len(self._frames) > self.capacity:
             self._frames.popitem(last=False)

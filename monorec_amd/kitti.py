@@ -15,7 +15,9 @@ reference.  What differs is where the work happens:
   * images: PNG decode on host threads, ahead of the sweep (`input_pipeline.FrameCache`), then ONE device launch per *new*
     image (crop, Pillow-exact bilinear resize, /255 - .5, CHW).  The reference decodes and resizes every image
     1 + frame_count times; here consecutive samples share the preprocessed frames in HBM;
-  * targets: annotated lidar (`:184-211`) and D(V)SO depth (`:156-182`) PNGs are scattered on the device.
+  * targets: annotated lidar (`:184-211`) and D(V)SO depth (`:156-182`) PNGs are scattered on the device;
+  * `frame_store=DIR` (monorec_amd.frame_store, written once by `python -m monorec_amd.frame_store pack`): the resized 8-bit frames and
+    the non-zero cells of the targets come from a packed store - no PNG decode, one small launch each, the same bits.
 
 Not provided (raise NotImplementedError): colour augmentation (training), dense `.npy` / non-annotated `.npz` depth folders.
 There is no CPU fallback: the first `__getitem__` needs a HIP device."""
@@ -83,7 +85,7 @@ class KittiOdometryDataset:
     def __init__(self, dataset_dir, frame_count=2, sequences=None, depth_folder="image_depth", target_image_size=(256, 512),
                  max_length=None, dilation=1, offset_d=0, use_color=True, use_dso_poses=False, use_color_augmentation=False,
                  lidar_depth=False, dso_depth=True, annotated_lidar=True, return_stereo=False, return_mvobj_mask=False,
-                 use_index_mask=(), device="cuda:0", decode_workers=8, cache_frames=None):
+                 use_index_mask=(), device="cuda:0", decode_workers=8, cache_frames=None, frame_store=None):
         if use_color_augmentation:
             raise NotImplementedError("monorec_amd.kitti: colour augmentation is a training feature (out of scope)")
         if not (lidar_depth or dso_depth):
@@ -144,6 +146,10 @@ class KittiOdometryDataset:
         self._decode_workers = int(decode_workers)
         self._cache_frames = int(cache_frames) if cache_frames is not None else 2 * (frame_count * dilation + 2)
         self._caches = {}                # (dataset index, camera) -> FrameCache
+        # pre-decoded store (monorec_amd.frame_store): a directory, kept as a plain string (evaluate.py dumps the public attributes);
+        # its files are opened on first use, per (sequence, camera), and checked against the geometry above
+        self.frame_store = None if frame_store is None else str(frame_store)
+        self._target_stores = {}         # dataset index -> FrameStoreReader
 
     # ------------------------------------------------------------------ bookkeeping like the reference
     def __len__(self):
@@ -167,6 +173,49 @@ class KittiOdometryDataset:
         fc, dl = self.frame_count, self.dilation
         return [i for i in range(-(fc // 2) * dl, ((fc + 1) // 2) * dl + 1, dl) if i != 0]
 
+    def _sample_keys(self, index):
+        """Sample index -> (dataset index, keyframe number, source frame numbers) (:212-224,248-255)."""
+        dataset_index, index = self.get_dataset_index(index)
+        if dataset_index is None:
+            raise IndexError()
+        if self.use_index_mask is not None:
+            index = self._indices[dataset_index][index] - self._offset
+        key = index + self._offset
+        return dataset_index, key, [key + i + self.offset_d for i in self._neighbour_offsets()]
+
+    # ------------------------------------------------------------------ pre-decoded store (monorec_amd.frame_store)
+    def _frame_header(self, dataset_index, cam):
+        from . import frame_store
+        from PIL import Image
+        files = self._datasets[dataset_index].cam_files[cam]
+        with Image.open(files[0]) as img:
+            channels = 1 if img.mode in ("L", "P", "1", "I", "I;16", "F") else 3
+        return frame_store.frame_header("KittiOdometryDataset", self.sequences[dataset_index], cam, self._orig_sizes[dataset_index],
+                                        self._crop_boxes[dataset_index], self.target_image_size, channels, len(files))
+
+    def _target_header(self, dataset_index):
+        from . import frame_store
+        return frame_store.target_header("KittiOdometryDataset", self.sequences[dataset_index], self._cam, self._orig_sizes[dataset_index],
+                                         self._crop_boxes[dataset_index], self.target_image_size,
+                                         len(self._datasets[dataset_index].cam_files[self._cam]), self.depth_folder, self.lidar_depth,
+                                         self.annotated_lidar, self.dso_depth,
+                                         self.dso_depth_parameters[dataset_index] if self.dso_depth else None)
+
+    def _store_reach(self, indices):
+        """What the samples `indices` read: ({(dataset index, camera): frame numbers}, {dataset index: target frame numbers}), with an
+        entry for every stream of the dataset."""
+        cams = [self._cam] + ([self._cam + 1] if self.return_stereo else [])
+        frames = {(d, c): set() for d in range(len(self._datasets)) for c in cams}
+        targets = {d: set() for d in range(len(self._datasets))} if self.return_mvobj_mask != 2 else {}
+        for i in indices:
+            d, key, sources = self._sample_keys(i)
+            frames[(d, self._cam)].update([key] + sources)
+            if self.return_stereo:
+                frames[(d, self._cam + 1)].add(key)
+            if d in targets:
+                targets[d].add(key)
+        return frames, targets
+
     # ------------------------------------------------------------------ device side
     def _cache(self, dataset_index, cam):
         key = (dataset_index, cam)
@@ -174,6 +223,10 @@ class KittiOdometryDataset:
         if cache is None:
             from PIL import Image
             files = self._datasets[dataset_index].cam_files[cam]
+            store = None
+            if self.frame_store is not None:
+                from . import frame_store
+                store = frame_store.open_frames(self.frame_store, self._frame_header(dataset_index, cam))
 
             def load(i, files=files):
                 with Image.open(files[i]) as img:
@@ -181,7 +234,7 @@ class KittiOdometryDataset:
             pre = input_pipeline.ImagePreprocessor(self._orig_sizes[dataset_index], self.target_image_size,
                                                    crop_box=self._crop_boxes[dataset_index], device=self._device)
             cache = input_pipeline.FrameCache(load, pre, capacity=self._cache_frames, workers=self._decode_workers,
-                                              index_range=(0, len(files)))
+                                              index_range=(0, len(files)), store=store)
             self._caches[key] = cache
         return cache
 
@@ -197,6 +250,14 @@ class KittiOdometryDataset:
     def _target(self, dataset_index, frame):
         """keyframe_depth of `__getitem__` (:226-246) for the sparse targets."""
         box, size = self._crop_boxes[dataset_index], self.target_image_size
+        if self.frame_store is not None:                    # stored as its non-zero cells: no PNG decode, one scatter launch
+            from . import frame_store
+            store = self._target_stores.get(dataset_index)
+            if store is None:
+                store = self._target_stores[dataset_index] = frame_store.open_targets(self.frame_store, self._target_header(dataset_index))
+            record = store.target(frame)
+            if record is not None:
+                return input_pipeline.scatter_sparse(record[1], record[0], size[0] * size[1], device=self._device).view(1, *size)
         png = self._read_depth_png(dataset_index, frame)
         if self.lidar_depth:
             depth = input_pipeline.lidar_inverse_depth(png, box, size, device=self._device)
@@ -208,20 +269,14 @@ class KittiOdometryDataset:
         return depth.unsqueeze(0)
 
     def __getitem__(self, index):
-        dataset_index, index = self.get_dataset_index(index)
-        if dataset_index is None:
-            raise IndexError()
-        if self.use_index_mask is not None:
-            index = self._indices[dataset_index][index] - self._offset
+        dataset_index, key, sources = self._sample_keys(index)
         seq = self._datasets[dataset_index]
-        key = index + self._offset
         # The 4x4 pose / intrinsics matrices stay on the HOST: MonoRecModel forms its projection matrices with the reference's CPU
         # operators (model.host_geometry) - matrices handed over on the device would have to come back first, and submit() would wait
         # for that copy behind everything queued on the caller's stream.  (A loop that moves them to the device anyway - the
         # reference's `to(data, device)`, evaluater.py:82 - still works; monorec_amd.evaluate.Evaluater leaves them where they are.)
         k = self._intrinsics[dataset_index]
         cache = self._cache(dataset_index, self._cam)
-        sources = [key + i + self.offset_d for i in self._neighbour_offsets()]
         pose = lambda j: torch.tensor(seq.poses[j], dtype=torch.float32)
         data = {
             "keyframe": cache.frame(key),
@@ -249,6 +304,7 @@ class KittiOdometryDataset:
         for cache in self._caches.values():
             cache.close()
         self._caches = {}
+        self._target_stores = {}
 
 
 def collate(samples):

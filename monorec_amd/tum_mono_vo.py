@@ -16,7 +16,9 @@ reference.  A sequence folder holds
     the host, in the reference's float64 expressions; the quaternion -> matrix step is written out (scipy is not a dependency);
   * images: decode on host threads ahead of the sweep (`input_pipeline.FrameCache`), then ONE device launch per *new* image
     (crop, Pillow-exact bilinear resize, inverse response table, /255 - .5, CHW).  The reference decodes, resizes and maps
-    every image 1 + frame_count times; here consecutive samples share the preprocessed frames in HBM.
+    every image 1 + frame_count times; here consecutive samples share the preprocessed frames in HBM;
+  * `frame_store=DIR` (monorec_amd.frame_store): the resized 8-bit frames come from a packed store instead of the image files - no
+    decode, one unpack launch that applies the response table, the same bits.
 
 Not provided (raise NotImplementedError): colour augmentation (training), `only_keyframes` and EXR depth maps (both need
 `images_depth/*.exr`, read through OpenCV; "WIP" in the reference).  There is no CPU fallback: the first `__getitem__` needs a
@@ -88,7 +90,7 @@ class TUMMonoVODataset:
     """Drop-in for `data_loader.tum_mono_vo_dataset.TUMMonoVODataset` with device-resident samples."""
 
     def __init__(self, dataset_dir, frame_count=2, target_image_size=(480, 640), max_length=None, dilation=1, only_keyframes=False,
-                 color_augmentation=True, scale_factor=1, device="cuda:0", decode_workers=8, cache_frames=None):
+                 color_augmentation=True, scale_factor=1, device="cuda:0", decode_workers=8, cache_frames=None, frame_store=None):
         if color_augmentation:
             raise NotImplementedError("monorec_amd.tum_mono_vo: colour augmentation is a training feature - pass "
                                       "color_augmentation=False, as configs/test/pointcloud_monorec_tmvo.json does")
@@ -119,6 +121,7 @@ class TUMMonoVODataset:
         from PIL import Image
         with Image.open(path("images", "00000.jpg")) as img:
             self._orig_size = (img.size[1], img.size[0])
+            self._channels = 1 if img.mode == "L" else 3
         p_cam = load_orig_intrinsics(path("camera.txt"))
         p_cam[0, 0] *= self._orig_size[1]
         p_cam[1, 1] *= self._orig_size[0]
@@ -138,6 +141,11 @@ class TUMMonoVODataset:
         self._cache_frames = int(cache_frames) if cache_frames is not None else 2 * ((frame_count + 1) * dilation + 1)
         self._frames = None              # FrameCache, keyed by the row of result.txt
         self._depth = None               # the constant (1, H, W) zero target (:79,129-130)
+        # pre-decoded store (monorec_amd.frame_store): a directory, kept as a plain string (the scripts dump the public attributes); the
+        # file of this sequence is opened on first use and checked against the geometry above.  It holds the bytes BEFORE the response
+        # table, which is applied at unpack.
+        self.frame_store = None if frame_store is None else str(frame_store)
+        self._store_key = os.path.basename(os.path.normpath(self.dataset_dir))
 
     def __len__(self):
         return self.length
@@ -147,11 +155,33 @@ class TUMMonoVODataset:
         class's own order, not KITTI's symmetric one."""
         return [index + i for i in range(0, (self.frame_count + 1) * self.dilation, self.dilation) if i != self._offset]
 
+    # ------------------------------------------------------------------ pre-decoded store (monorec_amd.frame_store)
+    def _frame_header(self, stream=0, cam=0):
+        from . import frame_store
+        return frame_store.frame_header("TUMMonoVODataset", self._store_key, 0, self._orig_size, self._crop_box, self.target_image_size,
+                                        self._channels, len(self._image_index))
+
+    def _store_reach(self, indices):
+        """What the samples `indices` read: ({(0, 0): rows of result.txt}, {}) - the target is the constant zero map."""
+        rows = set()
+        for i in indices:
+            if not 0 <= i < self.length:
+                raise IndexError()
+            rows.update([i + self._offset] + self._source_rows(i))
+        return {(0, 0): rows}, {}
+
+    def _cache(self, stream=0, cam=0):
+        return self.cache
+
     # ------------------------------------------------------------------ device side
     @property
     def cache(self):
         if self._frames is None:
             from PIL import Image
+            store = None
+            if self.frame_store is not None:
+                from . import frame_store
+                store = frame_store.open_frames(self.frame_store, self._frame_header())
             folder, image_index = os.path.join(self.dataset_dir, "images"), self._image_index
 
             def load(row):
@@ -162,7 +192,7 @@ class TUMMonoVODataset:
             pre = input_pipeline.ImagePreprocessor(self._orig_size, self.target_image_size, crop_box=self._crop_box,
                                                    device=self._device, lut=self._pcalib)
             self._frames = input_pipeline.FrameCache(load, pre, capacity=self._cache_frames, workers=self._decode_workers,
-                                                     index_range=(0, len(image_index)))
+                                                     index_range=(0, len(image_index)), store=store)
             self._depth = torch.zeros((1, *self.target_image_size), dtype=torch.float32, device=self._device)
         return self._frames
 

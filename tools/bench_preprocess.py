@@ -1,8 +1,11 @@
 """Times the per-frame image preprocessing (csrc/preprocess.hip) at a user's sizes, on the GPU:
 
   * the launch alone (device-resident source, device events over many launches): mr_preprocess_image_u8_f32 and
-    mr_preprocess_image_u8_lut_f32;
+    mr_preprocess_image_u8_lut_f32, and the two launches of the pre-decoded frame store (monorec_amd.frame_store) beside them, to be
+    compared with the f32 resize launch of the same session: mr_preprocess_image_u8_u8 (the packer's resize) and
+    mr_unpack_frame_u8_f32 (stored bytes -> frame, with and without the table);
   * a frame end to end on the device path: decoded uint8 image on the host -> pinned staging -> upload -> launch (host clock, synchronised);
+  * a stored frame end to end: record on the host -> pinned staging -> upload -> unpack launch (host clock, synchronised);
   * the reference-style host path for the same frame: Pillow convert / crop / resize, response table, /255 - .5, CHW on the CPU, then
     the upload of the float32 result (host clock, synchronised) - what a TUM-MonoVO sample cost per frame before the device path.
 
@@ -68,6 +71,18 @@ def raw_launch(lib, pre, image, channels, out, with_lut=False):
     return lambda: fn(*args, out.data_ptr(), stream)
 
 
+def raw_store_launches(lib, pre, image, channels, out):
+    """The frame store's launches as raw C-ABI calls: (u8 resize of `image` into a record, unpack of that record, unpack with the table)."""
+    record = torch.zeros(channels, pre.plane_stride, dtype=torch.uint8, device=image.device)
+    stream = torch.cuda.current_stream().cuda_stream
+    resize_args = (image.data_ptr(), pre.orig_h, pre.orig_w, channels, pre.orig_w * channels, pre._box_c, pre.out_h, pre.out_w, pre.hb.data_ptr(),
+                   pre.hk.data_ptr(), pre.hks, pre.vb.data_ptr(), pre.vk.data_ptr(), pre.vks, pre.max_rows, record.data_ptr(), pre.plane_stride, stream)
+    unpack_args = lambda lut: (record.data_ptr(), channels, pre.plane_stride, pre.out_h, pre.out_w, lut, out.data_ptr(), stream)
+    plain_args, lut_args = unpack_args(None), unpack_args(pre.lut.data_ptr())
+    return (record, lambda: lib.mr_preprocess_image_u8_u8(*resize_args), lambda: lib.mr_unpack_frame_u8_f32(*plain_args),
+            lambda: lib.mr_unpack_frame_u8_f32(*lut_args))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--compare-lib", default=None)
@@ -110,6 +125,21 @@ def main():
         else:
             row["launch_us_this_tree"] = [round(1e3 * v, 3) for v in event_ms(this, a.launches)]
         row["launch_us_lut_entry"] = [round(1e3 * v, 3) for v in event_ms(this_lut, a.launches)]
+        # the frame store's launches on the same image: the record the packer writes, and its way back
+        record, resize_u8, unpack, unpack_lut = raw_store_launches(lut.lib, lut, dev_img, c, out)
+        for _ in range(50):
+            resize_u8(), unpack(), unpack_lut()
+        this()
+        want = out.clone()
+        resize_u8(), unpack()
+        torch.cuda.synchronize()
+        row["unpack_bit_equal_to_f32_resize"] = bool(torch.equal(out, want))
+        row["launch_us_u8_resize"] = [round(1e3 * v, 3) for v in event_ms(resize_u8, a.launches)]
+        row["launch_us_unpack"] = [round(1e3 * v, 3) for v in event_ms(unpack, a.launches)]
+        row["launch_us_unpack_lut"] = [round(1e3 * v, 3) for v in event_ms(unpack_lut, a.launches)]
+        row["record_bytes"] = int(record.numel())
+        host_record = record.cpu().numpy()
+        row["frame_ms_store_path_lut"] = [round(v, 4) for v in host_ms(lambda: lut.unpack(host_record, out=out), 200)]
         # a frame end to end, device path (host image -> pinned ring -> upload -> launch) against the host path
         row["frame_ms_device_path_lut"] = [round(v, 4) for v in host_ms(lambda: lut(img, out=out), 200)]
         pil = Image.fromarray(img)
