@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 22
+#define MR_ABI_VERSION 23
 
 #define MR_COMPUTE_F32  0
 #define MR_COMPUTE_BF16 1
@@ -38,7 +38,7 @@ extern "C" {
 #define MR_MAX_SOURCES 3
 #define MR_MAX_FRAMES  8
 #define MR_MAX_HEADS   4   /* one-channel 3x3 heads per mr_depth_heads_f32 launch (DepthModule has 4 predictors) */
-#define MR_MAX_VOTE_MASKS 8   /* masks voted over by mr_pointcloud_append_f32 (the reference buffers 5) */
+#define MR_MAX_VOTE_MASKS 8   /* masks voted over by mr_pointcloud_append_f32 / mr_tsdf_frame_f32 (the reference buffers 5) */
 
 /* ---- activation codes for mr_conv2d_f32 (epilogue, applied after bias [+ residual]) ---- */
 enum {
@@ -642,6 +642,23 @@ int mr_pointcloud_append_f32(const float* inv_depth, const float* const* static_
                              const float* uniform, float dropout, float min_d, float max_d, const int32_t* roi,
                              int32_t batch, int32_t height, int32_t width, float* records, int64_t capacity_records,
                              int64_t* cursor, void* stream);
+
+/* ---- TSDF-fusion export (ABI 23; monorec_amd/tsdf_export.py): utils/util.py:78-92, save_frame_for_tsdf, up to its Image.fromarray ----
+ *
+ * One launch for a batch of keyframes, optionally preceded by the mask vote of create_pointcloud.py:90-92 (as in
+ * mr_pointcloud_append_f32: vote = sum_k static_masks[k] > vote_above, inv_depth *= vote; num_masks = 0: no masking):
+ *   depth  = int16(trunc(fp32(fp32(1 / inv_depth) * 100)))  - the low half of the truncating 32-bit conversion, as torch on x86 -,
+ *            then 0 where negative (327.68 m and beyond wraps, |v| >= 2^31 and NaN give 0, so does inv_depth == 0),
+ *            then 0 where fp32(depth) < min_cm and where fp32(depth) > max_cm  (centimetres; -INFINITY / +INFINITY: no threshold,
+ *            NaN: MR_ERR_BAD_ARGUMENT)
+ *   colour = uint8(trunc(fp32(fp32(keyframe + .5) * 255))), pixel-interleaved r g b
+ * both restricted to crop = (y0, y1, x0, x1), the reference's order, 0 <= y0 < y1 <= height, 0 <= x0 < x1 <= width (NULL: whole image).
+ * inv_depth (batch,1,H,W), keyframe (batch,3,H,W) in [-.5, .5]; depth (batch, y1-y0, x1-x0) int16, 8-byte aligned; colour
+ * (batch, y1-y0, x1-x0, 3) bytes, 4-byte aligned.  Null pointers, sizes < 1, a crop outside the image or empty, num_masks >
+ * MR_MAX_VOTE_MASKS: MR_ERR_BAD_ARGUMENT, nothing is launched. */
+int mr_tsdf_frame_f32(const float* inv_depth, const float* keyframe, const float* const* static_masks, int32_t num_masks,
+                      float vote_above, const int32_t* crop, float min_cm, float max_cm, int32_t batch, int32_t height,
+                      int32_t width, int16_t* depth, uint8_t* colour, void* stream);
 
 /* ---- input pipeline: KittiOdometryDataset.preprocess_image, kitti_odometry_dataset.py:120-134 ------
  *

@@ -88,7 +88,7 @@ class B8ConvDesc(ctypes.Structure):
 
 
 MR_MAX_COPY_SEGMENTS = 24
-MR_ABI_VERSION = 22            # include/monorec_hip.h
+MR_ABI_VERSION = 23            # include/monorec_hip.h
 
 
 class CopySegment(ctypes.Structure):
@@ -238,6 +238,9 @@ ABI = {
                                                 ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                                 ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                 ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_frame_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+                                         ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mr_resample_ksize_bilinear": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "mr_resample_coeffs_bilinear": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_void_p]),

@@ -21,6 +21,7 @@ SOURCES = [
     # which cannot carry a DPP shift (measured on the ISA: +20 % VALU instructions, 170 instead of 123 VGPRs)
     ("cost_volume.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("pointcloud.hip", ["-ffp-contract=off"]),
+    ("tsdf_export.hip", ["-ffp-contract=off"]),        # depth / colour packing of save_frame_for_tsdf: the reference's roundings, one by one
     ("preprocess.hip", ["-ffp-contract=off"]),
     ("eltwise.hip", []),
     ("select.hip", ["-ffp-contract=off"]),          # median scaling: exact masked selection; stage-scaled metric sums

@@ -14,6 +14,8 @@ directory / sys.path must be the reference checkout) and rebinds exactly these n
     model.metric.<the seven dense-target metrics, a1_metric .. sq_rel_metric> -> monorec_amd.metrics.<same name>
     utils.median_scaling, utils.util.median_scaling                       -> monorec_amd.metrics.median_scaling
     utils.PLYSaver, utils.ply_utils.PLYSaver                              -> monorec_amd.pointcloud.PLYSaver
+    utils.save_frame_for_tsdf, utils.util.save_frame_for_tsdf             -> monorec_amd.tsdf_export.save_frame_for_tsdf
+    utils.save_intrinsics_for_tsdf, utils.util.save_intrinsics_for_tsdf   -> monorec_amd.tsdf_export.save_intrinsics_for_tsdf
 
 Nothing else of the reference is touched (data loaders, config parser, Evaluater stay the reference's own code) - unless asked:
 
@@ -63,6 +65,11 @@ def install(model=True, metrics=True, pointcloud=True, data_loader=False):
         from .pointcloud import PLYSaver
         _rebind("utils.ply_utils", "PLYSaver", PLYSaver)
         _rebind("utils", "PLYSaver", PLYSaver)
+        # the TSDF-fusion export of utils/util.py:78-98 (device tensors in, the reference's files out)
+        from . import tsdf_export
+        for name in ("save_frame_for_tsdf", "save_intrinsics_for_tsdf"):
+            _rebind("utils.util", name, getattr(tsdf_export, name))
+            _rebind("utils", name, getattr(tsdf_export, name))
     if data_loader:
         from .kitti import KittiOdometryDataloader
         if not _rebind("data_loader.data_loaders", "KittiOdometryDataloader", KittiOdometryDataloader):

@@ -410,3 +410,51 @@ TMVO_CASES = {
     # RGB source: three channels through the table
     "rgb": (dict(height=36, width=52, channels=3, images=7, dropped=(2,), seed=7), dict(frame_count=2, target_image_size=(24, 32))),
 }
+
+
+# case matrix of the TSDF-fusion export shared by tools/make_golden_tsdf.py (writes the reference's arrays) and the tests
+TSDF_SIZES = ((13, 21), (32, 48))                # odd with a tail of one pixel; multiples of four (the 16-byte load path)
+TSDF_SETS = ("a", "b")                           # two seeded input sets per size: the batch of two of the device test
+TSDF_CROPS = {(13, 21): {"full": None, "crop": (2, 11, 3, 20)},          # 9 x 17 from an odd origin
+              (32, 48): {"full": None, "crop": (4, 28, 8, 40)}}          # 24 x 32 from an origin that keeps the rows 16-byte aligned
+# name -> (min_distance, max_distance) in metres.  "frac": not whole centimetres.  "ulp": .07 * 100 = 7.000000000000001 and
+# .29 * 100 = 28.999999999999996 in double, 7 and 29 in fp32 - a depth of exactly 7 / 29 cm tells the two comparisons apart
+TSDF_THRESHOLDS = {"none": (None, None), "3_30": (3, 30), "frac": (3.005, 29.995), "ulp": (.07, .29)}
+TSDF_BOUNDARY_32767 = float(torch.tensor(1 / 327.67, dtype=torch.float32))
+TSDF_BOUNDARY_32768 = float(torch.tensor(1 / 327.68, dtype=torch.float32))
+
+
+def make_tsdf_case(size, which="a"):
+    """Seeded inputs of save_frame_for_tsdf (utils/util.py:78-92) for one keyframe: inverse depth (H, W) uniform in the model's
+    range [0.0025, 0.33] with every special class planted inside TSDF_CROPS[size]["crop"], a keyframe (3, H, W) = u / 255 - .5
+    holding all 256 byte values u (`source_bytes`), a rigid pose and pixel intrinsics (4 x 4).  `planted`: name -> (y, x)."""
+    h, w = size
+    gen = torch.Generator().manual_seed(1000 * h + w + (0 if which == "a" else 77))
+    inv_depth = 0.0025 + (0.33 - 0.0025) * torch.rand(h, w, generator=gen)
+    specials = [("zero", 0.0), ("boundary_32767", TSDF_BOUNDARY_32767), ("boundary_32768", TSDF_BOUNDARY_32768),
+                ("wrapped", 0.003), ("wrapped_far", 100 / 65535.5), ("twice_wrapped", 100 / 70000.0), ("two_metres", 0.5),
+                ("five_cm", 20.0), ("seven_cm", 100 / 7.5), ("twentynine_cm", 100 / 29.5), ("fifty_metres", 0.02),
+                ("negative", -0.1), ("minus_zero", -0.0), ("tiny", 1e-30), ("subnormal", 1e-41), ("nan", float("nan")),
+                ("inf", float("inf")), ("past_int32", 100 / 3.0e9), ("minus_tiny", -1e-30),
+                ("three_metres", 100 / 300.5), ("thirty_metres", 100 / 3000.5)]      # 300 cm / 3000 cm: where 3 / 30 and 3.005 / 29.995 differ
+    y0, y1, x0, x1 = TSDF_CROPS[size]["crop"]
+    cw = x1 - x0
+    planted = {}
+    for i, (name, value) in enumerate(specials):
+        y, x = y0 + 1 + (3 * i) // cw, x0 + (3 * i) % cw          # every third pixel of the crop's second row onward
+        inv_depth[y, x] = value
+        planted[name] = (y, x)
+    u = torch.randint(0, 256, (3 * h * w,), generator=gen, dtype=torch.int64)
+    u[:256] = torch.arange(256)
+    u = u[torch.randperm(u.numel(), generator=gen)].view(3, h, w).to(torch.uint8)
+    keyframe = (u.to(torch.float32) / 255 - .5).contiguous()
+    ang = 0.4 * (torch.rand(3, generator=gen) - 0.5)
+    cz, sz, cy, sy, cx, sx = torch.cos(ang[0]), torch.sin(ang[0]), torch.cos(ang[1]), torch.sin(ang[1]), torch.cos(ang[2]), torch.sin(ang[2])
+    rz = torch.tensor([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1.0]])
+    ry = torch.tensor([[cy, 0, sy], [0, 1.0, 0], [-sy, 0, cy]])
+    rx = torch.tensor([[1.0, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    pose = torch.eye(4)
+    pose[:3, :3] = rz @ ry @ rx
+    pose[:3, 3] = 60.0 * (torch.rand(3, generator=gen) - 0.5)
+    return dict(inv_depth=inv_depth.contiguous(), keyframe=keyframe, source_bytes=u.numpy(), pose=pose.contiguous(),
+                intrinsics=make_intrinsics(h, w, 1)[0].contiguous(), planted=planted)
