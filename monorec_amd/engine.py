@@ -597,6 +597,7 @@ class Plan:
         # opt-in of the bf16 configuration (MonoRecModel(hip_bf16=True, hip_lean_outputs=True)): no dense fp32 `single_frame_cvs` - the fusion
         # kernel writes the fused volume and the B8 copies the mask encoder reads, nothing else (403 MB of HBM writes less at configs[4])
         self.lean_outputs = bool(lean_outputs)
+        self._sfcv_b8_ptrs = None
         # opt-in (MonoRecModel(hip_skip_dead_layer4=True)): ResNet layer4 (monorec_model.py:118-129) is computed by the reference but read by nobody -
         # MaskModule / DepthModule consume image_features[0..3] only (:372-380, :545).  With the switch its 5 convolutions + 3 split-K
         # finishing launches are not issued and `image_features` has four entries.
@@ -746,6 +747,12 @@ class Plan:
         them (no_cv zero volumes, pretrain_mode 1 / 3 masks, mask-only mode) hand out copies of the resident buffers instead."""
         preds = getattr(self, "preds", None)
         return self.pretrain_mode == 0 and not self.no_cv and preds is not None and all(p is not None for p in preds)
+
+    @property
+    def lean_active(self):
+        """`lean_outputs` in effect: the fusion kernel that writes the B8 copies runs (mr_cost_volume_b8_lean_f32), so `sfcv` stays scratch and is
+        no output.  Where the plan falls back (a depth count without that kernel, an option variant) the volumes are finalised and handed out."""
+        return bool(self.lean_outputs and self.b8 and self._sfcv_b8_ptrs is not None)
 
     # ------------------------------------------------------------------ buffers / parameters
     def alloc(self, name, *shape):

@@ -1050,7 +1050,7 @@ class MonoRecModel(nn.Module):
             data_dict["mask"] = data_dict["cv_mask"]
             return _Pending(data_dict, done, device, None, owned=True, stream=main if inline else None)
         data_dict["cost_volume"] = plan.buf["cost_volume"]
-        if not (plan.lean_outputs and plan.b8):               # (lean: the buffer holds raw per-frame costs, not monorec_model.py:251's volumes)
+        if not plan.lean_active:                              # (lean: the buffer holds raw per-frame costs, not monorec_model.py:251's volumes)
             data_dict["single_frame_cvs"] = [plan.buf["sfcv"][f] for f in range(nf)]
         data_dict["image_features"] = list(plan.feats)
         data_dict["cv_mask"] = plan.buf["cv_mask"]
@@ -1075,7 +1075,7 @@ class MonoRecModel(nn.Module):
         if lay is None:
             lay = {"small": [], "big": [], "size": {"small": 256, "big": 0}}      # the first 256 bytes of the small arena: the constants
             for name in plan.bound:
-                if name == "sfcv" and plan.lean_outputs and plan.b8:
+                if name == "sfcv" and plan.lean_active:
                     continue                                  # scratch of the cost-volume kernels, not an output: stays in the resident buffer
                 t = plan.buf[name]
                 kind = "small" if (name == "cv_mask" or name.startswith("pred")) else "big"
