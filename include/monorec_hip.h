@@ -490,6 +490,37 @@ int mr_copy_segments(const mr_copy_segment* segments, int32_t num_segments, void
  * divisor), 0 when the launch must use IEEE division for this divisor.  Exposed so that tests can pin the verdicts. */
 int mr_exact_const_division(float divisor);
 
+/* Host query of the cost-volume launch decision: what the mr_cost_volume_* entry points launch for a set of arguments, filled by the very
+ * function the launchers consume (one copy of the rules).  It never touches the device.  The arguments are those of the entry points the
+ * decision depends on; pointers are taken as given (`has_pixel_depths`, `has_b8`: pixel_depths / sfcv_b8 non-null), `tiled` selects
+ * mr_cost_volume_tiled_f32, `relaxed` mr_cost_volume_relaxed_f32, `lean` mr_cost_volume_b8_lean_f32 (with has_b8).  Returns out->status:
+ * 0, or the MR_ERR_* code the entry point returns for these arguments (every other field is then 0); MR_ERR_BAD_ARGUMENT for out == NULL.
+ * Exposed so that tests can pin which kernel instantiation a shape runs (tests/cost_volume_paths.py). */
+enum { MR_CV_FAMILY_MARCH = 1, MR_CV_FAMILY_TILED = 2, MR_CV_FAMILY_PATCH = 3 };
+enum { MR_CV_FUSE_REG = 1, MR_CV_FUSE_GENERIC = 2 };
+typedef struct mr_cv_launch {
+    int32_t status;
+    int32_t family;                 /* MR_CV_FAMILY_*: cv_sad_march_kernel / cv_sad_kernel / cv_sad_patch_kernel */
+    int32_t mode, opt;              /* MODE = use_ssim; OPT bit 0 per-pixel depths, bit 1 per-plane flags (sfcv_mult_mask = 0) */
+    int32_t sad_grid[3], sad_block; /* grid and workgroup size of the sad kernel */
+    /* marching kernel (family MARCH; 0 otherwise): template arguments, geometry, and whether cv_kf_stats_kernel runs first */
+    int32_t dp, pixd, kfs, fd, relaxed;
+    int32_t strips, pitch, ty, ysegs, npairs;
+    int32_t kf_prepass, kf_grid[2];
+    /* tiled / patch kernels (0 for MARCH) */
+    int32_t tile_w, tile_h, tiles_x, tiles, nchunk, dchunk;
+    int32_t radius;                 /* patch_size / 2 */
+    int32_t lds_bytes;              /* per workgroup: static (tiled) or dynamic (patch) */
+    int32_t flag_memset;            /* 1: the cost-volume buffer is set to all ones (validity words) before the sad kernel */
+    /* fusion kernel */
+    int32_t fuse;                   /* MR_CV_FUSE_REG: cv_fuse_reg_kernel<fuse_depths, fuse_b8>; MR_CV_FUSE_GENERIC: cv_fuse_kernel<fuse_pflag> */
+    int32_t fuse_depths, fuse_b8, fuse_lean, fuse_pflag;
+    int32_t fuse_grid[2];
+} mr_cv_launch;
+int mr_cost_volume_launch_query(int32_t num_frames, int32_t batch, int32_t num_depths, int32_t height, int32_t width,
+                                int32_t use_ssim, int32_t has_pixel_depths, int32_t sfcv_mult_mask, int32_t patch_size,
+                                int32_t tiled, int32_t has_b8, int32_t relaxed, int32_t lean, mr_cv_launch* out);
+
 /* `num` (<= MR_MAX_GATHER) small fp32 tensors of `floats_each` elements each, anywhere in device memory, -> dst[num][floats_each],
  * one launch.  MonoRecModel uses it to bring the 4x4 pose / intrinsics matrices of a forward (monorec_model.py:160-171: they feed
  * torch.inverse / matmul, which this implementation runs with the reference's CPU operators) into device-writable pinned host memory. */

@@ -112,6 +112,23 @@ class HeadDesc(ctypes.Structure):
 
 MR_MAX_HEADS = 4
 
+CV_FAMILY_MARCH, CV_FAMILY_TILED, CV_FAMILY_PATCH = 1, 2, 3
+CV_FUSE_REG, CV_FUSE_GENERIC = 1, 2
+
+
+class CvLaunch(ctypes.Structure):
+    """mirror of `mr_cv_launch` (include/monorec_hip.h): what mr_cost_volume_launch_query reports."""
+    _fields_ = [("status", ctypes.c_int32), ("family", ctypes.c_int32), ("mode", ctypes.c_int32), ("opt", ctypes.c_int32),
+                ("sad_grid", ctypes.c_int32 * 3), ("sad_block", ctypes.c_int32),
+                ("dp", ctypes.c_int32), ("pixd", ctypes.c_int32), ("kfs", ctypes.c_int32), ("fd", ctypes.c_int32), ("relaxed", ctypes.c_int32),
+                ("strips", ctypes.c_int32), ("pitch", ctypes.c_int32), ("ty", ctypes.c_int32), ("ysegs", ctypes.c_int32), ("npairs", ctypes.c_int32),
+                ("kf_prepass", ctypes.c_int32), ("kf_grid", ctypes.c_int32 * 2),
+                ("tile_w", ctypes.c_int32), ("tile_h", ctypes.c_int32), ("tiles_x", ctypes.c_int32), ("tiles", ctypes.c_int32),
+                ("nchunk", ctypes.c_int32), ("dchunk", ctypes.c_int32), ("radius", ctypes.c_int32), ("lds_bytes", ctypes.c_int32),
+                ("flag_memset", ctypes.c_int32),
+                ("fuse", ctypes.c_int32), ("fuse_depths", ctypes.c_int32), ("fuse_b8", ctypes.c_int32), ("fuse_lean", ctypes.c_int32),
+                ("fuse_pflag", ctypes.c_int32), ("fuse_grid", ctypes.c_int32 * 2)]
+
 # every symbol include/monorec_hip.h declares: (restype, argtypes)
 ABI = {
     "mr_conv_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
@@ -172,6 +189,7 @@ ABI = {
                                          ctypes.c_int32, ctypes.c_void_p]),
     "mr_resnet_normalize_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
     "mr_exact_const_division": (ctypes.c_int, [ctypes.c_float]),
+    "mr_cost_volume_launch_query": (ctypes.c_int, [ctypes.c_int32] * 13 + [ctypes.POINTER(CvLaunch)]),
     "mr_run_launches": (ctypes.c_int, [ctypes.POINTER(LaunchItem), ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
     "mr_upconv_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
     "mr_upconv2x2_winograd_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_void_p]),

@@ -1193,18 +1193,42 @@ void launch_sad_opt(const CvArgs& k, int opt, dim3 grid, hipStream_t stream) {
     }
 }
 
-void launch_fuse(const CvArgs& k, bool plane_flags, bool tiled, hipStream_t stream) {
-    const long long total = (long long)k.B * k.H * k.W;
-    if (!plane_flags && !tiled && (k.D == 32 || k.D == 48 || k.D == 64)) {
-        const dim3 grid((unsigned)(((long long)k.H * k.W + 255) / 256), (unsigned)k.B);
-        const bool b8 = k.sfcv_b8[0] != nullptr;
+// ---- the launch decision: ONE host function (cv_decide) fills an mr_cv_launch, the launchers below consume it and decide nothing themselves;
+// mr_cost_volume_launch_query hands the same struct out (tests/cost_volume_paths.py restates the rules and compares field by field) ----------
+
+constexpr int CV_TX = 32, CV_TY = 16;      // tile of cv_sad_kernel
+constexpr int CVP_TX = 32, CVP_TY = 8;     // tile of cv_sad_patch_kernel (its TX / TY)
+// static LDS of cv_sad_kernel: keyframe tile + two warped planes (2 px halo), two SSIM planes (1 px halo)
+constexpr int CV_TILED_LDS = (int)sizeof(float) * (3 * (CV_TY + 4) * (CV_TX + 4) + 2 * 3 * (CV_TY + 4) * (CV_TX + 4) + 2 * (CV_TY + 2) * (CV_TX + 2));
+
+void decide_fuse(mr_cv_launch& L, int B, int D, int H, int W, bool plane_flags, bool tiled, bool b8, bool lean) {
+    const long long total = (long long)B * H * W;
+    if (!plane_flags && !tiled && (D == 32 || D == 48 || D == 64)) {
+        L.fuse = MR_CV_FUSE_REG;
+        L.fuse_depths = D;
+        L.fuse_b8 = b8 ? 1 : 0;
+        L.fuse_lean = (b8 && lean) ? 1 : 0;
+        L.fuse_grid[0] = (int)(((long long)H * W + 255) / 256);
+        L.fuse_grid[1] = B;
+        return;
+    }
+    L.fuse = MR_CV_FUSE_GENERIC;
+    L.fuse_pflag = plane_flags ? 1 : 0;
+    L.fuse_grid[0] = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    L.fuse_grid[1] = 1;
+}
+
+void launch_fuse(const CvArgs& k, const mr_cv_launch& L, hipStream_t stream) {
+    if (L.fuse == MR_CV_FUSE_REG) {
+        const dim3 grid((unsigned)L.fuse_grid[0], (unsigned)L.fuse_grid[1]);
+        const bool b8 = L.fuse_b8 != 0;
         if (k.D == 32) { if (b8) hipLaunchKernelGGL((cv_fuse_reg_kernel<32, true>), grid, dim3(256), 0, stream, k); else hipLaunchKernelGGL((cv_fuse_reg_kernel<32, false>), grid, dim3(256), 0, stream, k); }
         else if (k.D == 48) { if (b8) hipLaunchKernelGGL((cv_fuse_reg_kernel<48, true>), grid, dim3(256), 0, stream, k); else hipLaunchKernelGGL((cv_fuse_reg_kernel<48, false>), grid, dim3(256), 0, stream, k); }
         else { if (b8) hipLaunchKernelGGL((cv_fuse_reg_kernel<64, true>), grid, dim3(256), 0, stream, k); else hipLaunchKernelGGL((cv_fuse_reg_kernel<64, false>), grid, dim3(256), 0, stream, k); }
         return;
     }
-    const unsigned blocks = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (plane_flags) hipLaunchKernelGGL(cv_fuse_kernel<true>, dim3(blocks), dim3(256), 0, stream, k);
+    const unsigned blocks = (unsigned)L.fuse_grid[0];
+    if (L.fuse_pflag) hipLaunchKernelGGL(cv_fuse_kernel<true>, dim3(blocks), dim3(256), 0, stream, k);
     else hipLaunchKernelGGL(cv_fuse_kernel<false>, dim3(blocks), dim3(256), 0, stream, k);
 }
 
@@ -1213,11 +1237,11 @@ void launch_fuse(const CvArgs& k, bool plane_flags, bool tiled, hipStream_t stre
 // trades the 4 halo rows every segment warps twice against how evenly the waves divide over the chip's 1024 SIMDs
 // (c2: TY 32 -> 2304 waves = 3 rounds at 2.25 average; TY 37 -> 2016 waves = 2 full rounds).
 
-MarchGeom march_geometry(const CvArgs& a, int dp) {
+MarchGeom march_geometry(int F, int B, int D, int H, int W, int dp) {
     MarchGeom g;
-    g.strips = (a.W + 59) / 60;
-    g.pitch = (a.W + g.strips - 1) / g.strips;
-    g.npairs = (a.D + dp - 1) / dp;
+    g.strips = (W + 59) / 60;
+    g.pitch = (W + g.strips - 1) / g.strips;
+    g.npairs = (D + dp - 1) / dp;
 #ifdef MR_TUNING_ENV         // tuning aids: diagnostic library only (python -m monorec_amd.build --timeline); the product reads no environment
     static const int forced = [] { const char* e = getenv("MR_CV_MARCH_TY"); return e ? atoi(e) : 0; }();
 #else
@@ -1227,27 +1251,44 @@ MarchGeom march_geometry(const CvArgs& a, int dp) {
     if (forced >= 4) best_ty = forced;
     else {
         const double simds = 1024.0;
-        const long long per_seg = (long long)g.strips * a.F * a.B * g.npairs;
+        const long long per_seg = (long long)g.strips * F * B * g.npairs;
         double best = -1.0;
         for (int ty = 8; ty <= 64; ++ty) {
-            const int segs = (a.H + ty - 1) / ty;
+            const int segs = (H + ty - 1) / ty;
             const double waves = (double)per_seg * segs;
             const double rounds = waves / simds;
             const double balance = rounds >= 8.0 ? 1.0 : rounds / (double)(long long)(rounds + 0.999999);
-            const double rows = (double)a.H / ((double)segs * (ty + 4));      // useful rows / warped rows
+            const double rows = (double)H / ((double)segs * (ty + 4));      // useful rows / warped rows
             const double score = balance * rows;
             if (score > best + 1e-9) { best = score; best_ty = ty; }
         }
     }
     g.TY = best_ty;
-    g.ysegs = (a.H + best_ty - 1) / best_ty;
+    g.ysegs = (H + best_ty - 1) / best_ty;
     return g;
 }
 
-template <int TX, int TY>
-int launch_cv(const CvArgs& a, int mode, bool plane_flags, bool tiled, hipStream_t stream) {
-    CvArgs k = a;
-    if (mode == 1 && !plane_flags && !tiled) {
+// Everything the entry points decide from their scalar arguments: the refusals (in the order cost_volume_entry has always returned them;
+// `pointers_ok` stands for its null-pointer checks, which sit between them), the sad kernel and its template arguments, grids, the fusion kernel.
+int cv_decide(int F, int B, int D, int H, int W, int use_ssim, bool pixd, bool mult_mask, int patch_size, bool tiled, bool b8, bool relaxed,
+              bool lean, bool pointers_ok, mr_cv_launch& L) {
+    memset(&L, 0, sizeof(L));
+    auto refuse = [&L](int code) { memset(&L, 0, sizeof(L)); L.status = code; return code; };
+    if (use_ssim < 0 || use_ssim > 3) return refuse(MR_ERR_BAD_ARGUMENT);
+    if (patch_size < 1 || patch_size > 7 || !(patch_size & 1)) return refuse(MR_ERR_UNSUPPORTED);
+    if (!mult_mask && D < F) return refuse(MR_ERR_UNSUPPORTED);      // validity words live in planes 0..F-1
+    if (!pointers_ok) return refuse(MR_ERR_BAD_ARGUMENT);
+    if (F < 1 || F > MR_MAX_FRAMES || B < 1 || H < 5 || W < 5) return refuse(MR_ERR_BAD_ARGUMENT);
+    if (D < 2) return refuse(MR_ERR_BAD_ARGUMENT);                       // (:258 divides by num_depths - 1)
+    // the bf16 copy is written by the register-held fusion kernel of the default configuration only
+    if (b8 && !(patch_size == 3 && mult_mask && !tiled && (D == 32 || D == 48 || D == 64))) return refuse(MR_ERR_UNSUPPORTED);
+    const int border = patch_size / 2 + 1;                                                                   // :139
+    if (H < 2 * border + 1 || W < 2 * border + 1) return refuse(MR_ERR_BAD_ARGUMENT);
+    const bool plane_flags = !mult_mask;
+    const bool relaxed_sums = b8 || relaxed;
+    L.mode = use_ssim;
+    L.opt = (pixd ? 1 : 0) | (plane_flags ? 2 : 0);
+    if (patch_size == 3 && use_ssim == 1 && !plane_flags && !tiled) {
         // default configuration: LDS-free marching kernel, two depth planes per wave
         // One plane per wave instead of two when two would leave the 1024 SIMDs with fewer than 4 waves each (a wave issues one
         // VALU instruction per ~4.6 cycles on its own, a SIMD takes one per ~1.6 from 4 waves): c2 2016 -> 4032 waves, 143 -> 133 us;
@@ -1258,64 +1299,108 @@ int launch_cv(const CvArgs& a, int mode, bool plane_flags, bool tiled, hipStream
         const int dp_env = 0;
 #endif
         bool dp1 = false;
-        if (!a.pix_depths && a.D >= 6) {
-            const MarchGeom g2 = march_geometry(a, 2);
-            const long long waves2 = (long long)g2.strips * g2.ysegs * a.F * a.B * g2.npairs;
+        if (!pixd && D >= 6) {
+            const MarchGeom g2 = march_geometry(F, B, D, H, W, 2);
+            const long long waves2 = (long long)g2.strips * g2.ysegs * F * B * g2.npairs;
             dp1 = dp_env == 1 || (dp_env != 2 && waves2 < 4096);
         }
-        const MarchGeom g = march_geometry(a, dp1 ? 1 : 2);
-        const dim3 grid((unsigned)(g.strips * g.ysegs), (unsigned)(a.F * ((g.npairs + 3) / 4)), (unsigned)a.B);
+        const MarchGeom g = march_geometry(F, B, D, H, W, dp1 ? 1 : 2);
 #ifdef MR_TUNING_ENV
         static const bool no_prepass = getenv("MR_CV_NO_KF_PREPASS") != nullptr;           // A/B aid
 #else
         const bool no_prepass = false;
 #endif
-        const bool fd = a.fast_w && a.fast_h;  // both constant divisions by the exact 3-instruction sequence (checked on the host)
-        const bool kfs = dp1 || (a.D >= 6 && !no_prepass);
-        if (kfs)                             // keyframe window statistics once, into planes 0..5 of the cost-volume buffer
-            hipLaunchKernelGGL(cv_kf_stats_kernel, dim3((unsigned)((a.H * a.W + 255) / 256), (unsigned)a.B), dim3(256), 0, stream, k);
+        // both constant divisions by the exact 3-instruction sequence (checked on the host)
+        const bool fd = mr_exact_const_division((float)(W - 1)) && mr_exact_const_division((float)(H - 1));
+        const bool kfs = dp1 || (D >= 6 && !no_prepass);
+        L.family = MR_CV_FAMILY_MARCH;
+        L.dp = dp1 ? 1 : 2;
+        L.pixd = pixd ? 1 : 0;
+        L.kfs = kfs ? 1 : 0;
+        L.fd = fd ? 1 : 0;
+        L.relaxed = (relaxed_sums && fd && kfs && !pixd) ? 1 : 0;      // the bf16 configuration (mr_cost_volume_b8_f32): separable sums, see march_finish
+        L.strips = g.strips; L.pitch = g.pitch; L.ty = g.TY; L.ysegs = g.ysegs; L.npairs = g.npairs;
+        L.sad_grid[0] = g.strips * g.ysegs; L.sad_grid[1] = F * ((g.npairs + 3) / 4); L.sad_grid[2] = B;
+        L.sad_block = 256;
+        L.kf_prepass = kfs ? 1 : 0;          // keyframe window statistics once, into planes 0..5 of the cost-volume buffer
+        if (kfs) { L.kf_grid[0] = (H * W + 255) / 256; L.kf_grid[1] = B; }
+        decide_fuse(L, B, D, H, W, false, false, b8, lean);
+        return 0;
+    }
+    const bool patch = patch_size != 3;
+    L.family = patch ? MR_CV_FAMILY_PATCH : MR_CV_FAMILY_TILED;
+    L.tile_w = patch ? CVP_TX : CV_TX;
+    L.tile_h = patch ? CVP_TY : CV_TY;
+    L.tiles_x = (W + L.tile_w - 1) / L.tile_w;
+    L.tiles = L.tiles_x * ((H + L.tile_h - 1) / L.tile_h);
+    // depth chunks: enough workgroups to put >= 4 on every CU; the tiled kernel takes chunks of an even number of planes
+    const int even = patch ? 2 : 4;
+    int nchunk = 1;
+    while ((long long)L.tiles * F * B * nchunk < 1024 && (D / (nchunk * 2)) >= 4 && (D % (nchunk * even)) == 0) nchunk *= 2;
+    L.nchunk = nchunk;
+    L.dchunk = D / nchunk;
+    L.sad_grid[0] = L.tiles; L.sad_grid[1] = F * nchunk; L.sad_grid[2] = B;
+    L.sad_block = L.tile_w * L.tile_h;
+    L.radius = patch_size / 2;
+    if (patch) {
+        const int R = L.radius;
+        const int hx = CVP_TX + 2 * (R + 1), hy = CVP_TY + 2 * (R + 1), sx = CVP_TX + 2 * R, sy = CVP_TY + 2 * R;
+        L.lds_bytes = (int)(sizeof(float) * (size_t)(6 * hy * hx + 7 * sy * sx));
+    } else {
+        L.lds_bytes = CV_TILED_LDS;
+    }
+    L.flag_memset = plane_flags ? 1 : 0;     // validity words (plane f of every sample of the cost-volume buffer) start as all ones
+    decide_fuse(L, B, D, H, W, plane_flags, patch ? false : tiled, b8, lean);
+    return 0;
+}
+
+template <int TX, int TY>
+int launch_cv(const CvArgs& a, const mr_cv_launch& L, hipStream_t stream) {
+    CvArgs k = a;
+    if (L.family == MR_CV_FAMILY_MARCH) {
+        MarchGeom g;
+        g.strips = L.strips; g.pitch = L.pitch; g.TY = L.ty; g.ysegs = L.ysegs; g.npairs = L.npairs;
+        const dim3 grid((unsigned)L.sad_grid[0], (unsigned)L.sad_grid[1], (unsigned)L.sad_grid[2]);
+        const bool fd = L.fd != 0, kfs = L.kfs != 0, dp1 = L.dp == 1, pixd = L.pixd != 0;
+        if (L.kf_prepass)
+            hipLaunchKernelGGL(cv_kf_stats_kernel, dim3((unsigned)L.kf_grid[0], (unsigned)L.kf_grid[1]), dim3(256), 0, stream, k);
 #define MR_MARCH(DP_, PIXD_, KFS_)                                                                                              \
     do {                                                                                                                        \
         if (fd) hipLaunchKernelGGL((cv_sad_march_kernel<DP_, PIXD_, KFS_, true>), grid, dim3(256), 0, stream, k, g);          \
         else hipLaunchKernelGGL((cv_sad_march_kernel<DP_, PIXD_, KFS_, false>), grid, dim3(256), 0, stream, k, g);                 \
     } while (0)
-        if (a.relaxed_sums && fd && kfs && !a.pix_depths) {      // the bf16 configuration (mr_cost_volume_b8_f32): separable sums, see march_finish
+        if (L.relaxed) {
             if (dp1) hipLaunchKernelGGL((cv_sad_march_kernel<1, false, true, true, true>), grid, dim3(256), 0, stream, k, g);
             else hipLaunchKernelGGL((cv_sad_march_kernel<2, false, true, true, true>), grid, dim3(256), 0, stream, k, g);
         } else
         if (dp1) MR_MARCH(1, false, true);   // twice the waves, each with one plane: for shapes that leave the SIMDs short of waves
-        else if (kfs && a.pix_depths) MR_MARCH(2, true, true);
+        else if (kfs && pixd) MR_MARCH(2, true, true);
         else if (kfs) MR_MARCH(2, false, true);
-        else if (a.pix_depths) MR_MARCH(2, true, false);
+        else if (pixd) MR_MARCH(2, true, false);
         else MR_MARCH(2, false, false);
 #undef MR_MARCH
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
-        launch_fuse(k, false, false, stream);
+        launch_fuse(k, L, stream);
         return (int)hipGetLastError();
     }
-    k.tiles_x = (a.W + TX - 1) / TX;
-    const int tiles = k.tiles_x * ((a.H + TY - 1) / TY);
-    // depth chunks: enough workgroups to put >= 4 on every CU, chunks of an even number of planes
-    int nchunk = 1;
-    while ((long long)tiles * a.F * a.B * nchunk < 1024 && (a.D / (nchunk * 2)) >= 4 && (a.D % (nchunk * 4)) == 0) nchunk *= 2;
-    k.nchunk = nchunk;
-    k.dchunk = a.D / nchunk;
-    const dim3 grid(tiles, a.F * nchunk, a.B);
-    const int opt = (a.pix_depths ? 1 : 0) | (plane_flags ? 2 : 0);
-    if (plane_flags) {     // validity words (plane f of every sample of the cost-volume buffer) start as all ones
+    k.tiles_x = L.tiles_x;
+    k.nchunk = L.nchunk;
+    k.dchunk = L.dchunk;
+    const dim3 grid((unsigned)L.sad_grid[0], (unsigned)L.sad_grid[1], (unsigned)L.sad_grid[2]);
+    if (L.flag_memset) {
         hipError_t e = hipMemsetAsync(a.cv, 0xff, (size_t)a.B * a.D * a.H * a.W * sizeof(float), stream);
         if (e != hipSuccess) return (int)e;
     }
-    switch (mode) {
-        case 0: launch_sad_opt<TX, TY, 0>(k, opt, grid, stream); break;
-        case 2: launch_sad_opt<TX, TY, 2>(k, opt, grid, stream); break;
-        case 3: launch_sad_opt<TX, TY, 3>(k, opt, grid, stream); break;
-        default: launch_sad_opt<TX, TY, 1>(k, opt, grid, stream); break;
+    switch (L.mode) {
+        case 0: launch_sad_opt<TX, TY, 0>(k, L.opt, grid, stream); break;
+        case 2: launch_sad_opt<TX, TY, 2>(k, L.opt, grid, stream); break;
+        case 3: launch_sad_opt<TX, TY, 3>(k, L.opt, grid, stream); break;
+        default: launch_sad_opt<TX, TY, 1>(k, L.opt, grid, stream); break;
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    launch_fuse(k, plane_flags, tiled, stream);
+    launch_fuse(k, L, stream);
     return (int)hipGetLastError();
 }
 
@@ -1329,32 +1414,27 @@ void launch_sad_patch(const CvArgs& k, int opt, int R, dim3 grid, size_t lds, hi
     }
 }
 
-int launch_cv_patch(const CvArgs& a, int mode, bool plane_flags, int R, hipStream_t stream) {
-    constexpr int TX = 32, TY = 8;
+int launch_cv_patch(const CvArgs& a, const mr_cv_launch& L, hipStream_t stream) {
     CvArgs k = a;
-    k.tiles_x = (a.W + TX - 1) / TX;
-    const int tiles = k.tiles_x * ((a.H + TY - 1) / TY);
-    int nchunk = 1;
-    while ((long long)tiles * a.F * a.B * nchunk < 1024 && (a.D / (nchunk * 2)) >= 4 && (a.D % (nchunk * 2)) == 0) nchunk *= 2;
-    k.nchunk = nchunk;
-    k.dchunk = a.D / nchunk;
-    const dim3 grid(tiles, a.F * nchunk, a.B);
-    const int opt = (a.pix_depths ? 1 : 0) | (plane_flags ? 2 : 0);
-    const int hx = TX + 2 * (R + 1), hy = TY + 2 * (R + 1), sx = TX + 2 * R, sy = TY + 2 * R;
-    const size_t lds = sizeof(float) * (size_t)(6 * hy * hx + 7 * sy * sx);
-    if (plane_flags) {
+    k.tiles_x = L.tiles_x;
+    k.nchunk = L.nchunk;
+    k.dchunk = L.dchunk;
+    const dim3 grid((unsigned)L.sad_grid[0], (unsigned)L.sad_grid[1], (unsigned)L.sad_grid[2]);
+    const size_t lds = (size_t)L.lds_bytes;
+    const int R = L.radius;
+    if (L.flag_memset) {
         hipError_t e = hipMemsetAsync(a.cv, 0xff, (size_t)a.B * a.D * a.H * a.W * sizeof(float), stream);
         if (e != hipSuccess) return (int)e;
     }
-    switch (mode) {
-        case 0: launch_sad_patch<0>(k, opt, R, grid, lds, stream); break;
-        case 2: launch_sad_patch<2>(k, opt, R, grid, lds, stream); break;
-        case 3: launch_sad_patch<3>(k, opt, R, grid, lds, stream); break;
-        default: launch_sad_patch<1>(k, opt, R, grid, lds, stream); break;
+    switch (L.mode) {
+        case 0: launch_sad_patch<0>(k, L.opt, R, grid, lds, stream); break;
+        case 2: launch_sad_patch<2>(k, L.opt, R, grid, lds, stream); break;
+        case 3: launch_sad_patch<3>(k, L.opt, R, grid, lds, stream); break;
+        default: launch_sad_patch<1>(k, L.opt, R, grid, lds, stream); break;
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    launch_fuse(k, plane_flags, false, stream);
+    launch_fuse(k, L, stream);
     return (int)hipGetLastError();
 }
 
@@ -1364,23 +1444,20 @@ int cost_volume_entry(const float* keyframe, const float* const* frames, int32_t
                       float alpha, const float* channel_weights, int32_t use_ssim,
                       const float* pixel_depths, int32_t sfcv_mult_mask, int32_t patch_size, bool tiled,
                       float* cost_volume, float* const* sfcv, void* stream, void* const* sfcv_b8 = nullptr, bool relaxed = false, bool lean = false) {
-    if (use_ssim < 0 || use_ssim > 3) return MR_ERR_BAD_ARGUMENT;
-    if (patch_size < 1 || patch_size > 7 || !(patch_size & 1)) return MR_ERR_UNSUPPORTED;
-    if (!sfcv_mult_mask && num_depths < num_frames) return MR_ERR_UNSUPPORTED;      // validity words live in planes 0..F-1
-    if (!keyframe || !frames || !kinv || !proj || (!depths && !pixel_depths) || !cost_volume || !sfcv || !channel_weights)
-        return MR_ERR_BAD_ARGUMENT;
-    if (num_frames < 1 || num_frames > MR_MAX_FRAMES || batch < 1 || height < 5 || width < 5) return MR_ERR_BAD_ARGUMENT;
-    if (num_depths < 2) return MR_ERR_BAD_ARGUMENT;                       // (:258 divides by num_depths - 1)
+    bool pointers_ok = keyframe && frames && kinv && proj && (depths || pixel_depths) && cost_volume && sfcv && channel_weights;
+    for (int f = 0; pointers_ok && f < num_frames && f < MR_MAX_FRAMES; ++f)
+        if (!frames[f] || !sfcv[f] || (sfcv_b8 && !sfcv_b8[f])) pointers_ok = false;
+    mr_cv_launch L;
+    const int refused = cv_decide(num_frames, batch, num_depths, height, width, use_ssim, pixel_depths != nullptr, sfcv_mult_mask != 0, patch_size,
+                                  tiled, sfcv_b8 != nullptr, relaxed, lean, pointers_ok, L);
+    if (refused) return refused;
     CvArgs a;
     a.keyframe = keyframe;
     for (int f = 0; f < MR_MAX_FRAMES; ++f) {
         a.frames[f] = f < num_frames ? frames[f] : nullptr;
         a.sfcv[f] = f < num_frames ? sfcv[f] : nullptr;
         a.sfcv_b8[f] = (sfcv_b8 && f < num_frames) ? sfcv_b8[f] : nullptr;
-        if (f < num_frames && (!a.frames[f] || !a.sfcv[f] || (sfcv_b8 && !a.sfcv_b8[f]))) return MR_ERR_BAD_ARGUMENT;
     }
-    // the bf16 copy is written by the register-held fusion kernel of the default configuration only
-    if (sfcv_b8 && !(patch_size == 3 && sfcv_mult_mask && !tiled && (num_depths == 32 || num_depths == 48 || num_depths == 64))) return MR_ERR_UNSUPPORTED;
     a.kinv = kinv; a.proj = proj; a.depths = depths; a.pix_depths = pixel_depths; a.cv = cost_volume;
     a.F = num_frames; a.B = batch; a.D = num_depths; a.H = height; a.W = width;
     a.tiles_x = 0; a.nchunk = 1; a.dchunk = num_depths;
@@ -1393,9 +1470,8 @@ int cost_volume_entry(const float* keyframe, const float* const* frames, int32_t
     a.wm1 = (float)(width - 1); a.hm1 = (float)(height - 1);
     a.rwm1 = 1.0f / a.wm1; a.rhm1 = 1.0f / a.hm1;
     a.fast_w = mr_exact_const_division(a.wm1); a.fast_h = mr_exact_const_division(a.hm1);
-    if (height < 2 * a.border + 1 || width < 2 * a.border + 1) return MR_ERR_BAD_ARGUMENT;
-    if (patch_size == 3) return launch_cv<32, 16>(a, use_ssim, !sfcv_mult_mask, tiled, (hipStream_t)stream);
-    return launch_cv_patch(a, use_ssim, !sfcv_mult_mask, patch_size / 2, (hipStream_t)stream);
+    if (L.family == MR_CV_FAMILY_PATCH) return launch_cv_patch(a, L, (hipStream_t)stream);
+    return launch_cv<CV_TX, CV_TY>(a, L, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -1426,6 +1502,15 @@ extern "C" int mr_exact_const_division(float d) {
     }
     verdict[key] = ok;
     return ok;
+}
+
+// The launch decision of the entry points below, for tests and tools: cv_decide is the function cost_volume_entry itself consumes.
+extern "C" int mr_cost_volume_launch_query(int32_t num_frames, int32_t batch, int32_t num_depths, int32_t height, int32_t width,
+                                           int32_t use_ssim, int32_t has_pixel_depths, int32_t sfcv_mult_mask, int32_t patch_size,
+                                           int32_t tiled, int32_t has_b8, int32_t relaxed, int32_t lean, mr_cv_launch* out) {
+    if (!out) return MR_ERR_BAD_ARGUMENT;
+    return cv_decide(num_frames, batch, num_depths, height, width, use_ssim, has_pixel_depths != 0, sfcv_mult_mask != 0, patch_size, tiled != 0,
+                     has_b8 != 0, relaxed != 0, lean != 0, true, *out);
 }
 
 extern "C" int mr_cost_volume_patch_f32(const float* keyframe, const float* const* frames, int32_t num_frames,
