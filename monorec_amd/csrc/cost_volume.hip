@@ -56,7 +56,6 @@ struct CvArgs {
     int border;           // border_radius = patch_size / 2 + 1 (monorec_model.py:139); 2 for the default 3x3 patch
     float wm1, hm1;       // fp32(W - 1), fp32(H - 1): the divisors of layers.py:67-68
     float rwm1, rhm1;     // fp32(1 / wm1), fp32(1 / hm1)
-    int relaxed_sums;     // 1 (mr_cost_volume_b8_f32 = the bf16 configuration only): separable 3x3 window sums and x * fp32(1/9) - see march_finish
     int fast_w, fast_h;   // 1: the 3-instruction sequence div_const() equals the correctly rounded quotient for EVERY fp32 dividend
                           // (checked exhaustively on the host, mr_exact_const_division); 0: IEEE division
     int lean;             // 1 (mr_cost_volume_b8_lean_f32): the fusion kernel does NOT finalise the dense fp32 single-frame volumes (sfcv stays scratch)
@@ -151,17 +150,80 @@ __device__ __forceinline__ float bilinear(__amdgpu_buffer_rsrc_t img, int plane_
     return fmaf(d, sp.se, fmaf(c, sp.sw, fmaf(b, sp.ne, a * sp.nw)));
 }
 
-// bilinear sample of the border mask (ones with a 2 px zero frame, monorec_model.py:282-284) != 0
-__device__ __forceinline__ bool mask_hit(const Sample& sp, int H, int W) {
-    const float ml = (sp.x0 >= 2 && sp.x0 < W - 2) ? 1.f : 0.f, mr = (sp.x0 + 1 >= 2 && sp.x0 + 1 < W - 2) ? 1.f : 0.f;
-    const float mt = (sp.y0 >= 2 && sp.y0 < H - 2) ? 1.f : 0.f, mb = (sp.y0 + 1 >= 2 && sp.y0 + 1 < H - 2) ? 1.f : 0.f;
+// bilinear sample of the border mask (ones with a `br` px zero frame, monorec_model.py:282-284; br = 2 for the default 3x3 patch) != 0
+__device__ __forceinline__ bool mask_hit_r(const Sample& sp, int H, int W, int br) {
+    const float ml = (sp.x0 >= br && sp.x0 < W - br) ? 1.f : 0.f, mr = (sp.x0 + 1 >= br && sp.x0 + 1 < W - br) ? 1.f : 0.f;
+    const float mt = (sp.y0 >= br && sp.y0 < H - br) ? 1.f : 0.f, mb = (sp.y0 + 1 >= br && sp.y0 + 1 < H - br) ? 1.f : 0.f;
     const float m = fmaf(mr * mb, sp.se, fmaf(ml * mb, sp.sw, fmaf(mr * mt, sp.ne, (ml * mt) * sp.nw)));
     return m != 0.f;
 }
 
+// ---- what cv_sad_kernel and cv_sad_patch_kernel share ----------------------------------------------------------------------
+// Keyframe tile (+0.5; 0 outside the image) -> kf[3][HY][HX]; (y0, x0) = the image position of the tile's first entry, NT threads.
+__device__ __forceinline__ void load_kf_tile(float* kf, const float* kimg, int y0, int x0, int HY, int HX, int H, int W, int tid, int NT) {
+    const int HWp = H * W;
+    for (int i = tid; i < 3 * HY * HX; i += NT) {
+        const int c = i / (HY * HX), r = i % (HY * HX);
+        const int gy = y0 + r / HX, gx = x0 + r % HX;
+        float v = 0.f;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = kimg[c * HWp + gy * W + gx] + 0.5f;
+        kf[i] = v;
+    }
+}
+
 // MODE = the photometric term of monorec_model.py:227-243 (use_ssim): 1 SSIM distance (default), 0 absolute difference,
 // 2 the 0.85 / 0.15 mix of both, 3 absolute difference averaged over 3x3 (zero padded, avg_pool2d).
-// OPT bit 0: per-pixel depth hypotheses (cv_depths).  OPT bit 1: sfcv_mult_mask=False (monorec_model.py:252-253) - the single-frame
+// photo_term: MODE 0 - 2 for channel c of one position.  wr / kf: warped and keyframe tile [3][HY][HX] (+0.5); lyy / lxx: rows / columns of
+// the position's reflection-padded 3x3 window inside the tile, li_c the index of the position itself in channel c; mu_y / sig_y: the keyframe window statistics.
+// (MODE 3 stays in the kernels: the tiled one unrolls its window loop, the patch one does not.)
+template <int MODE>
+__device__ __forceinline__ float photo_term(const float* wr, const float* kf, int c, int HY, int HX, const int (&lyy)[3], const int (&lxx)[3],
+                                            int li_c, float mu_y, float sig_y) {
+    const float C1 = 0x1.a36e2ep-14f, C2 = 0x1.d7dbf4p-11f;   // fp32(0.01**2), fp32(0.03**2)  layers.py:116-117
+    float sv = 0.f;
+    if (MODE == 1 || MODE == 2) {
+        float sx1 = 0.f, sx2 = 0.f, sxy = 0.f;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int li = (c * HY + lyy[dy]) * HX + lxx[dx];
+                const float x = wr[li], k = kf[li];
+                const float xx = x * x, xk = x * k;
+                if (dy == 0 && dx == 0) { sx1 = x; sx2 = xx; sxy = xk; }
+                else { sx1 = sx1 + x; sx2 = sx2 + xx; sxy = sxy + xk; }
+            }
+        const float mu_x = div9(sx1);
+        const float mu_x_sq = mu_x * mu_x, mu_y_sq = mu_y * mu_y, mu_xy = mu_x * mu_y;
+        const float sig_x = div9(sx2) - mu_x_sq;
+        const float sig_xy = div9(sxy) - mu_xy;
+        const float sn = (2.0f * mu_xy + C1) * (2.0f * sig_xy + C2);          // layers.py:133
+        const float sd = (mu_x_sq + mu_y_sq + C1) * (sig_x + sig_y + C2);     // layers.py:134
+        sv = fminf(fmaxf((1.0f - ssim_ratio(sn, sd)) / 2.0f, 0.0f), 1.0f);    // layers.py:137
+    }
+    if (MODE == 0 || MODE == 2) {                                             // |warped - keyframe|, :228,239
+        const float ad = fabsf(wr[li_c] - kf[li_c]);
+        sv = MODE == 0 ? ad : 0.85f * sv + 0.15f * ad;
+    }
+    return sv;
+}
+
+// The flag a raw sad plane carries in its sign bit (sad >= 0, so the sign is free; -0.0 keeps it): with PFLAG the plane's own flag, else
+// the all-depth validity, on the last plane of the chunk.
+template <bool PFLAG>
+__device__ __forceinline__ float sad_with_flag(float s, bool pflag, bool last_plane, bool hit_all) {
+    if (PFLAG) return pflag ? s : -s;
+    return (last_plane && !hit_all) ? -s : s;
+}
+
+// PFLAG: the all-depth validity of pixel (opy, opx) lives in plane f of sample b of the cost-volume buffer; a chunk that saw an invalid plane clears it.
+template <bool PFLAG>
+__device__ __forceinline__ void clear_validity(const CvArgs& a, int b, int f, int opy, int opx, bool invalid) {
+    if (PFLAG && invalid)
+        atomicAnd((unsigned int*)a.cv + ((long long)b * a.D + f) * (a.H * a.W) + opy * a.W + opx, 0u);
+}
+
+// MODE: see photo_term.  OPT bit 0: per-pixel depth hypotheses (cv_depths).  OPT bit 1: sfcv_mult_mask=False (monorec_model.py:252-253) - the single-frame
 // volumes are masked per depth plane by (any channel of the warped pixel != 0) | (warped pixel == keyframe pixel) instead of by
 // the all-depth validity; that flag rides in the sign bit of every raw sad plane and the validity moves into the (not yet
 // written) cost-volume buffer, plane f of sample b, cleared with an atomic AND.
@@ -191,13 +253,7 @@ __global__ __launch_bounds__(TX * TY) void cv_sad_kernel(const CvArgs a) {
     const float* kimg = a.keyframe + (long long)b * 3 * HWp;
 
     // ---- keyframe tile (+0.5) ---------------------------------------------------------------------
-    for (int i = tid; i < 3 * HY * HX; i += NT) {
-        const int c = i / (HY * HX), r = i % (HY * HX);
-        const int gy = ty0 - 2 + r / HX, gx = tx0 - 2 + r % HX;
-        float v = 0.f;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = kimg[c * HWp + gy * W + gx] + 0.5f;
-        kf[i] = v;
-    }
+    load_kf_tile(kf, kimg, ty0 - 2, tx0 - 2, HY, HX, H, W, tid, NT);
 
     // ---- positions owned by this thread ---------------------------------------------------------------
     const int oly = tid / TX, olx = tid % TX;
@@ -257,7 +313,6 @@ __global__ __launch_bounds__(TX * TY) void cv_sad_kernel(const CvArgs a) {
         }
     }
 
-    const float C1 = 0x1.a36e2ep-14f, C2 = 0x1.d7dbf4p-11f;   // fp32(0.01**2), fp32(0.03**2)  layers.py:116-117
     const float* P = a.proj + ((long long)b * a.F + f) * 12;
     const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void*)(a.frames[f] + (long long)b * 3 * HWp), 0, 3 * HWp * 4, 0x00020000);
     float* sad_out = a.sfcv[f] + (long long)b * D * HWp + opy * W + opx;
@@ -279,7 +334,7 @@ __global__ __launch_bounds__(TX * TY) void cv_sad_kernel(const CvArgs a) {
             float* wru = wr + u * 3 * HY * HX;
             if (own_in) {
                 const Sample sp = project(ro[0], ro[1], ro[2], PIXD ? pd[opy * W + opx] : depth, P, H, W, a);
-                hit_all = hit_all && mask_hit(sp, H, W);                   // monorec_model.py:218-219
+                hit_all = hit_all && mask_hit_r(sp, H, W, 2);                 // monorec_model.py:218-219
                 const Taps tp = tap_offsets(sp, H, W);
                 bool any_nz = false, all_eq = true;
 #pragma unroll
@@ -319,32 +374,7 @@ __global__ __launch_bounds__(TX * TY) void cv_sad_kernel(const CvArgs a) {
                     if (s_in[r]) {
 #pragma unroll
                         for (int c = 0; c < 3; ++c) {
-                            float sv = 0.f;
-                            if (MODE == 1 || MODE == 2) {
-                                float sx1 = 0.f, sx2 = 0.f, sxy = 0.f;
-#pragma unroll
-                                for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                                    for (int dx = 0; dx < 3; ++dx) {
-                                        const int li = (c * HY + lyy[dy]) * HX + lxx[dx];
-                                        const float x = wru[li], k = kf[li];
-                                        const float xx = x * x, xk = x * k;
-                                        if (dy == 0 && dx == 0) { sx1 = x; sx2 = xx; sxy = xk; }
-                                        else { sx1 = sx1 + x; sx2 = sx2 + xx; sxy = sxy + xk; }
-                                    }
-                                const float mu_x = div9(sx1), mu_y = kmu[r][c];
-                                const float mu_x_sq = mu_x * mu_x, mu_y_sq = mu_y * mu_y, mu_xy = mu_x * mu_y;
-                                const float sig_x = div9(sx2) - mu_x_sq;
-                                const float sig_xy = div9(sxy) - mu_xy;
-                                const float sn = (2.0f * mu_xy + C1) * (2.0f * sig_xy + C2);          // layers.py:133
-                                const float sd = (mu_x_sq + mu_y_sq + C1) * (sig_x + ksg[r][c] + C2); // layers.py:134
-                                sv = fminf(fmaxf((1.0f - ssim_ratio(sn, sd)) / 2.0f, 0.0f), 1.0f);               // layers.py:137
-                            }
-                            if (MODE == 0 || MODE == 2) {                                             // |warped - keyframe|, :228,239
-                                const int li = (c * HY + sly[r] + 1) * HX + slx[r] + 1;
-                                const float ad = fabsf(wru[li] - kf[li]);
-                                sv = MODE == 0 ? ad : 0.85f * sv + 0.15f * ad;
-                            }
+                            float sv = photo_term<MODE>(wru, kf, c, HY, HX, lyy, lxx, (c * HY + sly[r] + 1) * HX + slx[r] + 1, kmu[r][c], ksg[r][c]);
                             if (MODE == 3) {                                                          // avg_pool2d(|.|, 3, 1, padding=1), :241
                                 const int qy = ty0 - 1 + sly[r], qx = tx0 - 1 + slx[r];
                                 float acc = 0.f;
@@ -382,14 +412,12 @@ __global__ __launch_bounds__(TX * TY) void cv_sad_kernel(const CvArgs a) {
                         const float v = esu[(oly + dy) * SX + olx + dx];
                         s = (dy == 0 && dx == 0) ? v : s + v;
                     }
-                if (PFLAG) { if (!pflag[u]) s = -s; }           // per-plane flag in the sign bit
-                else if (d + u == d_hi - 1 && !hit_all) s = -s; // sad >= 0: the sign bit is free (-0.0 keeps it)
+                s = sad_with_flag<PFLAG>(s, pflag[u], d + u == d_hi - 1, hit_all);
                 if (d + u < d_hi) sad_out[(long long)(d + u) * HWp] = s;
             }
         }
     }
-    if (PFLAG && own_in && !hit_all)
-        atomicAnd((unsigned int*)a.cv + ((long long)b * D + f) * HWp + opy * W + opx, 0u);
+    clear_validity<PFLAG>(a, b, f, opy, opx, own_in && !hit_all);
 }
 
 // ---- A2  cv_sad_march_kernel: the default configuration (SSIM, 3x3 patch, all-depth validity) without LDS ------------------
@@ -510,30 +538,8 @@ __device__ __forceinline__ void project_batch(Sample (&o)[N], bool (&hit)[N], fl
     }
 }
 
-// bilinear() for N planes x 3 channels: all 12 N gathers first, then the N * 3 FMA chains level by level
-template <int N>
-__device__ __forceinline__ void bilinear_batch(float (&out)[N * 3], __amdgpu_buffer_rsrc_t img, int plane_bytes, const Taps (&t)[N],
-                                               const Sample (&sp)[N]) {
-    float a[N * 3], b[N * 3], c[N * 3], d[N * 3];
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) {
-        const int so = (i % 3) * plane_bytes;
-        a[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(img, t[i / 3].a, so, 0));
-        b[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(img, t[i / 3].b, so, 0));
-        c[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(img, t[i / 3].c, so, 0));
-        d[i] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(img, t[i / 3].d, so, 0));
-    }
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) out[i] = a[i] * sp[i / 3].nw;
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) out[i] = fmaf(b[i], sp[i / 3].ne, out[i]);
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) out[i] = fmaf(c[i], sp[i / 3].sw, out[i]);
-#pragma unroll
-    for (int i = 0; i < N * 3; ++i) out[i] = fmaf(d[i], sp[i / 3].se, out[i]);
-}
-
-// The same in two halves for the prefetching marching step: the 12 N gathers of a row are issued one step ahead of their use.
+// bilinear() for N planes x 3 channels in two halves: all 12 N gathers first (bilinear_issue), then the N * 3 FMA chains level by level
+// (bilinear_combine).
 template <int N>
 struct Gathered {
     float a[N * 3], b[N * 3], c[N * 3], d[N * 3];     // the four taps of every (plane, channel)
@@ -598,9 +604,6 @@ struct MarchCtx {
     int planes;             // planes of this wave that exist: DP, or 1 for the last wave of an odd D
 };
 
-// One marching step: warp virtual row r into `cur`, emit the SSIM row r - 1 (windows over top / mid / cur) as cur.e, emit the
-// sad of output row r - 2 (box over the e rows), then turn `mid` into the next top sums.  The caller alternates two MarchRow
-// objects as mid / cur, so the raw rows never move between registers.
 // First half of a marching step: project virtual row r for DP planes and ISSUE every global load the step needs (12 DP gathers, the
 // keyframe pixel, the prepass statistics of SSIM row r - 1).  Nothing here waits for a load.
 template <int DP, bool PIXD, bool KFS, bool FD>
@@ -608,7 +611,7 @@ __device__ __forceinline__ void march_issue(const MarchCtx<DP>& c, int r, Gather
     const CvArgs& a = c.a;
     const int H = a.H, W = a.W;
     const int HWp = H * W;
-    int wr = r < 0 ? -r : (r >= H ? 2 * H - 2 - r : r);
+    int wr = r < 0 ? -r : (r >= H ? 2 * H - 2 - r : r);          // reflect_idx(), spelled out: the call schedules the marching kernels differently
     wr = min(max(wr, 0), H - 1);
     const int pix = wr * W + c.cx;
     float ray[3];
@@ -926,13 +929,6 @@ __global__ __launch_bounds__(256) void cv_fuse_reg_kernel(const CvArgs a) {
 // it), so this variant trades speed for simplicity: 32x8 tile, one depth plane per iteration, every stage a strided loop over its
 // tile (warped planes on tile + R + 1, photometric term on tile + R, R = P / 2), keyframe SSIM statistics kept in LDS.
 // Same conventions as cv_sad_kernel for the raw sad planes (validity / per-plane flag in the sign bit).
-__device__ __forceinline__ bool mask_hit_r(const Sample& sp, int H, int W, int br) {
-    const float ml = (sp.x0 >= br && sp.x0 < W - br) ? 1.f : 0.f, mr = (sp.x0 + 1 >= br && sp.x0 + 1 < W - br) ? 1.f : 0.f;
-    const float mt = (sp.y0 >= br && sp.y0 < H - br) ? 1.f : 0.f, mb = (sp.y0 + 1 >= br && sp.y0 + 1 < H - br) ? 1.f : 0.f;
-    const float m = fmaf(mr * mb, sp.se, fmaf(ml * mb, sp.sw, fmaf(mr * mt, sp.ne, (ml * mt) * sp.nw)));
-    return m != 0.f;
-}
-
 template <int MODE, int OPT>
 __global__ __launch_bounds__(256) void cv_sad_patch_kernel(const CvArgs a, const int R) {
     constexpr bool PIXD = OPT & 1, PFLAG = (OPT & 2) != 0;
@@ -956,13 +952,7 @@ __global__ __launch_bounds__(256) void cv_sad_patch_kernel(const CvArgs a, const
     const int HWp = H * W;
     const float* kimg = a.keyframe + (long long)b * 3 * HWp;
 
-    for (int i = tid; i < 3 * HY * HX; i += NT) {
-        const int c = i / (HY * HX), r = i % (HY * HX);
-        const int gy = ty0 - HALO + r / HX, gx = tx0 - HALO + r % HX;
-        float v = 0.f;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = kimg[c * HWp + gy * W + gx] + 0.5f;
-        kf[i] = v;
-    }
+    load_kf_tile(kf, kimg, ty0 - HALO, tx0 - HALO, HY, HX, H, W, tid, NT);
     __syncthreads();
     if (MODE == 1 || MODE == 2) {
         for (int i = tid; i < SX * SY; i += NT) {
@@ -991,7 +981,6 @@ __global__ __launch_bounds__(256) void cv_sad_patch_kernel(const CvArgs a, const
     const int opy = ty0 + oly, opx = tx0 + olx;
     const bool own_in = opy < H && opx < W;
     const float* Ki = a.kinv + b * 9;
-    const float C1 = 0x1.a36e2ep-14f, C2 = 0x1.d7dbf4p-11f;
     const float* P = a.proj + ((long long)b * a.F + f) * 12;
     const __amdgpu_buffer_rsrc_t img = __builtin_amdgcn_make_buffer_rsrc((void*)(a.frames[f] + (long long)b * 3 * HWp), 0, 3 * HWp * 4, 0x00020000);
     float* sad_out = a.sfcv[f] + (long long)b * D * HWp + opy * W + opx;
@@ -1052,32 +1041,7 @@ __global__ __launch_bounds__(256) void cv_sad_patch_kernel(const CvArgs a, const
                 }
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    float sv = 0.f;
-                    if (MODE == 1 || MODE == 2) {
-                        float sx1 = 0.f, sx2 = 0.f, sxy = 0.f;
-#pragma unroll
-                        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) {
-                                const int li = (c * HY + lyy[dy]) * HX + lxx[dx];
-                                const float x = wr[li], k = kf[li];
-                                const float xx = x * x, xk = x * k;
-                                if (dy == 0 && dx == 0) { sx1 = x; sx2 = xx; sxy = xk; }
-                                else { sx1 = sx1 + x; sx2 = sx2 + xx; sxy = sxy + xk; }
-                            }
-                        const float mu_x = div9(sx1), mu_y = kmu[c * SY * SX + i];
-                        const float mu_x_sq = mu_x * mu_x, mu_y_sq = mu_y * mu_y, mu_xy = mu_x * mu_y;
-                        const float sig_x = div9(sx2) - mu_x_sq;
-                        const float sig_xy = div9(sxy) - mu_xy;
-                        const float sn = (2.0f * mu_xy + C1) * (2.0f * sig_xy + C2);                      // layers.py:133
-                        const float sd = (mu_x_sq + mu_y_sq + C1) * (sig_x + ksg[c * SY * SX + i] + C2);  // layers.py:134
-                        sv = fminf(fmaxf((1.0f - ssim_ratio(sn, sd)) / 2.0f, 0.0f), 1.0f);                           // layers.py:137
-                    }
-                    if (MODE == 0 || MODE == 2) {
-                        const int li = (c * HY + sy + 1) * HX + sx + 1;
-                        const float ad = fabsf(wr[li] - kf[li]);
-                        sv = MODE == 0 ? ad : 0.85f * sv + 0.15f * ad;
-                    }
+                    float sv = photo_term<MODE>(wr, kf, c, HY, HX, lyy, lxx, (c * HY + sy + 1) * HX + sx + 1, kmu[c * SY * SX + i], ksg[c * SY * SX + i]);
                     if (MODE == 3) {
                         float acc = 0.f;
                         bool first = true;
@@ -1105,13 +1069,10 @@ __global__ __launch_bounds__(256) void cv_sad_patch_kernel(const CvArgs a, const
                     const float v = es[(oly + dy) * SX + olx + dx];
                     s = (dy == 0 && dx == 0) ? v : s + v;
                 }
-            if (PFLAG) { if (!pflag) s = -s; }
-            else if (d == d_hi - 1 && !hit_all) s = -s;
-            sad_out[(long long)d * HWp] = s;
+            sad_out[(long long)d * HWp] = sad_with_flag<PFLAG>(s, pflag, d == d_hi - 1, hit_all);
         }
     }
-    if (PFLAG && own_in && !hit_all)
-        atomicAnd((unsigned int*)a.cv + ((long long)b * D + f) * HWp + opy * W + opx, 0u);
+    clear_validity<PFLAG>(a, b, f, opy, opx, own_in && !hit_all);
 }
 
 // Per-pixel frame fusion (monorec_model.py:251-269) over the raw sad values kernel A left in the sfcv buffers.
@@ -1178,22 +1139,7 @@ __global__ __launch_bounds__(256) void cv_fuse_kernel(const CvArgs a) {
     }
 }
 
-template <int TX, int TY, int MODE, int OPT>
-void launch_sad(const CvArgs& k, dim3 grid, hipStream_t stream) {
-    hipLaunchKernelGGL((cv_sad_kernel<TX, TY, MODE, OPT>), grid, dim3(TX * TY), 0, stream, k);
-}
-
-template <int TX, int TY, int MODE>
-void launch_sad_opt(const CvArgs& k, int opt, dim3 grid, hipStream_t stream) {
-    switch (opt) {
-        case 1: launch_sad<TX, TY, MODE, 1>(k, grid, stream); break;
-        case 2: launch_sad<TX, TY, MODE, 2>(k, grid, stream); break;
-        case 3: launch_sad<TX, TY, MODE, 3>(k, grid, stream); break;
-        default: launch_sad<TX, TY, MODE, 0>(k, grid, stream); break;
-    }
-}
-
-// ---- the launch decision: ONE host function (cv_decide) fills an mr_cv_launch, the launchers below consume it and decide nothing themselves;
+// ---- the launch decision: ONE host function (cv_decide) fills an mr_cv_launch, the launcher below (launch_cv) consumes it and decides nothing itself;
 // mr_cost_volume_launch_query hands the same struct out (tests/cost_volume_paths.py restates the rules and compares field by field) ----------
 
 constexpr int CV_TX = 32, CV_TY = 16;      // tile of cv_sad_kernel
@@ -1216,20 +1162,6 @@ void decide_fuse(mr_cv_launch& L, int B, int D, int H, int W, bool plane_flags, 
     L.fuse_pflag = plane_flags ? 1 : 0;
     L.fuse_grid[0] = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     L.fuse_grid[1] = 1;
-}
-
-void launch_fuse(const CvArgs& k, const mr_cv_launch& L, hipStream_t stream) {
-    if (L.fuse == MR_CV_FUSE_REG) {
-        const dim3 grid((unsigned)L.fuse_grid[0], (unsigned)L.fuse_grid[1]);
-        const bool b8 = L.fuse_b8 != 0;
-        if (k.D == 32) { if (b8) hipLaunchKernelGGL((cv_fuse_reg_kernel<32, true>), grid, dim3(256), 0, stream, k); else hipLaunchKernelGGL((cv_fuse_reg_kernel<32, false>), grid, dim3(256), 0, stream, k); }
-        else if (k.D == 48) { if (b8) hipLaunchKernelGGL((cv_fuse_reg_kernel<48, true>), grid, dim3(256), 0, stream, k); else hipLaunchKernelGGL((cv_fuse_reg_kernel<48, false>), grid, dim3(256), 0, stream, k); }
-        else { if (b8) hipLaunchKernelGGL((cv_fuse_reg_kernel<64, true>), grid, dim3(256), 0, stream, k); else hipLaunchKernelGGL((cv_fuse_reg_kernel<64, false>), grid, dim3(256), 0, stream, k); }
-        return;
-    }
-    const unsigned blocks = (unsigned)L.fuse_grid[0];
-    if (L.fuse_pflag) hipLaunchKernelGGL(cv_fuse_kernel<true>, dim3(blocks), dim3(256), 0, stream, k);
-    else hipLaunchKernelGGL(cv_fuse_kernel<false>, dim3(blocks), dim3(256), 0, stream, k);
 }
 
 // Marching kernel geometry: strips of <= 60 output columns (equal pitch, so that every strip carries the same load) and row
@@ -1354,87 +1286,100 @@ int cv_decide(int F, int B, int D, int H, int W, int use_ssim, bool pixd, bool m
     return 0;
 }
 
-template <int TX, int TY>
-int launch_cv(const CvArgs& a, const mr_cv_launch& L, hipStream_t stream) {
-    CvArgs k = a;
+// ---- kernel tables, indexed by fields of mr_cv_launch.  They name every instantiation this file launches (tests/cost_volume_paths.py reads them
+// back) and nothing else: a combination cv_decide cannot produce has no row, and cv_kernels() answers it with a null pointer ----------------------
+using TiledKernel = void (*)(CvArgs);
+using PatchKernel = void (*)(CvArgs, int);
+using MarchKernel = void (*)(CvArgs, MarchGeom);
+using FuseKernel = void (*)(CvArgs);
+
+const TiledKernel TILED[4][4] = {       // [mode][opt]
+    {cv_sad_kernel<CV_TX, CV_TY, 0, 0>, cv_sad_kernel<CV_TX, CV_TY, 0, 1>, cv_sad_kernel<CV_TX, CV_TY, 0, 2>, cv_sad_kernel<CV_TX, CV_TY, 0, 3>},
+    {cv_sad_kernel<CV_TX, CV_TY, 1, 0>, cv_sad_kernel<CV_TX, CV_TY, 1, 1>, cv_sad_kernel<CV_TX, CV_TY, 1, 2>, cv_sad_kernel<CV_TX, CV_TY, 1, 3>},
+    {cv_sad_kernel<CV_TX, CV_TY, 2, 0>, cv_sad_kernel<CV_TX, CV_TY, 2, 1>, cv_sad_kernel<CV_TX, CV_TY, 2, 2>, cv_sad_kernel<CV_TX, CV_TY, 2, 3>},
+    {cv_sad_kernel<CV_TX, CV_TY, 3, 0>, cv_sad_kernel<CV_TX, CV_TY, 3, 1>, cv_sad_kernel<CV_TX, CV_TY, 3, 2>, cv_sad_kernel<CV_TX, CV_TY, 3, 3>}};
+
+const PatchKernel PATCH[4][4] = {       // [mode][opt]
+    {cv_sad_patch_kernel<0, 0>, cv_sad_patch_kernel<0, 1>, cv_sad_patch_kernel<0, 2>, cv_sad_patch_kernel<0, 3>},
+    {cv_sad_patch_kernel<1, 0>, cv_sad_patch_kernel<1, 1>, cv_sad_patch_kernel<1, 2>, cv_sad_patch_kernel<1, 3>},
+    {cv_sad_patch_kernel<2, 0>, cv_sad_patch_kernel<2, 1>, cv_sad_patch_kernel<2, 2>, cv_sad_patch_kernel<2, 3>},
+    {cv_sad_patch_kernel<3, 0>, cv_sad_patch_kernel<3, 1>, cv_sad_patch_kernel<3, 2>, cv_sad_patch_kernel<3, 3>}};
+
+struct MarchEntry { int dp, pixd, kfs, fd, relaxed; MarchKernel kernel; };
+template <int DP, bool PIXD, bool KFS, bool FD, bool RELAXED>
+constexpr MarchEntry march_entry() { return {DP, PIXD, KFS, FD, RELAXED, cv_sad_march_kernel<DP, PIXD, KFS, FD, RELAXED>}; }
+
+// One plane per wave runs with the prepass and without per-pixel depths only; the relaxed sums exist for FD, KFS, no per-pixel depths only.
+const MarchEntry MARCH[] = {        // matched on (dp, pixd, kfs, fd, relaxed)
+    march_entry<1, false, true, false, false>(),  march_entry<1, false, true, true, false>(),
+    march_entry<2, true, true, false, false>(),   march_entry<2, true, true, true, false>(),
+    march_entry<2, false, true, false, false>(),  march_entry<2, false, true, true, false>(),
+    march_entry<2, true, false, false, false>(),  march_entry<2, true, false, true, false>(),
+    march_entry<2, false, false, false, false>(), march_entry<2, false, false, true, false>(),
+    march_entry<1, false, true, true, true>(),    march_entry<2, false, true, true, true>()};
+
+struct FuseRegRow { int depths; FuseKernel kernel[2]; };
+const FuseRegRow FUSE_REG[] = {          // matched on depths, then [b8]
+    {32, {cv_fuse_reg_kernel<32, false>, cv_fuse_reg_kernel<32, true>}},
+    {48, {cv_fuse_reg_kernel<48, false>, cv_fuse_reg_kernel<48, true>}},
+    {64, {cv_fuse_reg_kernel<64, false>, cv_fuse_reg_kernel<64, true>}}};
+
+const FuseKernel FUSE_GENERIC[2] = {cv_fuse_kernel<false>, cv_fuse_kernel<true>};      // [pflag]
+
+// The kernels of a launch decision: exactly one sad kernel (that of L.family) and the fusion kernel, or null where the tables have no row.
+struct CvKernels {
+    MarchKernel march;
+    TiledKernel tiled;
+    PatchKernel patch;
+    FuseKernel fuse;
+    bool complete() const { return (march || tiled || patch) && fuse; }
+};
+
+CvKernels cv_kernels(const mr_cv_launch& L) {
+    CvKernels k = {nullptr, nullptr, nullptr, nullptr};
+    const bool slot = L.mode >= 0 && L.mode < 4 && L.opt >= 0 && L.opt < 4;
     if (L.family == MR_CV_FAMILY_MARCH) {
-        MarchGeom g;
-        g.strips = L.strips; g.pitch = L.pitch; g.TY = L.ty; g.ysegs = L.ysegs; g.npairs = L.npairs;
-        const dim3 grid((unsigned)L.sad_grid[0], (unsigned)L.sad_grid[1], (unsigned)L.sad_grid[2]);
-        const bool fd = L.fd != 0, kfs = L.kfs != 0, dp1 = L.dp == 1, pixd = L.pixd != 0;
-        if (L.kf_prepass)
-            hipLaunchKernelGGL(cv_kf_stats_kernel, dim3((unsigned)L.kf_grid[0], (unsigned)L.kf_grid[1]), dim3(256), 0, stream, k);
-#define MR_MARCH(DP_, PIXD_, KFS_)                                                                                              \
-    do {                                                                                                                        \
-        if (fd) hipLaunchKernelGGL((cv_sad_march_kernel<DP_, PIXD_, KFS_, true>), grid, dim3(256), 0, stream, k, g);          \
-        else hipLaunchKernelGGL((cv_sad_march_kernel<DP_, PIXD_, KFS_, false>), grid, dim3(256), 0, stream, k, g);                 \
-    } while (0)
-        if (L.relaxed) {
-            if (dp1) hipLaunchKernelGGL((cv_sad_march_kernel<1, false, true, true, true>), grid, dim3(256), 0, stream, k, g);
-            else hipLaunchKernelGGL((cv_sad_march_kernel<2, false, true, true, true>), grid, dim3(256), 0, stream, k, g);
-        } else
-        if (dp1) MR_MARCH(1, false, true);   // twice the waves, each with one plane: for shapes that leave the SIMDs short of waves
-        else if (kfs && pixd) MR_MARCH(2, true, true);
-        else if (kfs) MR_MARCH(2, false, true);
-        else if (pixd) MR_MARCH(2, true, false);
-        else MR_MARCH(2, false, false);
-#undef MR_MARCH
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        launch_fuse(k, L, stream);
-        return (int)hipGetLastError();
+        for (const MarchEntry& m : MARCH)
+            if (m.dp == L.dp && m.pixd == L.pixd && m.kfs == L.kfs && m.fd == L.fd && m.relaxed == L.relaxed) k.march = m.kernel;
+    } else if (L.family == MR_CV_FAMILY_TILED && slot) {
+        k.tiled = TILED[L.mode][L.opt];
+    } else if (L.family == MR_CV_FAMILY_PATCH && slot) {
+        k.patch = PATCH[L.mode][L.opt];
     }
-    k.tiles_x = L.tiles_x;
-    k.nchunk = L.nchunk;
-    k.dchunk = L.dchunk;
-    const dim3 grid((unsigned)L.sad_grid[0], (unsigned)L.sad_grid[1], (unsigned)L.sad_grid[2]);
-    if (L.flag_memset) {
-        hipError_t e = hipMemsetAsync(a.cv, 0xff, (size_t)a.B * a.D * a.H * a.W * sizeof(float), stream);
-        if (e != hipSuccess) return (int)e;
+    if (L.fuse == MR_CV_FUSE_REG) {
+        for (const FuseRegRow& r : FUSE_REG)
+            if (r.depths == L.fuse_depths) k.fuse = r.kernel[L.fuse_b8 != 0];
+    } else if (L.fuse == MR_CV_FUSE_GENERIC) {
+        k.fuse = FUSE_GENERIC[L.fuse_pflag != 0];
     }
-    switch (L.mode) {
-        case 0: launch_sad_opt<TX, TY, 0>(k, L.opt, grid, stream); break;
-        case 2: launch_sad_opt<TX, TY, 2>(k, L.opt, grid, stream); break;
-        case 3: launch_sad_opt<TX, TY, 3>(k, L.opt, grid, stream); break;
-        default: launch_sad_opt<TX, TY, 1>(k, L.opt, grid, stream); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    launch_fuse(k, L, stream);
-    return (int)hipGetLastError();
+    return k;
 }
 
-template <int MODE>
-void launch_sad_patch(const CvArgs& k, int opt, int R, dim3 grid, size_t lds, hipStream_t stream) {
-    switch (opt) {
-        case 1: hipLaunchKernelGGL((cv_sad_patch_kernel<MODE, 1>), grid, dim3(256), lds, stream, k, R); break;
-        case 2: hipLaunchKernelGGL((cv_sad_patch_kernel<MODE, 2>), grid, dim3(256), lds, stream, k, R); break;
-        case 3: hipLaunchKernelGGL((cv_sad_patch_kernel<MODE, 3>), grid, dim3(256), lds, stream, k, R); break;
-        default: hipLaunchKernelGGL((cv_sad_patch_kernel<MODE, 0>), grid, dim3(256), lds, stream, k, R); break;
-    }
-}
-
-int launch_cv_patch(const CvArgs& a, const mr_cv_launch& L, hipStream_t stream) {
+// The one launcher: it decides nothing, every number comes from `L`.  (L.lds_bytes is DYNAMIC LDS for the patch kernel only: the tiled
+// kernel's arrays are static, the marching kernels use none.)
+int launch_cv(const CvArgs& a, const mr_cv_launch& L, hipStream_t stream) {
+    const CvKernels kernels = cv_kernels(L);
+    if (!kernels.complete()) return MR_ERR_UNSUPPORTED;
     CvArgs k = a;
-    k.tiles_x = L.tiles_x;
-    k.nchunk = L.nchunk;
-    k.dchunk = L.dchunk;
-    const dim3 grid((unsigned)L.sad_grid[0], (unsigned)L.sad_grid[1], (unsigned)L.sad_grid[2]);
-    const size_t lds = (size_t)L.lds_bytes;
-    const int R = L.radius;
+    if (L.family != MR_CV_FAMILY_MARCH) { k.tiles_x = L.tiles_x; k.nchunk = L.nchunk; k.dchunk = L.dchunk; }
+    if (L.kf_prepass)
+        hipLaunchKernelGGL(cv_kf_stats_kernel, dim3((unsigned)L.kf_grid[0], (unsigned)L.kf_grid[1]), dim3(256), 0, stream, k);
     if (L.flag_memset) {
         hipError_t e = hipMemsetAsync(a.cv, 0xff, (size_t)a.B * a.D * a.H * a.W * sizeof(float), stream);
         if (e != hipSuccess) return (int)e;
     }
-    switch (L.mode) {
-        case 0: launch_sad_patch<0>(k, L.opt, R, grid, lds, stream); break;
-        case 2: launch_sad_patch<2>(k, L.opt, R, grid, lds, stream); break;
-        case 3: launch_sad_patch<3>(k, L.opt, R, grid, lds, stream); break;
-        default: launch_sad_patch<1>(k, L.opt, R, grid, lds, stream); break;
+    const dim3 grid((unsigned)L.sad_grid[0], (unsigned)L.sad_grid[1], (unsigned)L.sad_grid[2]), block((unsigned)L.sad_block);
+    if (kernels.march) {
+        const MarchGeom g = {L.strips, L.pitch, L.ty, L.ysegs, L.npairs};
+        hipLaunchKernelGGL(kernels.march, grid, block, 0, stream, k, g);
+    } else if (kernels.patch) {
+        hipLaunchKernelGGL(kernels.patch, grid, block, (size_t)L.lds_bytes, stream, k, (int)L.radius);
+    } else {
+        hipLaunchKernelGGL(kernels.tiled, grid, block, 0, stream, k);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    launch_fuse(k, L, stream);
+    hipLaunchKernelGGL(kernels.fuse, dim3((unsigned)L.fuse_grid[0], (unsigned)L.fuse_grid[1]), dim3(256), 0, stream, k);
     return (int)hipGetLastError();
 }
 
@@ -1461,7 +1406,6 @@ int cost_volume_entry(const float* keyframe, const float* const* frames, int32_t
     a.kinv = kinv; a.proj = proj; a.depths = depths; a.pix_depths = pixel_depths; a.cv = cost_volume;
     a.F = num_frames; a.B = batch; a.D = num_depths; a.H = height; a.W = width;
     a.tiles_x = 0; a.nchunk = 1; a.dchunk = num_depths;
-    a.relaxed_sums = (sfcv_b8 != nullptr || relaxed) ? 1 : 0;
     a.lean = (lean && sfcv_b8 != nullptr) ? 1 : 0;
     a.alpha = alpha;
     for (int c = 0; c < 3; ++c) a.cw[c] = channel_weights[c] / (float)(patch_size * patch_size);      // :141
@@ -1470,8 +1414,7 @@ int cost_volume_entry(const float* keyframe, const float* const* frames, int32_t
     a.wm1 = (float)(width - 1); a.hm1 = (float)(height - 1);
     a.rwm1 = 1.0f / a.wm1; a.rhm1 = 1.0f / a.hm1;
     a.fast_w = mr_exact_const_division(a.wm1); a.fast_h = mr_exact_const_division(a.hm1);
-    if (L.family == MR_CV_FAMILY_PATCH) return launch_cv_patch(a, L, (hipStream_t)stream);
-    return launch_cv<CV_TX, CV_TY>(a, L, (hipStream_t)stream);
+    return launch_cv(a, L, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -1509,8 +1452,10 @@ extern "C" int mr_cost_volume_launch_query(int32_t num_frames, int32_t batch, in
                                            int32_t use_ssim, int32_t has_pixel_depths, int32_t sfcv_mult_mask, int32_t patch_size,
                                            int32_t tiled, int32_t has_b8, int32_t relaxed, int32_t lean, mr_cv_launch* out) {
     if (!out) return MR_ERR_BAD_ARGUMENT;
-    return cv_decide(num_frames, batch, num_depths, height, width, use_ssim, has_pixel_depths != 0, sfcv_mult_mask != 0, patch_size, tiled != 0,
-                     has_b8 != 0, relaxed != 0, lean != 0, true, *out);
+    const int refused = cv_decide(num_frames, batch, num_depths, height, width, use_ssim, has_pixel_depths != 0, sfcv_mult_mask != 0, patch_size,
+                                  tiled != 0, has_b8 != 0, relaxed != 0, lean != 0, true, *out);
+    // a decision without a kernel in the tables is what the launcher refuses: answer as it would, with `out` left as decided (status 0)
+    return (!refused && !cv_kernels(*out).complete()) ? MR_ERR_UNSUPPORTED : refused;
 }
 
 extern "C" int mr_cost_volume_patch_f32(const float* keyframe, const float* const* frames, int32_t num_frames,

@@ -2,11 +2,11 @@
 
     * `rule()`: the launch decision (entry checks, the one-plane-per-wave rule, march_geometry, both depth-chunk loops, the patch LDS formula,
       the choice of the fusion kernel) restated in plain Python.  tests/test_cost_volume_paths.py compares it FIELD BY FIELD with what the
-      library itself answers (mr_cost_volume_launch_query - the function the launchers consume) for every case and for a few hundred
+      library itself answers (mr_cost_volume_launch_query - the function the launcher consumes) for every case and for a few hundred
       pseudo-random argument sets, refused ones included.
     * `constants()`: what the rules rest on, read from the source by regular expression, never typed in.
-    * `instantiations()`: every kernel instantiation NAMED AT A LAUNCH SITE of the source (the MR_MARCH macro expanded).  Each is either run by
-      at least one case or listed in UNREACHABLE with the reason - those are run by NO test.
+    * `instantiations()`: every kernel instantiation NAMED IN THE KERNEL TABLES of the source (the one launcher, launch_cv, launches nothing
+      else).  Each is either run by at least one case or listed in UNREACHABLE with the reason - those are run by NO test.
     * CASES: each names the sad-kernel instantiation and the fusion instantiation it is there for; `path_of(case)` re-derives both from the
       shape through `rule()`.  SUBPATHS: the branches inside a path key (strip counts, row-loop residues, chunking, ...), each with a predicate
       over (case, rule) that at least one case must satisfy.
@@ -161,50 +161,38 @@ def query(lib, F, B, D, H, W, use_ssim=1, pixd=False, mult_mask=True, patch=3, t
     out = _lib.CvLaunch()
     rc = lib.mr_cost_volume_launch_query(F, B, D, H, W, use_ssim, int(pixd), int(mult_mask), patch, int(tiled), int(b8), int(relaxed), int(lean), ctypes.byref(out))
     got = {k: (list(getattr(out, k)) if k in _ARRAYS else int(getattr(out, k))) for k in FIELDS}
-    assert rc == got["status"]
+    assert rc == got["status"]        # (a decision the kernel tables have no entry for would answer MR_ERR_UNSUPPORTED with status 0)
     return got
 
 
-# ---- kernel instantiations named at the launch sites ------------------------------------------------------------------------------------------------
+# ---- kernel instantiations named in the kernel tables ---------------------------------------------------------------------------------------------
 def _bools(text):
-    return text.replace("true", "1").replace("false", "0")
+    return text.replace("true", "1").replace("false", "0").replace(" ", "")
+
+
+def _table(name, s):
+    """The initialiser of the constant table `name` (up to its closing `};`)."""
+    return _one(r"\nconst \w+ %s(?:\[\d*\])+ = \{(.*?)\};" % name, s, re.S)
 
 
 @functools.lru_cache(None)
 def instantiations():
-    """Every kernel instantiation a launch site of csrc/cost_volume.hip names, as strings like `cv_sad_march_kernel<2,0,1,1,0>`
+    """Every kernel instantiation the kernel tables of csrc/cost_volume.hip name, as strings like `cv_sad_march_kernel<2,0,1,1,0>`
     (DP, PIXD, KFS, FD, RELAXED), `cv_sad_kernel<32,16,MODE,OPT>`, `cv_sad_patch_kernel<MODE,OPT>`, `cv_fuse_reg_kernel<DD,B8OUT>`,
-    `cv_fuse_kernel<PFLAG>`, `cv_kf_stats_kernel`."""
+    `cv_fuse_kernel<PFLAG>`, `cv_kf_stats_kernel`.  One pattern per table; the launcher launches table entries and the prepass, nothing else."""
     s = _src("monorec_amd", "csrc", "cost_volume.hip")
-    out = set()
-    macro = _one(r"#define MR_MARCH\(DP_, PIXD_, KFS_\)(.*?)#undef MR_MARCH", s, re.S)
-    body, uses = macro.split("while (0)")
-    macro_forms = re.findall(r"cv_sad_march_kernel<DP_, PIXD_, KFS_, (true|false)>", body)
-    assert sorted(macro_forms) == ["false", "true"]
-    for dp, pixd, kfs in re.findall(r"MR_MARCH\((\d), (true|false), (true|false)\)", uses):
-        for fd in macro_forms:
-            out.add(_bools(f"cv_sad_march_kernel<{dp},{pixd},{kfs},{fd},0>"))
-    for args in re.findall(r"hipLaunchKernelGGL\(\(cv_sad_march_kernel<(\d, (?:true|false), (?:true|false), (?:true|false), (?:true|false))>\)", s):
-        out.add(_bools("cv_sad_march_kernel<" + args.replace(" ", "") + ">"))
-    c = constants()
-    opts = [int(v) for v in re.findall(r"launch_sad<TX, TY, MODE, (\d)>\(k, grid, stream\)", s)]
-    modes = [int(v) for v in re.findall(r"launch_sad_opt<TX, TY, (\d)>\(k, L\.opt, grid, stream\)", s)]
-    assert "launch_cv<CV_TX, CV_TY>(a, L, (hipStream_t)stream)" in s and "hipLaunchKernelGGL((cv_sad_kernel<TX, TY, MODE, OPT>)" in s
-    for m in modes:
-        for o in opts:
-            out.add("cv_sad_kernel<%d,%d,%d,%d>" % (c["tiled_tile"] + (m, o)))
-    popts = [int(v) for v in re.findall(r"hipLaunchKernelGGL\(\(cv_sad_patch_kernel<MODE, (\d)>\)", s)]
-    pmodes = [int(v) for v in re.findall(r"launch_sad_patch<(\d)>\(k, L\.opt, R, grid, lds, stream\)", s)]
-    for m in pmodes:
-        for o in popts:
-            out.add(f"cv_sad_patch_kernel<{m},{o}>")
-    for dd, b8 in re.findall(r"hipLaunchKernelGGL\(\(cv_fuse_reg_kernel<(\d+), (true|false)>\)", s):
-        out.add(_bools(f"cv_fuse_reg_kernel<{dd},{b8}>"))
-    for pf in re.findall(r"hipLaunchKernelGGL\(cv_fuse_kernel<(true|false)>", s):
-        out.add(_bools(f"cv_fuse_kernel<{pf}>"))
-    assert len(re.findall(r"hipLaunchKernelGGL\(cv_kf_stats_kernel,", s)) == 1
-    out.add("cv_kf_stats_kernel")
-    assert len(re.findall(r"hipLaunchKernelGGL\(", s)) == 2 + 2 + 1 + 1 + 4 + 6 + 2        # macro, relaxed pair, prepass, tiled (one templated site), patch, fusion
+    tw, th = constants()["tiled_tile"]
+    tiled = [f"cv_sad_kernel<{tw},{th},{m},{o}>" for m, o in re.findall(r"cv_sad_kernel<CV_TX, CV_TY, (\d), (\d)>", _table("TILED", s))]
+    patch = [f"cv_sad_patch_kernel<{m},{o}>" for m, o in re.findall(r"cv_sad_patch_kernel<(\d), (\d)>", _table("PATCH", s))]
+    assert "cv_sad_march_kernel<DP, PIXD, KFS, FD, RELAXED>}; }" in s          # march_entry<...>() names the instantiation of its own arguments
+    march = [_bools(f"cv_sad_march_kernel<{a}>") for a in re.findall(r"march_entry<(\d(?:, (?:true|false)){4})>\(\)", _table("MARCH", s))]
+    reg = [_bools(f"cv_fuse_reg_kernel<{a}>") for a in re.findall(r"cv_fuse_reg_kernel<(\d+, (?:true|false))>", _table("FUSE_REG", s))]
+    gen = [_bools(f"cv_fuse_kernel<{a}>") for a in re.findall(r"cv_fuse_kernel<(true|false)>", _table("FUSE_GENERIC", s))]
+    out = tiled + patch + march + reg + gen + ["cv_kf_stats_kernel"]
+    assert len(set(out)) == len(out)
+    # the launch sites: the prepass by name, everything else through a table entry (`kernels.`) - no instantiation is named outside the tables
+    sites = re.findall(r"hipLaunchKernelGGL\((\(?\w+)", s)
+    assert sorted(sites) == ["cv_kf_stats_kernel"] + ["kernels"] * 4, sites
     return tuple(sorted(out))
 
 

@@ -1,6 +1,6 @@
 """Host side (no GPU): the launch paths of csrc/cost_volume.hip (tests/cost_volume_paths.py) that tests/test_gpu_cost_volume_paths.py runs.
 The constants the rules rest on parse and are pinned; the restated rule equals the library's own answer (mr_cost_volume_launch_query, the
-function the launchers consume) field by field; every kernel instantiation named at a launch site is run by a case or is on the pinned
+function the launcher consumes) field by field; every kernel instantiation named in the kernel tables is run by a case or is on the pinned
 unreachable list; every case sits on the path it names; every branch inside a path key has a case; every CPU reference runs here."""
 import random
 import re
