@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define MR_ABI_VERSION 23
+#define MR_ABI_VERSION 24
 
 #define MR_COMPUTE_F32  0
 #define MR_COMPUTE_BF16 1
@@ -39,6 +39,10 @@ extern "C" {
 #define MR_MAX_FRAMES  8
 #define MR_MAX_HEADS   4   /* one-channel 3x3 heads per mr_depth_heads_f32 launch (DepthModule has 4 predictors) */
 #define MR_MAX_VOTE_MASKS 8   /* masks voted over by mr_pointcloud_append_f32 / mr_tsdf_frame_f32 (the reference buffers 5) */
+#define MR_TSDF_MAX_FRAMES 8  /* keyframes integrated by one mr_tsdf_integrate_f32 launch */
+#define MR_TSDF_TILE_X 32     /* voxels of one workgroup of mr_tsdf_integrate_f32 - the unit of its frustum culling */
+#define MR_TSDF_TILE_Y 8
+#define MR_TSDF_TILE_Z 4
 
 /* ---- activation codes for mr_conv2d_f32 (epilogue, applied after bias [+ residual]) ---- */
 enum {
@@ -690,6 +694,58 @@ int mr_pointcloud_append_f32(const float* inv_depth, const float* const* static_
 int mr_tsdf_frame_f32(const float* inv_depth, const float* keyframe, const float* const* static_masks, int32_t num_masks,
                       float vote_above, const int32_t* crop, float min_cm, float max_cm, int32_t batch, int32_t height,
                       int32_t width, int16_t* depth, uint8_t* colour, void* stream);
+
+/* ---- TSDF fusion (ABI 24; monorec_amd/tsdf_fusion.py): a dense voxel volume in device memory, the packed keyframes of mr_tsdf_frame_f32
+ * integrated into it, the zero-crossing surface points out.  No reference lines stand behind these: the arithmetic below is the definition.
+ *
+ * The volume has nx x ny x nz voxels, x fastest (idx = (z * ny + y) * nx + x, a 64-bit index): tsdf fp32 (initially 1), weight fp32
+ * (initially 0) and, optionally (colour NULL: none), 4 bytes r g b 0 per voxel (initially 0).  Voxel (x, y, z) lies at
+ * p_a = origin_a + (float)i_a * voxel_size.  `origin`: 3 floats in HOST memory, read during the call.  tsdf / weight need 4-byte,
+ * colour 4-byte alignment; rows that start on a 16-byte boundary are moved with 16-byte accesses.
+ * Null required pointers, nx / ny / nz < 1, nx * ny * nz >= 2^40, voxel_size <= 0 (or NaN): MR_ERR_BAD_ARGUMENT, nothing is launched. */
+int mr_tsdf_volume_reset_f32(float* tsdf, float* weight, uint8_t* colour, int32_t nx, int32_t ny, int32_t nz, void* stream);
+
+/* One keyframe of mr_tsdf_integrate_f32, passed by value in the launch arguments. */
+typedef struct mr_tsdf_view {
+    float m[12];                 /* world -> camera, 3 x 4 row-major (the fp32 inverse of the camera -> world pose, inverted on the host) */
+    float fx, fy, cx, cy;        /* pixel intrinsics of the packed image (after the crop) */
+    const int16_t* depth_cm;     /* height x width, device memory: depth of mr_tsdf_frame_f32 (centimetres, 0 = no depth) */
+    const uint8_t* colour;       /* height x width x 3, device memory; may be NULL when the volume has no colour */
+} mr_tsdf_view;
+
+/* Integrate frames[0 .. num_frames) (HOST array, 1 <= num_frames <= MR_TSDF_MAX_FRAMES), all height x width, into the volume in the order
+ * given.  Every voxel is loaded once, updated by the frames in turn and stored once, and only if a frame updated it: the result equals
+ * num_frames launches of one frame bit for bit.  All fp32, every operation rounded on its own, for voxel (x, y, z) and one frame:
+ *   p_a   = origin_a + (float)i_a * voxel_size
+ *   cam_r = ((m[4r] * p_x + m[4r+1] * p_y) + m[4r+2] * p_z) + m[4r+3]                       skip if cam_2 <= 0
+ *   u = roundf(fx * (cam_0 / cam_2) + cx), v = roundf(fy * (cam_1 / cam_2) + cy)             skip unless 0 <= u < width, 0 <= v < height
+ *   d = (float)depth_cm[v][u] / 100                                                          skip if d <= 0 or d > max_depth_m (+INFINITY: no limit)
+ *   diff = d - cam_2                                                                         skip if diff <= -trunc
+ *   dist = fminf(1, diff / trunc);  w_new = w_old + 1;  tsdf = (tsdf * w_old + dist) / w_new
+ *   colour_c = (uint8)fminf(255, floorf(((float)colour_c * w_old + (float)pixel_c) / w_new + .5))     c = r, g, b
+ *   weight = w_new
+ * A workgroup owns MR_TSDF_TILE_X x _Y x _Z voxels and skips a frame when the tile's bounding sphere lies outside one of the frame's near
+ * and four side planes (prepared here in double, pushed outwards by more than the half pixel of roundf and the fp32 evaluation can
+ * move a voxel; a frame with fx <= 0 or fy <= 0 is never culled): no voxel of such a tile could have passed the cam_2 and image-bounds
+ * tests, so culling changes no result; a tile every frame skips touches no memory.
+ * Besides the cases above: frames NULL, num_frames outside 1 .. MR_TSDF_MAX_FRAMES, a frame without depth_cm, a colour volume with a frame
+ * without colour, height / width < 1, trunc <= 0, NaN max_depth_m: MR_ERR_BAD_ARGUMENT. */
+int mr_tsdf_integrate_f32(float* tsdf, float* weight, uint8_t* colour, int32_t nx, int32_t ny, int32_t nz, const float* origin,
+                          float voxel_size, float trunc, float max_depth_m, const mr_tsdf_view* frames, int32_t num_frames,
+                          int32_t height, int32_t width, void* stream);
+
+/* Surface points at the edge crossings of the grid: for every voxel v and axis a whose neighbour n = v + e_a is inside the volume,
+ * when weight[v] > min_weight, weight[n] > min_weight and (tsdf[v] < 0) != (tsdf[n] < 0):
+ *   s = tsdf[v] / (tsdf[v] - tsdf[n]);  pos_a = (origin_a + (float)i_a * voxel_size) + s * voxel_size, the other two coordinates p of v
+ *   value_c = floorf((float)C_v + s * ((float)C_n - (float)C_v) + .5)                       (0 without a colour volume)
+ * One record of 6 floats x y z red green blue per point, the record of mr_pointcloud_append_f32, in no particular order.  Every
+ * workgroup draws its range of records with one atomicAdd on *cursor (int64 in device memory, set by the caller, normally to 0) and
+ * writes those below capacity_records; *cursor ends advanced by the number of points whatever the capacity.  records NULL: count only
+ * (capacity_records is ignored) - count, allocate exactly, zero the cursor, fill.  cursor NULL, capacity_records < 0, NaN min_weight:
+ * MR_ERR_BAD_ARGUMENT. */
+int mr_tsdf_extract_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                        const float* origin, float voxel_size, float min_weight, float* records, int64_t capacity_records,
+                        int64_t* cursor, void* stream);
 
 /* ---- input pipeline: KittiOdometryDataset.preprocess_image, kitti_odometry_dataset.py:120-134 ------
  *

@@ -88,12 +88,22 @@ class B8ConvDesc(ctypes.Structure):
 
 
 MR_MAX_COPY_SEGMENTS = 24
-MR_ABI_VERSION = 23            # include/monorec_hip.h
+MR_ABI_VERSION = 24            # include/monorec_hip.h
 
 
 class CopySegment(ctypes.Structure):
     """mirror of `mr_copy_segment` (include/monorec_hip.h)."""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
+
+
+MR_TSDF_MAX_FRAMES = 8
+MR_TSDF_TILE = (32, 8, 4)      # MR_TSDF_TILE_X / _Y / _Z: voxels of one workgroup of mr_tsdf_integrate_f32, the unit of its culling
+
+
+class TsdfView(ctypes.Structure):
+    """mirror of `mr_tsdf_view` (include/monorec_hip.h)."""
+    _fields_ = [("m", ctypes.c_float * 12), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("depth_cm", ctypes.c_void_p), ("colour", ctypes.c_void_p)]
 
 
 class LaunchItem(ctypes.Structure):
@@ -259,6 +269,14 @@ ABI = {
     "mr_tsdf_frame_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
                                          ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.c_float, ctypes.c_float,
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_volume_reset_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                ctypes.c_void_p]),
+    "mr_tsdf_integrate_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                             _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.POINTER(TsdfView), ctypes.c_int32,
+                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
+    "mr_tsdf_extract_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                           _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
     "mr_resample_ksize_bilinear": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "mr_resample_coeffs_bilinear": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_void_p]),

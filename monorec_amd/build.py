@@ -22,6 +22,7 @@ SOURCES = [
     ("cost_volume.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("pointcloud.hip", ["-ffp-contract=off"]),
     ("tsdf_export.hip", ["-ffp-contract=off"]),        # depth / colour packing of save_frame_for_tsdf: the reference's roundings, one by one
+    ("tsdf_fusion.hip", ["-ffp-contract=off"]),        # TSDF integration / surface extraction: the roundings of include/monorec_hip.h, one by one
     ("preprocess.hip", ["-ffp-contract=off"]),
     ("eltwise.hip", []),
     ("select.hip", ["-ffp-contract=off"]),          # median scaling: exact masked selection; stage-scaled metric sums

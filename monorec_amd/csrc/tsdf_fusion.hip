@@ -1,0 +1,374 @@
+// TSDF fusion on the device (monorec_amd/tsdf_fusion.py): a dense voxel volume, the packed keyframes of mr_tsdf_frame_f32 integrated
+// into it by running average, the zero-crossing surface points out.  The arithmetic is the one include/monorec_hip.h spells out -
+// all fp32, every operation rounded on its own (compiled with -ffp-contract=off; `/` is the correctly rounded division) - and
+// tests/tsdf_fusion_ref.py restates it in numpy; the GPU tests compare bit for bit.
+//
+//   tsdf_reset_kernel       tsdf = 1, weight = 0, colour = 0
+//   tsdf_integrate_kernel   up to MR_TSDF_MAX_FRAMES keyframes per launch: a voxel is loaded once, updated by the frames in order in
+//                           registers and stored once, and only by a thread one of whose voxels a frame updated
+//   tsdf_extract_kernel     edge crossings as x y z r g b records; with records == nullptr it only counts
+//
+// The integration sweeps the volume: 8 bytes (12 with colour) in and out per voxel and frame BATCH, the depth and colour images are
+// gathered through the caches (a keyframe is a few hundred KB).  Measured kernel time (DESIGN.md section 7, 512 x 512 x 128 voxels,
+// every voxel updated): 61 % of the achievable HBM rate at one frame per launch with colour, 70 % without; each further frame of a
+// launch adds about 0.6 of the one-frame time and no volume traffic.  Shape of the sweep:
+//   * a workgroup of 256 threads owns a tile of 32 x 8 x 4 voxels (MR_TSDF_TILE_X / _Y / _Z), a thread four voxels along x.  The 8
+//     threads of a row move 128 contiguous bytes of tsdf and of weight - one whole cache line each where the row is aligned - and a
+//     wave one z slice of 8 rows.  32 along x is the shortest row that fills a line; y and z are kept small so that the tile's
+//     bounding sphere (radius 16 voxels, nearly all of it the x extent) stays tight for the culling, and so that volumes of a few
+//     dozen voxels per side still spread over many workgroups.
+//   * where a thread's four voxels are all inside the row and start on a 16-byte boundary they are one 16-byte load and store per
+//     array; otherwise (odd nx, the tail of a row, a view that starts off the boundary) scalar accesses.  nx is arbitrary.
+//   * culling: per frame five planes in world space (near and four sides, prepared by the host entry in double and pushed outwards),
+//     tested against the tile's bounding sphere from blockIdx alone, so the test is uniform over the workgroup.  A tile all frames
+//     skip returns before it has touched memory.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/monorec_hip.h"
+
+namespace {
+
+constexpr int TX = MR_TSDF_TILE_X, TY = MR_TSDF_TILE_Y, TZ = MR_TSDF_TILE_Z;
+static_assert(TX == 32 && TY == 8 && TZ == 4, "256 threads, four voxels along x each");
+constexpr long long MAX_VOXELS = 1ll << 40;      // 64-bit voxel indices; the bound keeps idx * 4 bytes and the block counts far from overflow
+
+struct IntegrateArgs {
+    float* tsdf;
+    float* weight;
+    uint8_t* colour;                             // 4 bytes per voxel or null
+    int nx, ny, nz;
+    int tiles_x, tiles_y;
+    float ox, oy, oz, voxel, trunc, max_depth;
+    int num_frames, h, w;
+    float cull_radius;                           // bounding sphere of a tile plus the margin for the fp32 evaluation
+    mr_tsdf_view f[MR_TSDF_MAX_FRAMES];
+    float plane[MR_TSDF_MAX_FRAMES][5][4];       // (n, d) in world space, |n| = 1 or 0 (0: never culls); inside is n . p + d >= 0
+};
+
+__global__ __launch_bounds__(256) void tsdf_reset_kernel(float* __restrict__ tsdf, float* __restrict__ weight, unsigned* __restrict__ colour,
+                                                         long long voxels) {
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < voxels; i += stride) {
+        tsdf[i] = 1.0f;
+        weight[i] = 0.0f;
+        if (colour) colour[i] = 0u;
+    }
+}
+
+__device__ __forceinline__ unsigned blend_byte(unsigned old, unsigned pix, float w_old, float w_new) {
+    const float c = fminf(255.0f, floorf(((float)old * w_old + (float)pix) / w_new + 0.5f));
+    return (unsigned)c;
+}
+
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs a) {
+    const int tile = blockIdx.x;
+    const int bx = tile % a.tiles_x, by = (tile / a.tiles_x) % a.tiles_y, bz = tile / (a.tiles_x * a.tiles_y);
+    // which frames can reach this tile: the centre of the (full) tile against the five planes of each frame
+    const float ccx = a.ox + ((float)(bx * TX) + 0.5f * (TX - 1)) * a.voxel;
+    const float ccy = a.oy + ((float)(by * TY) + 0.5f * (TY - 1)) * a.voxel;
+    const float ccz = a.oz + ((float)(bz * TZ) + 0.5f * (TZ - 1)) * a.voxel;
+    unsigned live = 0;
+    for (int fi = 0; fi < a.num_frames; ++fi) {
+        bool out = false;
+#pragma unroll
+        for (int p = 0; p < 5; ++p) {
+            const float* q = a.plane[fi][p];
+            const float dist = ((q[0] * ccx + q[1] * ccy) + q[2] * ccz) + q[3];
+            out = out || (dist < -a.cull_radius);                      // NaN: not culled
+        }
+        if (!out) live |= 1u << fi;
+    }
+    if (live == 0) return;
+
+    const int tid = threadIdx.x;
+    const int x = bx * TX + (tid & 7) * 4, y = by * TY + ((tid >> 3) & 7), z = bz * TZ + (tid >> 6);
+    if (x >= a.nx || y >= a.ny || z >= a.nz) return;
+    const int n = a.nx - x < 4 ? a.nx - x : 4;
+    const long long idx = ((long long)z * a.ny + y) * a.nx + x;
+    float* tp = a.tsdf + idx;
+    float* wp = a.weight + idx;
+    unsigned* cp = a.colour ? reinterpret_cast<unsigned*>(a.colour) + idx : nullptr;
+    const bool vec = n == 4 && (((uintptr_t)tp | (uintptr_t)wp) & 15) == 0;
+    const bool cvec = n == 4 && ((uintptr_t)cp & 15) == 0;
+
+    float t[4], wgt[4];
+    unsigned col[4] = {0u, 0u, 0u, 0u};
+    if (vec) {
+        const float4 tv = *reinterpret_cast<const float4*>(tp);
+        const float4 wv = *reinterpret_cast<const float4*>(wp);
+        t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
+        wgt[0] = wv.x; wgt[1] = wv.y; wgt[2] = wv.z; wgt[3] = wv.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            t[j] = j < n ? tp[j] : 1.0f;
+            wgt[j] = j < n ? wp[j] : 0.0f;
+        }
+    }
+    if (cp) {
+        if (cvec) {
+            const uint4 cv = *reinterpret_cast<const uint4*>(cp);
+            col[0] = cv.x; col[1] = cv.y; col[2] = cv.z; col[3] = cv.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (j < n) col[j] = cp[j];
+        }
+    }
+
+    const float py = a.oy + (float)y * a.voxel, pz = a.oz + (float)z * a.voxel;
+    const float wf = (float)a.w, hf = (float)a.h;
+    unsigned touched = 0;
+    for (int fi = 0; fi < a.num_frames; ++fi) {
+        if (!(live & (1u << fi))) continue;
+        const mr_tsdf_view& f = a.f[fi];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) continue;
+            const float px = a.ox + (float)(x + j) * a.voxel;
+            const float c0 = ((f.m[0] * px + f.m[1] * py) + f.m[2] * pz) + f.m[3];
+            const float c1 = ((f.m[4] * px + f.m[5] * py) + f.m[6] * pz) + f.m[7];
+            const float c2 = ((f.m[8] * px + f.m[9] * py) + f.m[10] * pz) + f.m[11];
+            if (!(c2 > 0.0f)) continue;
+            const float uf = roundf(f.fx * (c0 / c2) + f.cx);
+            const float vf = roundf(f.fy * (c1 / c2) + f.cy);
+            if (!(uf >= 0.0f && uf < wf && vf >= 0.0f && vf < hf)) continue;
+            const long long pix = (long long)(int)vf * a.w + (int)uf;
+            const float d = (float)f.depth_cm[pix] / 100.0f;
+            if (d <= 0.0f || d > a.max_depth) continue;
+            const float diff = d - c2;
+            if (diff <= -a.trunc) continue;
+            const float dist = fminf(1.0f, diff / a.trunc);
+            const float w_old = wgt[j], w_new = w_old + 1.0f;
+            t[j] = (t[j] * w_old + dist) / w_new;
+            if (cp) {
+                const uint8_t* s = f.colour + pix * 3;
+                const unsigned r = blend_byte(col[j] & 0xffu, s[0], w_old, w_new);
+                const unsigned g = blend_byte((col[j] >> 8) & 0xffu, s[1], w_old, w_new);
+                const unsigned b = blend_byte((col[j] >> 16) & 0xffu, s[2], w_old, w_new);
+                col[j] = r | (g << 8) | (b << 16);
+            }
+            wgt[j] = w_new;
+            touched |= 1u << j;
+        }
+    }
+    if (!touched) return;
+    if (vec) {
+        *reinterpret_cast<float4*>(tp) = make_float4(t[0], t[1], t[2], t[3]);
+        *reinterpret_cast<float4*>(wp) = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (touched & (1u << j)) { tp[j] = t[j]; wp[j] = wgt[j]; }
+    }
+    if (cp) {
+        if (cvec) {
+            *reinterpret_cast<uint4*>(cp) = make_uint4(col[0], col[1], col[2], col[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) if (touched & (1u << j)) cp[j] = col[j];
+        }
+    }
+}
+
+struct ExtractArgs {
+    const float* tsdf;
+    const float* weight;
+    const unsigned* colour;                      // r g b 0 per voxel or null
+    int nx, ny, nz;
+    long long voxels;
+    float ox, oy, oz, voxel, min_weight;
+    float* records;                              // null: count only
+    long long capacity;
+    unsigned long long* cursor;
+};
+
+__device__ __forceinline__ float mix_byte(unsigned cv, unsigned cn, float s) {
+    const float fv = (float)cv, fn = (float)cn;
+    return floorf(fv + s * (fn - fv) + 0.5f);
+}
+
+__global__ __launch_bounds__(256) void tsdf_extract_kernel(const ExtractArgs a) {
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long i = (long long)blockIdx.x * 256 + tid;
+    const long long plane = (long long)a.nx * a.ny;
+    int x = 0, y = 0, z = 0, hits = 0;
+    float tv = 0.f, tn[3] = {0.f, 0.f, 0.f};
+    long long step[3] = {1, a.nx, plane};
+    if (i < a.voxels) {
+        z = (int)(i / plane);
+        const long long r = i - (long long)z * plane;
+        y = (int)(r / a.nx);
+        x = (int)(r - (long long)y * a.nx);
+        if (a.weight[i] > a.min_weight) {
+            tv = a.tsdf[i];
+            const bool inside[3] = {x + 1 < a.nx, y + 1 < a.ny, z + 1 < a.nz};
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                if (!inside[e] || !(a.weight[i + step[e]] > a.min_weight)) continue;
+                tn[e] = a.tsdf[i + step[e]];
+                if ((tv < 0.0f) != (tn[e] < 0.0f)) hits |= 1 << e;
+            }
+        }
+    }
+    const int mine = __popc(hits);
+    // exclusive prefix of `mine` over the workgroup: shuffles within the wave, wave totals through LDS
+    int incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int before = incl - mine, total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const int v = wave_tot[w]; if (w < wave) before += v; total += v; }
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);       // one per workgroup
+    if (!a.records) return;
+    __syncthreads();
+    if (!hits) return;
+    long long rec = (long long)s_base + before;
+    const float p[3] = {a.ox + (float)x * a.voxel, a.oy + (float)y * a.voxel, a.oz + (float)z * a.voxel};
+    const unsigned cv = a.colour ? a.colour[i] : 0u;
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        if (!(hits & (1 << e))) continue;
+        if (rec < a.capacity) {
+            const float s = tv / (tv - tn[e]);
+            float* o = a.records + rec * 6;
+            o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
+            o[e] = p[e] + s * a.voxel;
+            const unsigned cn = a.colour ? a.colour[i + step[e]] : 0u;
+            o[3] = mix_byte(cv & 0xffu, cn & 0xffu, s);
+            o[4] = mix_byte((cv >> 8) & 0xffu, (cn >> 8) & 0xffu, s);
+            o[5] = mix_byte((cv >> 16) & 0xffu, (cn >> 16) & 0xffu, s);
+        }
+        ++rec;
+    }
+}
+
+long long voxel_count(int nx, int ny, int nz) {                  // MAX_VOXELS for anything at or beyond the bound, without overflow
+    const long long xy = (long long)nx * ny;                     // < 2^62
+    if (xy >= MAX_VOXELS || nz > MAX_VOXELS / xy) return MAX_VOXELS;
+    return xy * nz;
+}
+
+bool bad_volume(const void* tsdf, const void* weight, int nx, int ny, int nz) {
+    if (!tsdf || !weight || nx < 1 || ny < 1 || nz < 1) return true;
+    if (((uintptr_t)tsdf | (uintptr_t)weight) & 3) return true;
+    return voxel_count(nx, ny, nz) >= MAX_VOXELS;
+}
+
+// The near and four side planes of one view in world space, in double.  A voxel can pass the kernel's cam_2 > 0 and image-bounds
+// tests only if its camera-space point c = A p + t has c_2 > 0 and -0.5 <= fx c_0 / c_2 + cx < w - 0.5 (likewise v): the intersection
+// of five half spaces n_c . c >= 0 through the camera centre.  They are widened by `slack` pixels beyond the half pixel of roundf, and
+// the kernel culls a tile only when its sphere is `margin` further out than that (see mr_tsdf_integrate_f32): more than the fp32
+// evaluation of c, of u and v and of the plane test itself can move a point.  Anything doubtful (non-positive focal lengths, A far
+// from a rotation, non-finite numbers) leaves the plane at zero, which never culls.
+void view_planes(const mr_tsdf_view& f, int h, int w, float out[5][4]) {
+    for (int p = 0; p < 5; ++p) for (int k = 0; k < 4; ++k) out[p][k] = 0.0f;
+    if (!(f.fx > 0.0f) || !(f.fy > 0.0f)) return;
+    double rows[3];
+    for (int r = 0; r < 3; ++r) {
+        rows[r] = sqrt((double)f.m[4 * r] * f.m[4 * r] + (double)f.m[4 * r + 1] * f.m[4 * r + 1] + (double)f.m[4 * r + 2] * f.m[4 * r + 2]);
+        if (!(rows[r] > 0.5 && rows[r] < 2.0)) return;
+    }
+    const double slack_u = 1.0 + 1e-6 * (fabs((double)f.cx) + w + f.fx), slack_v = 1.0 + 1e-6 * (fabs((double)f.cy) + h + f.fy);
+    const double nc[5][3] = {
+        {0.0, 0.0, 1.0},                                                          // c_2 >= 0
+        {(double)f.fx, 0.0, (double)f.cx + 0.5 + slack_u},                        // u >= -0.5 - slack
+        {-(double)f.fx, 0.0, (double)w - 0.5 + slack_u - (double)f.cx},           // u <= w - 0.5 + slack
+        {0.0, (double)f.fy, (double)f.cy + 0.5 + slack_v},
+        {0.0, -(double)f.fy, (double)h - 0.5 + slack_v - (double)f.cy},
+    };
+    for (int p = 0; p < 5; ++p) {
+        double nw[3], d = 0.0;
+        for (int k = 0; k < 3; ++k) nw[k] = nc[p][0] * f.m[k] + nc[p][1] * f.m[4 + k] + nc[p][2] * f.m[8 + k];
+        for (int r = 0; r < 3; ++r) d += nc[p][r] * f.m[4 * r + 3];
+        const double len = sqrt(nw[0] * nw[0] + nw[1] * nw[1] + nw[2] * nw[2]);
+        const double lc = sqrt(nc[p][0] * nc[p][0] + nc[p][1] * nc[p][1] + nc[p][2] * nc[p][2]);
+        if (!(len > 0.25 * lc) || !isfinite(len) || !isfinite(d)) continue;      // (A within [0.5, 2] per row, yet nearly singular along n_c)
+        out[p][0] = (float)(nw[0] / len); out[p][1] = (float)(nw[1] / len); out[p][2] = (float)(nw[2] / len); out[p][3] = (float)(d / len);
+    }
+}
+
+}  // namespace
+
+extern "C" int mr_tsdf_volume_reset_f32(float* tsdf, float* weight, uint8_t* colour, int32_t nx, int32_t ny, int32_t nz, void* stream) {
+    if (bad_volume(tsdf, weight, nx, ny, nz) || ((uintptr_t)colour & 3)) return MR_ERR_BAD_ARGUMENT;
+    const long long voxels = voxel_count(nx, ny, nz);
+    long long blocks = (voxels + 255) / 256;
+    if (blocks > 65536) blocks = 65536;                          // grid-stride beyond that
+    hipLaunchKernelGGL(tsdf_reset_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tsdf, weight,
+                       reinterpret_cast<unsigned*>(colour), voxels);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_integrate_f32(float* tsdf, float* weight, uint8_t* colour, int32_t nx, int32_t ny, int32_t nz, const float* origin,
+                                     float voxel_size, float trunc, float max_depth_m, const mr_tsdf_view* frames, int32_t num_frames,
+                                     int32_t height, int32_t width, void* stream) {
+    if (bad_volume(tsdf, weight, nx, ny, nz) || ((uintptr_t)colour & 3) || !origin || !frames) return MR_ERR_BAD_ARGUMENT;
+    if (num_frames < 1 || num_frames > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return MR_ERR_BAD_ARGUMENT;
+    if (!(voxel_size > 0.0f) || !(trunc > 0.0f) || max_depth_m != max_depth_m) return MR_ERR_BAD_ARGUMENT;
+    if ((long long)height * width * 3 >= (1ll << 40)) return MR_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < num_frames; ++i)
+        if (!frames[i].depth_cm || (colour && !frames[i].colour)) return MR_ERR_BAD_ARGUMENT;
+    IntegrateArgs a;
+    a.tsdf = tsdf; a.weight = weight; a.colour = colour;
+    a.nx = nx; a.ny = ny; a.nz = nz;
+    a.tiles_x = (nx + TX - 1) / TX; a.tiles_y = (ny + TY - 1) / TY;
+    const long long tiles = (long long)a.tiles_x * a.tiles_y * ((nz + TZ - 1) / TZ);
+    if (tiles > 0x7fffffffLL) return MR_ERR_BAD_ARGUMENT;
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
+    a.voxel = voxel_size; a.trunc = trunc; a.max_depth = max_depth_m;
+    a.num_frames = num_frames; a.h = height; a.w = width;
+    // sphere round the voxel CENTRES of a full tile, plus what fp32 can move: the tile centre, a voxel's camera-space point and the plane
+    // test are each a handful of roundings of numbers no larger than `reach` (the far corner of the volume plus a camera's translation),
+    // so 64 ulp of it (4e-6) is several times their sum; a thousandth of a voxel covers volumes at the origin
+    const double v = (double)voxel_size;
+    double reach = 0.0, corner = 0.0;
+    const int dims[3] = {nx, ny, nz};
+    for (int k = 0; k < 3; ++k) {
+        const double far_k = fmax(fabs((double)origin[k]), fabs((double)origin[k] + (dims[k] + TX) * v));
+        corner += far_k * far_k;
+    }
+    corner = sqrt(corner);
+    for (int i = 0; i < num_frames; ++i) {
+        a.f[i] = frames[i];
+        view_planes(frames[i], height, width, a.plane[i]);
+        const float* m = frames[i].m;
+        reach = fmax(reach, 2.0 * corner + sqrt((double)m[3] * m[3] + (double)m[7] * m[7] + (double)m[11] * m[11]));
+    }
+    for (int i = num_frames; i < MR_TSDF_MAX_FRAMES; ++i) {
+        a.f[i] = frames[0];
+        for (int p = 0; p < 5; ++p) for (int k = 0; k < 4; ++k) a.plane[i][p][k] = 0.0f;
+    }
+    const double radius = 0.5 * v * sqrt((double)((TX - 1) * (TX - 1) + (TY - 1) * (TY - 1) + (TZ - 1) * (TZ - 1)));
+    const double cull = radius + 1e-3 * v + 64.0 * 5.97e-8 * reach;
+    a.cull_radius = isfinite(cull) ? nextafterf((float)cull, INFINITY) : INFINITY;       // infinite: `dist < -inf` never holds
+    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_extract_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                                   const float* origin, float voxel_size, float min_weight, float* records, int64_t capacity_records,
+                                   int64_t* cursor, void* stream) {
+    if (bad_volume(tsdf, weight, nx, ny, nz) || ((uintptr_t)colour & 3) || !origin || !cursor) return MR_ERR_BAD_ARGUMENT;
+    const long long voxels = voxel_count(nx, ny, nz);
+    if (!(voxel_size > 0.0f) || min_weight != min_weight || (records && capacity_records < 0)) return MR_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)records & 3) || ((uintptr_t)cursor & 7)) return MR_ERR_BAD_ARGUMENT;
+    const long long blocks = (voxels + 255) / 256;
+    if (blocks > 0x7fffffffLL) return MR_ERR_BAD_ARGUMENT;
+    ExtractArgs a;
+    a.tsdf = tsdf; a.weight = weight; a.colour = reinterpret_cast<const unsigned*>(colour);
+    a.nx = nx; a.ny = ny; a.nz = nz; a.voxels = voxels;
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.voxel = voxel_size; a.min_weight = min_weight;
+    a.records = records; a.capacity = records ? capacity_records : 0;
+    a.cursor = reinterpret_cast<unsigned long long*>(cursor);
+    hipLaunchKernelGGL(tsdf_extract_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}

@@ -300,6 +300,12 @@ class KittiOdometryDataset:
                 return data, mask
         return data, self._target(dataset_index, key)
 
+    def keyframe_geometry(self, index):
+        """(keyframe_pose, keyframe_intrinsics) of sample `index`, the host matrices `__getitem__` hands out, without decoding a frame
+        (monorec_amd.tsdf_fusion sizes its volume from the poses before the model runs)."""
+        dataset_index, key, _ = self._sample_keys(index)
+        return torch.tensor(self._datasets[dataset_index].poses[key], dtype=torch.float32), self._intrinsics[dataset_index]
+
     def close(self):
         for cache in self._caches.values():
             cache.close()

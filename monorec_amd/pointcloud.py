@@ -42,6 +42,19 @@ def static_mask(cv_mask, mask_fill=32, threshold=0.1):
     return out
 
 
+def write_ply(file, data):
+    """utils/ply_utils.py:18-32: the header and the binary little-endian float records x y z red green blue.  `data`: a flat
+    `array('f')` or fp32 numpy array of six floats per vertex (also what monorec_amd.tsdf_fusion writes its surface points with)."""
+    fields = ("x", "y", "z", "red", "green", "blue")
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {len(data) // 6}"]
+    lines += [f"property float {name}" for name in fields] + ["end_header"]
+    file.write(("\n".join(lines) + "\n").encode("ascii"))
+    if isinstance(data, array):
+        data.tofile(file)
+    else:
+        file.write(data.tobytes())
+
+
 class PLYSaver(torch.nn.Module):
     """utils/ply_utils.py:8-53 with device-resident records."""
 
@@ -126,12 +139,7 @@ class PLYSaver(torch.nn.Module):
 
     def save(self, file):
         """utils/ply_utils.py:18-32 (same header, binary little-endian float records)."""
-        data = self.data
-        fields = ("x", "y", "z", "red", "green", "blue")
-        lines = ["ply", "format binary_little_endian 1.0", f"element vertex {len(data) // 6}"]
-        lines += [f"property float {name}" for name in fields] + ["end_header"]
-        file.write(("\n".join(lines) + "\n").encode("ascii"))
-        data.tofile(file)
+        write_ply(file, self.data)
 
 
 class PointcloudBuilder:

@@ -345,108 +345,141 @@ class TSDFExporter:
 
 
 # ------------------------------------------------------------------------------------------ the runner
+class KeyframeStream:
+    """The keyframe loop of `run`, shared with monorec_amd.tsdf_fusion.run: builds model and dataset from a config of
+    create_pointcloud.py's shape unless they are handed in, plans the window (`plan_shard`), checks that the model keeps enough slots
+    in flight for the vote, and `run(emit)` drives the pipelined loop (prepare / submit / synchronize), calling
+    `emit(number, entry, masks)` once per exported keyframe in export order: `entry` holds keyframe, depth (views of the model's
+    resident buffers, valid until the next submit), pose, intrinsics, sequence, image_id; `masks` the static masks to vote over, or None."""
+
+    def __init__(self, config, model=None, dataset=None, shard=(0, 1), device="cuda:0", who="monorec_amd.tsdf_export"):
+        from .pointcloud import _dataset_class
+        self.who = who
+        rank, world = int(shard[0]), int(shard[1])
+        self.rank, self.world = rank, world
+        self.use_mask = use_mask = bool(config.get("use_mask", True))
+        plan_shard(0, use_mask, rank, world)                                # a bad shard is reported before anything is built
+        if model is None and config["arch"]["type"] != "MonoRecModel":
+            raise ValueError(f"{who}: arch.type {config['arch']['type']!r} is not MonoRecModel")
+        if dataset is None:
+            dataset_class = _dataset_class(config["data_set"]["type"])
+        if model is None:
+            from .model import MonoRecModel
+            args = dict(config["arch"].get("args", {}))
+            if use_mask:
+                args.setdefault("hip_in_flight", 6)
+            model = MonoRecModel(**args).to(device)
+        device = next(model.parameters()).device
+        if dataset is None:
+            dataset = dataset_class(**dict(config["data_set"]["args"], device=device))
+        model.eval()
+        self.model, self.dataset, self.device = model, dataset, device
+        self.start, end = int(config.get("start", 0)), int(config.get("end", -1))
+        self.window = max(0, (len(dataset) if end == -1 else end) - self.start)
+        self.plan = plan_shard(self.window, use_mask, rank, world)
+        halo = self.plan["halo"]
+        self.slots = int(getattr(model, "hip_in_flight", 1))
+        # keyframe e is packed when keyframe e + halo has been collected, and that must come before submit number e + slots, which reuses its
+        # slot: with P forwards pending the collect of e + halo precedes submit e + halo + P, so P <= slots - halo
+        self.depth_in_flight = self.slots - halo
+        if self.depth_in_flight < 1:
+            raise ValueError(f"{who}: use_mask keeps a keyframe's outputs for {halo} more keyframes; the model needs "
+                             f"hip_in_flight >= {halo + 1} (has {self.slots})")
+        self.height, self.width = dataset.target_image_size
+        self.crop = config.get("roi", None)
+        self.intrinsics = None                                              # keyframe_intrinsics of the first item run() has loaded
+
+    def export_items(self):
+        """Dataset indices of the keyframes this rank exports, in export order."""
+        lo, hi = self.plan["exports"]
+        return [self.start + e + self.plan["halo"] for e in range(lo, hi)]
+
+    def run(self, emit):
+        import collections
+        from .kitti import DeviceLoader
+        from .pointcloud import static_mask
+        model, plan, slots, use_mask = self.model, self.plan, self.slots, self.use_mask
+        first, last = plan["items"]
+        loader = DeviceLoader(self.dataset, batch_size=1, start=self.start + first, end=self.start + last) if last > first else ()
+        pending, buffer = collections.deque(), []
+        state = {"submitted": 0, "exported": 0}
+
+        def export(entry, masks):
+            # the submit that overwrites this keyframe's resident outputs is number entry.item + slots: it must not have happened yet
+            if state["submitted"] > entry["item"] + slots:
+                raise RuntimeError(f"{self.who}: a buffered keyframe's slot was reused before its pack launch (internal)")
+            number = plan["exports"][0] + state["exported"]
+            state["exported"] += 1
+            emit(number, entry, masks)
+
+        def collect():
+            item, data, handle = pending.popleft()
+            out = handle.synchronize()                                  # the host waits: no blocked wait packet on the stream
+            entry = dict(item=item, keyframe=data["keyframe"], depth=out["result"], pose=data["keyframe_pose"],
+                         intrinsics=data["keyframe_intrinsics"], sequence=data.get("sequence"), image_id=data.get("image_id"))
+            if not use_mask:
+                export(entry, None)
+                return
+            cv_mask = out["cv_mask"] if "cv_mask" in out else out["result"].new_zeros(out["result"].shape)
+            entry["mask"] = static_mask(cv_mask, 32)                    # create_pointcloud.py:76-77; an output of its own, not a view
+            buffer.append(entry)
+            if len(buffer) >= BUFFER_LENGTH:
+                export(buffer[BUFFER_LENGTH // 2], [e["mask"] for e in buffer])
+                del buffer[0]
+
+        with torch.no_grad():
+            for item, (data, _) in enumerate(loader):
+                if self.intrinsics is None:
+                    self.intrinsics = data["keyframe_intrinsics"][0]
+                token = model.prepare(data)                             # pose algebra while the device is busy
+                while len(pending) >= self.depth_in_flight:
+                    collect()
+                pending.append((item, data, model.submit(data, token)))
+                state["submitted"] += 1
+            while pending:
+                collect()
+        assert state["exported"] == plan["exports"][1] - plan["exports"][0]
+        return state["exported"]
+
+
 def run(config, model=None, dataset=None, shard=(0, 1), device="cuda:0", export=True):
     """Export the keyframes of a config of create_pointcloud.py's shape (configs/test/pointcloud_monorec*.json): `data_set` -> device
     dataset windowed by `start` / `end`, `arch` -> MonoRecModel, `roi` -> the crop, `min_d` / `max_d` -> the thresholds (absent: none),
     `use_mask` -> the 5-keyframe vote, `output_dir` -> the directory.  Optional keys: `export_ring`, `export_workers`,
     `png_compress_level`.  `model` / `dataset`: use these instead of building them.
 
-    The loop is pipelined (prepare / submit / synchronize with the model's `hip_in_flight`).  The outputs of submit() are views of the
-    slot's resident buffers; nothing is cloned but the static masks (outputs of their own launch): the pack launch of a keyframe is
-    enqueued before the submit that reuses its slot.  With `use_mask` a keyframe is exported two collects after its own, so two slots
-    fewer are kept in flight (a model built here gets `hip_in_flight` 6 for that reason, unless `arch.args` says otherwise; a model
-    handed in needs at least 3).
+    The loop (KeyframeStream) is pipelined (prepare / submit / synchronize with the model's `hip_in_flight`).  The outputs of submit() are
+    views of the slot's resident buffers; nothing is cloned but the static masks (outputs of their own launch): the pack launch of a
+    keyframe is enqueued before the submit that reuses its slot.  With `use_mask` a keyframe is exported two collects after its own, so
+    two slots fewer are kept in flight (a model built here gets `hip_in_flight` 6 for that reason, unless `arch.args` says otherwise; a
+    model handed in needs at least 3).
 
     `shard=(rank, world)`: the exported frames 0 .. N-1 are split into contiguous ranges; a rank runs the two extra keyframes either side
     its votes need and writes only its own files, rank 0 also `camera-intrinsics.txt`; `frames.json` is merged.  The union of the shards
     is the unsharded directory, byte for byte.  `export=False` runs the same loop without `add()` (the measurement of DESIGN.md section 7).
     Returns the number of frames this rank wrote."""
-    import collections
-    from .kitti import DeviceLoader
-    from .pointcloud import _dataset_class, static_mask
-    rank, world = int(shard[0]), int(shard[1])
-    use_mask = bool(config.get("use_mask", True))
-    plan_shard(0, use_mask, rank, world)                                # a bad shard is reported before anything is built
-    if model is None and config["arch"]["type"] != "MonoRecModel":
-        raise ValueError(f"monorec_amd.tsdf_export: arch.type {config['arch']['type']!r} is not MonoRecModel")
-    if dataset is None:
-        dataset_class = _dataset_class(config["data_set"]["type"])
-    if model is None:
-        from .model import MonoRecModel
-        args = dict(config["arch"].get("args", {}))
-        if use_mask:
-            args.setdefault("hip_in_flight", 6)
-        model = MonoRecModel(**args).to(device)
-    device = next(model.parameters()).device
-    if dataset is None:
-        dataset = dataset_class(**dict(config["data_set"]["args"], device=device))
-    model.eval()
-    start, end = int(config.get("start", 0)), int(config.get("end", -1))
-    window = max(0, (len(dataset) if end == -1 else end) - start)
-    plan = plan_shard(window, use_mask, rank, world)
-    first, last = plan["items"]
-    halo = plan["halo"]
-    slots = int(getattr(model, "hip_in_flight", 1))
-    # keyframe e is packed when keyframe e + halo has been collected, and that must come before submit number e + slots, which reuses its
-    # slot: with P forwards pending the collect of e + halo precedes submit e + halo + P, so P <= slots - halo
-    depth_in_flight = slots - halo
-    if depth_in_flight < 1:
-        raise ValueError(f"monorec_amd.tsdf_export: use_mask keeps a keyframe's outputs for {halo} more keyframes; the model needs "
-                         f"hip_in_flight >= {halo + 1} (has {slots})")
-    height, width = dataset.target_image_size
-    crop = config.get("roi", None)
+    stream = KeyframeStream(config, model, dataset, shard, device)
+    crop = stream.crop
     out_dir = config.get("output_dir", "saved")
     os.makedirs(out_dir, exist_ok=True)
     exporter = None
     if export:
-        exporter = TSDFExporter(out_dir, height, width, crop=crop, min_distance=config.get("min_d", None), max_distance=config.get("max_d", None),
-                                ring=int(config.get("export_ring", 8)), workers=int(config.get("export_workers", 8)),
-                                png_compress_level=config.get("png_compress_level", None), merge_manifest=world > 1)
-    loader = DeviceLoader(dataset, batch_size=1, start=start + first, end=start + last) if last > first else ()
-    pending, buffer = collections.deque(), []
-    state = {"submitted": 0, "exported": 0, "intrinsics": None}
+        exporter = TSDFExporter(out_dir, stream.height, stream.width, crop=crop, min_distance=config.get("min_d", None),
+                                max_distance=config.get("max_d", None), ring=int(config.get("export_ring", 8)),
+                                workers=int(config.get("export_workers", 8)), png_compress_level=config.get("png_compress_level", None),
+                                merge_manifest=stream.world > 1)
 
-    def emit(entry, masks):
-        # the submit that overwrites this keyframe's resident outputs is number entry.item + slots: it must not have happened yet
-        if state["submitted"] > entry["item"] + slots:
-            raise RuntimeError("monorec_amd.tsdf_export: a buffered keyframe's slot was reused before its pack launch (internal)")
-        number = plan["exports"][0] + state["exported"]
-        state["exported"] += 1
+    def emit(number, entry, masks):
         if exporter is not None:
             exporter.add(number, entry["keyframe"], entry["depth"], entry["pose"], static_masks=masks, min_hits=1,
                          sequence=entry["sequence"], image_id=entry["image_id"])
 
-    def collect():
-        item, data, handle = pending.popleft()
-        out = handle.synchronize()                                  # the host waits: no blocked wait packet on the stream
-        entry = dict(item=item, keyframe=data["keyframe"], depth=out["result"], pose=data["keyframe_pose"],
-                     sequence=data.get("sequence"), image_id=data.get("image_id"))
-        if not use_mask:
-            emit(entry, None)
-            return
-        cv_mask = out["cv_mask"] if "cv_mask" in out else out["result"].new_zeros(out["result"].shape)
-        entry["mask"] = static_mask(cv_mask, 32)                    # create_pointcloud.py:76-77; an output of its own, not a view
-        buffer.append(entry)
-        if len(buffer) >= BUFFER_LENGTH:
-            emit(buffer[BUFFER_LENGTH // 2], [e["mask"] for e in buffer])
-            del buffer[0]
-
     try:
-        with torch.no_grad():
-            for item, (data, _) in enumerate(loader):
-                if state["intrinsics"] is None:
-                    state["intrinsics"] = data["keyframe_intrinsics"][0]
-                token = model.prepare(data)                         # pose algebra while the device is busy
-                while len(pending) >= depth_in_flight:
-                    collect()
-                pending.append((item, data, model.submit(data, token)))
-                state["submitted"] += 1
-            while pending:
-                collect()
-        if rank == 0 and window > 0 and export:
-            k = state["intrinsics"]
+        exported = stream.run(emit)
+        if stream.rank == 0 and stream.window > 0 and export:
+            k = stream.intrinsics
             if k is None:                                           # rank 0 ran nothing (fewer exports than ranks, or none at all)
-                k = dataset[start][0]["keyframe_intrinsics"]
+                k = stream.dataset[stream.start][0]["keyframe_intrinsics"]
             save_intrinsics_for_tsdf(out_dir, k, crop=crop)
     except BaseException:
         if exporter is not None:
@@ -457,16 +490,15 @@ def run(config, model=None, dataset=None, shard=(0, 1), device="cuda:0", export=
         raise
     if exporter is not None:
         exporter.close()
-    assert state["exported"] == plan["exports"][1] - plan["exports"][0]
-    return state["exported"]
+    return exported
 
 
-def load_config(argv=None):
+def load_config(argv=None, prog="python -m monorec_amd.tsdf_export",
+                description="MonoRec keyframes as TSDF-fusion input (frame-%%06d.color.jpg / .depth.png / .pose.txt)"):
     """The command line of create_pointcloud.py:108-119 (utils/parse_config.py:21-32: with --resume the config.json beside the
     checkpoint is read first and --config updates it).  Returns (config, device)."""
     import argparse
-    parser = argparse.ArgumentParser(prog="python -m monorec_amd.tsdf_export",
-                                     description="MonoRec keyframes as TSDF-fusion input (frame-%%06d.color.jpg / .depth.png / .pose.txt)")
+    parser = argparse.ArgumentParser(prog=prog, description=description)
     parser.add_argument("-c", "--config", default=None, type=str, help="config file path")
     parser.add_argument("-r", "--resume", default=None, type=str, help="checkpoint; its folder's config.json is the base config")
     parser.add_argument("-d", "--device", default="cuda:0", type=str, help="torch device (default: cuda:0)")

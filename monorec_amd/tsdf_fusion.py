@@ -1,0 +1,463 @@
+"""TSDF fusion on the MI355X: the keyframes `tsdf_export` packs, integrated into a dense voxel volume in device memory, and the
+surface points at its zero crossings - the step the export's files were written for, without the files.
+
+    from monorec_amd.tsdf_fusion import TSDFVolume, bounds_from_frusta, fuse_directory, run
+    python -m monorec_amd.tsdf_fusion --config configs/test/pointcloud_monorec.json
+
+`TSDFVolume` owns three device arrays, x fastest (`idx = (z * ny + y) * nx + x`): `tsdf` fp32 (1 = far in front of any surface),
+`weight` fp32 (number of keyframes that saw the voxel) and optionally `colour` (r, g, b, 0 bytes).  `integrate()` is one launch
+(`mr_tsdf_integrate_f32`) per up to 8 keyframes: int16 centimetre depth and interleaved byte colour exactly as `mr_tsdf_frame_f32` /
+`tsdf_export.pack_frames` leave them, a camera -> world pose (inverted on the host in fp32) and the pixel intrinsics.  The
+arithmetic - a running average of the truncated signed distance along the camera's z axis - is written out operation by operation in
+include/monorec_hip.h and restated in numpy by tests/tsdf_fusion_ref.py; the device result equals it bit for bit.  `extract()` returns
+the points where an edge of the grid crosses zero between two seen voxels (`mr_tsdf_extract_f32`: count, then fill), as the x y z r g b
+records `pointcloud.PLYSaver` writes.  There is no CPU fallback: CPU tensors raise.
+
+`run(config)` takes the configs of `pointcloud.run` / `tsdf_export.run` and drives the same pipelined loop
+(`tsdf_export.KeyframeStream`): per keyframe one pack launch into a staging slot on the device, per `fuse_batch` keyframes one
+integrate launch on the same stream; nothing is copied to the host before the surface is written.
+
+Not here: a triangle mesh (marching cubes over the saved volume - `save()` writes an .npz a mesher elsewhere can read); sparse or
+hashed volumes (the volume is dense, `max_bytes` bounds it); a cap on the weight; fusing across ranks (`run` is single-process)."""
+import ctypes
+import math
+import os
+import re
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import tsdf_export as tx
+from .pointcloud import write_ply
+
+MAX_FRAMES = _lib.MR_TSDF_MAX_FRAMES          # keyframes per integrate launch
+TILE = _lib.MR_TSDF_TILE                      # (x, y, z) voxels of one workgroup of the integrate kernel: the unit of its frustum culling
+
+
+def _need_cuda(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"monorec_amd.tsdf_fusion: {what} must be a CUDA (HIP) tensor - there is no CPU fallback")
+
+
+def _matrix(m, what):
+    """A 4 x 4 (or 3 x 3 / 3 x 4) matrix from anywhere as fp32 on the host."""
+    m = torch.as_tensor(m).detach().to("cpu", torch.float32)
+    if m.dim() != 2:
+        raise ValueError(f"{what}: expected one matrix, got shape {tuple(m.shape)}")
+    return m
+
+
+# ------------------------------------------------------------------------------------------ geometry on the host
+def bounds_from_frusta(cam_to_world_list, intrinsics, height, width, max_depth_m, voxel_size=0.1):
+    """The axis-aligned box, in double on the host, of every camera centre and of the four image-corner rays at depth `max_depth_m`
+    (corners of the pixel grid's outline, (-.5, -.5) .. (width - .5, height - .5): what rounds into the image) - it contains every
+    point a keyframe can see within `max_depth_m`.  `intrinsics`: one matrix, or one per pose (a list or a stacked array).  Rounded
+    outwards to whole multiples of `voxel_size`.
+    Returns ((x0, y0, z0), (x1, y1, z1))."""
+    if isinstance(intrinsics, (list, tuple)):
+        intrinsics = np.stack([np.asarray(torch.as_tensor(k).detach().cpu().numpy(), dtype=np.float64) for k in intrinsics])
+    ks = np.asarray(torch.as_tensor(intrinsics).detach().cpu().numpy(), dtype=np.float64)
+    ks = ks.reshape(-1, ks.shape[-2], ks.shape[-1])
+    poses = list(cam_to_world_list)
+    if not poses:
+        raise ValueError("bounds_from_frusta: no poses")
+    if ks.shape[0] not in (1, len(poses)):
+        raise ValueError(f"bounds_from_frusta: {len(poses)} poses but {ks.shape[0]} intrinsics (one, or one per pose)")
+    depth, voxel = float(max_depth_m), float(voxel_size)
+    if not (depth > 0 and math.isfinite(depth)) or not voxel > 0:
+        raise ValueError("bounds_from_frusta: max_depth_m must be positive and finite, voxel_size positive")
+    points = []
+    for i, pose in enumerate(poses):
+        k = ks[i if ks.shape[0] > 1 else 0]
+        fx, fy, cx, cy = k[0, 0], k[1, 1], k[0, 2], k[1, 2]
+        corners = np.array([[(u - cx) / fx * depth, (v - cy) / fy * depth, depth, 1.0]
+                            for u in (-0.5, width - 0.5) for v in (-0.5, height - 0.5)] + [[0.0, 0.0, 0.0, 1.0]])
+        t = np.asarray(torch.as_tensor(pose).detach().cpu().numpy(), dtype=np.float64).reshape(4, 4)
+        points.append((corners @ t.T)[:, :3])
+    points = np.concatenate(points)
+    lo = np.floor(points.min(axis=0) / voxel) * voxel
+    hi = np.ceil(points.max(axis=0) / voxel) * voxel
+    return tuple(float(v) for v in lo), tuple(float(v) for v in hi)
+
+
+def dims_of_bounds(bounds, voxel_size):
+    """Voxels per axis whose points `lo + i * voxel_size` cover [lo, hi]: `round-up((hi - lo) / voxel_size) + 1`."""
+    lo, hi = (np.asarray(b, dtype=np.float64) for b in bounds)
+    if lo.shape != (3,) or hi.shape != (3,) or not np.all(hi >= lo):
+        raise ValueError(f"bounds {bounds}: expected ((x0, y0, z0), (x1, y1, z1)) with hi >= lo")
+    return tuple(int(math.ceil(float(d) / float(voxel_size) - 1e-9)) + 1 for d in hi - lo)
+
+
+def volume_bytes(dims, colour=True):
+    return int(dims[0]) * int(dims[1]) * int(dims[2]) * (12 if colour else 8)
+
+
+# ------------------------------------------------------------------------------------------ the volume
+class TSDFVolume:
+    """A dense TSDF volume on the device.  Give `bounds` = ((x0, y0, z0), (x1, y1, z1)) - e.g. from `bounds_from_frusta` - or `origin`
+    and `dims` = (nx, ny, nz); `voxel_size` in metres; `trunc` (default 5 voxels) the truncation distance.  A volume above `max_bytes`
+    raises a ValueError that names the voxel size that would fit.  `storage` = (tsdf, weight, colour | None): use these device tensors
+    (flat, of nx * ny * nz elements / x 4 bytes) instead of allocating - they are reset too."""
+
+    def __init__(self, bounds=None, voxel_size=0.1, trunc=None, colour=True, device="cuda:0", max_bytes=8 << 30, origin=None, dims=None,
+                 storage=None):
+        voxel_size = float(voxel_size)
+        if not voxel_size > 0:
+            raise ValueError(f"voxel_size {voxel_size}: must be positive")
+        if (bounds is None) == (origin is None or dims is None):
+            raise ValueError("TSDFVolume: give either bounds or origin and dims")
+        if bounds is not None:
+            origin, dims = bounds[0], dims_of_bounds(bounds, voxel_size)
+        self.dims = tuple(int(d) for d in dims)
+        if len(self.dims) != 3 or min(self.dims) < 1:
+            raise ValueError(f"dims {dims}: expected three sizes of at least 1")
+        self.origin = tuple(float(np.float32(v)) for v in origin)
+        self.voxel_size = float(np.float32(voxel_size))
+        self.trunc = float(np.float32(5 * voxel_size if trunc is None else trunc))
+        if not self.trunc > 0:
+            raise ValueError(f"trunc {trunc}: must be positive")
+        self.has_colour = bool(colour)
+        need = volume_bytes(self.dims, self.has_colour)
+        if need > int(max_bytes):
+            extent = [(d - 1) * voxel_size for d in self.dims]
+            box, fits = ((0.0, 0.0, 0.0), tuple(extent)), voxel_size
+            while volume_bytes(dims_of_bounds(box, float(f"{fits:.3g}")), self.has_colour) > int(max_bytes):
+                fits *= 1.01
+            raise ValueError(f"TSDFVolume: {self.dims[0]} x {self.dims[1]} x {self.dims[2]} voxels of {voxel_size:g} m need {need / 2 ** 30:.2f} GiB, "
+                             f"more than max_bytes = {int(max_bytes) / 2 ** 30:.2f} GiB; a voxel size of {float(f'{fits:.3g}'):g} m would fit")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("monorec_amd.tsdf_fusion: the volume lives on a CUDA (HIP) device - there is no CPU fallback")
+        n = self.dims[0] * self.dims[1] * self.dims[2]
+        if storage is None:
+            self.tsdf = torch.empty(n, dtype=torch.float32, device=self.device)
+            self.weight = torch.empty(n, dtype=torch.float32, device=self.device)
+            self.colour = torch.empty(n, 4, dtype=torch.uint8, device=self.device) if self.has_colour else None
+        else:
+            self.tsdf, self.weight, self.colour = storage
+            for t, what in ((self.tsdf, "tsdf"), (self.weight, "weight")) + (((self.colour, "colour"),) if self.has_colour else ()):
+                _need_cuda(t, what)
+                if not t.is_contiguous() or t.numel() != (n * 4 if what == "colour" else n) or \
+                        t.dtype != (torch.uint8 if what == "colour" else torch.float32):
+                    raise ValueError(f"storage: {what} must be a contiguous tensor of the volume's size and type")
+            if not self.has_colour:
+                self.colour = None
+        self._origin = (ctypes.c_float * 3)(*self.origin)
+        self._keep = None
+        self.frames = 0                                        # keyframes integrated so far
+        self.reset()
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _volume_args(self):
+        return (self.tsdf.data_ptr(), self.weight.data_ptr(), self.colour.data_ptr() if self.colour is not None else None, *self.dims)
+
+    def reset(self):
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mr_tsdf_volume_reset_f32(*self._volume_args(), self._stream()), "mr_tsdf_volume_reset_f32")
+        self.frames = 0
+
+    # -- integrate
+    def integrate(self, depth_cm, colour, cam_to_world, intrinsics, max_depth_m=None):
+        """Integrate one keyframe or a batch, in order: depth_cm (h, w) / (B, h, w) int16 centimetres (0: no depth), colour (h, w, 3) /
+        (B, h, w, 3) uint8 (None for a volume without colour) - the two outputs of `tsdf_export.pack_frames` -, cam_to_world (4, 4) /
+        (B, 4, 4) anywhere, intrinsics one 3 x 3 / 4 x 4 matrix of the packed image or one per keyframe.  `max_depth_m`: depths beyond
+        it are ignored.  Launches of at most 8 keyframes on the current stream."""
+        _need_cuda(depth_cm, "depth_cm")
+        if depth_cm.dim() == 2:
+            depth_cm = depth_cm.unsqueeze(0)
+            colour = None if colour is None else colour.unsqueeze(0)
+        b = depth_cm.shape[0]
+        poses = torch.as_tensor(cam_to_world).detach().to("cpu", torch.float32).reshape(-1, 4, 4)
+        ks = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32)
+        ks = ks.reshape(-1, ks.shape[-2], ks.shape[-1])
+        if poses.shape[0] != b or ks.shape[0] not in (1, b) or (colour is not None and colour.shape[0] != b):
+            raise ValueError(f"integrate: {b} depth maps, {poses.shape[0]} poses, {ks.shape[0]} intrinsics"
+                             + ("" if colour is None else f", {colour.shape[0]} colour images"))
+        self.integrate_views([(depth_cm[i], None if colour is None else colour[i], poses[i], ks[i if ks.shape[0] == b else 0])
+                              for i in range(b)], max_depth_m)
+
+    def integrate_views(self, views, max_depth_m=None):
+        """The same for a list of (depth_cm (h, w), colour (h, w, 3) | None, cam_to_world, intrinsics) whose arrays need not be slices
+        of one tensor (the runner's staging slots)."""
+        self.integrate_prepared(self.prepare_views(views), max_depth_m)
+
+    def prepare_views(self, views):
+        """The host half of `integrate_views`: checks, the fp32 inverse of every pose and the `mr_tsdf_view` arrays of the launches (at
+        most 8 views each).  Returns what `integrate_prepared` launches; it keeps the images alive."""
+        keep, frames, size = [], [], None
+        for depth, colour, pose, k in views:
+            _need_cuda(depth, "depth_cm")
+            if depth.dtype != torch.int16 or depth.dim() != 2:
+                raise ValueError(f"depth_cm: expected (h, w) int16, got {tuple(depth.shape)} {depth.dtype}")
+            if size is None:
+                size = tuple(depth.shape)
+            if tuple(depth.shape) != size:
+                raise ValueError("integrate: the keyframes of one call must have one size")
+            depth = depth.contiguous()
+            if self.has_colour:
+                if colour is None:
+                    raise ValueError("integrate: this volume has colour; pass the packed colour image (or build it with colour=False)")
+                _need_cuda(colour, "colour")
+                if colour.dtype != torch.uint8 or tuple(colour.shape) != size + (3,):
+                    raise ValueError(f"colour: expected {size + (3,)} uint8, got {tuple(colour.shape)} {colour.dtype}")
+                colour = colour.contiguous()
+            else:
+                colour = None
+            k = _matrix(k, "intrinsics")
+            view = _lib.TsdfView()
+            m = torch.inverse(_matrix(pose, "cam_to_world").reshape(4, 4))          # world -> camera, fp32 on the host
+            view.m[:] = [float(v) for v in m[:3, :4].reshape(-1)]
+            view.fx, view.fy, view.cx, view.cy = float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+            view.depth_cm = depth.data_ptr()
+            view.colour = colour.data_ptr() if colour is not None else None
+            frames.append(view)
+            keep.append((depth, colour))
+        arrays = [(_lib.TsdfView * len(frames[lo:lo + MAX_FRAMES]))(*frames[lo:lo + MAX_FRAMES]) for lo in range(0, len(frames), MAX_FRAMES)]
+        return dict(arrays=arrays, size=size, count=len(frames), keep=keep)
+
+    def integrate_prepared(self, prepared, max_depth_m=None):
+        """The launches of `prepare_views`' result, on the current stream."""
+        lib = _lib.load()
+        limit = float("inf") if max_depth_m is None else float(max_depth_m)
+        with torch.cuda.device(self.device):
+            for array in prepared["arrays"]:
+                _lib.check(lib.mr_tsdf_integrate_f32(*self._volume_args(), self._origin, self.voxel_size, self.trunc, limit, array, len(array),
+                                                     prepared["size"][0], prepared["size"][1], self._stream()), "mr_tsdf_integrate_f32")
+        self._keep = prepared["keep"]                          # alive until the launches have run (same stream: the next call may drop them)
+        self.frames += prepared["count"]
+
+    # -- surface
+    def extract(self, min_weight=0):
+        """(n, 6) fp32 on the device: x y z red green blue of every edge crossing between two voxels of weight > min_weight.  Two
+        launches (count, fill) and one read of the count.  The order of the records is unspecified."""
+        lib = _lib.load()
+        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        common = (*self._volume_args(), self._origin, self.voxel_size, float(min_weight))
+        with torch.cuda.device(self.device):
+            _lib.check(lib.mr_tsdf_extract_f32(*common, None, 0, cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
+            count = int(cursor.item())
+            records = torch.empty(count, 6, dtype=torch.float32, device=self.device)
+            if count:
+                cursor.zero_()
+                _lib.check(lib.mr_tsdf_extract_f32(*common, records.data_ptr(), count, cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
+                if int(cursor.item()) != count:
+                    raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launch")
+        return records
+
+    def count(self, min_weight=0):
+        """Number of records `extract(min_weight)` would return (the count launch alone)."""
+        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mr_tsdf_extract_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), None, 0,
+                                                       cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
+        return int(cursor.item())
+
+    def save_ply(self, file, min_weight=0):
+        """The surface points as a binary .ply (pointcloud.PLYSaver's header and records) to a path or a binary file object.  Returns
+        the number of vertices."""
+        records = self.extract(min_weight).cpu().numpy()
+        if hasattr(file, "write"):
+            write_ply(file, records.reshape(-1))
+        else:
+            with open(file, "wb") as f:
+                write_ply(f, records.reshape(-1))
+        return records.shape[0]
+
+    # -- the volume itself
+    def grids(self):
+        """Host copies shaped (nz, ny, nx): tsdf, weight, colour (nz, ny, nx, 4) or None."""
+        nx, ny, nz = self.dims
+        colour = self.colour.cpu().numpy().reshape(nz, ny, nx, 4) if self.colour is not None else None
+        return self.tsdf.cpu().numpy().reshape(nz, ny, nx), self.weight.cpu().numpy().reshape(nz, ny, nx), colour
+
+    def save(self, file):
+        """.npz: tsdf, weight (nz, ny, nx) fp32, colour (nz, ny, nx, 4) uint8 if any, origin, dims (nx, ny, nz), voxel_size, trunc."""
+        tsdf, weight, colour = self.grids()
+        arrays = dict(tsdf=tsdf, weight=weight, origin=np.asarray(self.origin, dtype=np.float32), dims=np.asarray(self.dims, dtype=np.int64),
+                      voxel_size=np.float32(self.voxel_size), trunc=np.float32(self.trunc), frames=np.int64(self.frames))
+        if colour is not None:
+            arrays["colour"] = colour
+        np.savez(file, **arrays)
+
+    @classmethod
+    def load(cls, file, device="cuda:0", max_bytes=8 << 30):
+        with np.load(file) as z:
+            volume = cls(origin=z["origin"], dims=z["dims"], voxel_size=float(z["voxel_size"]), trunc=float(z["trunc"]),
+                         colour="colour" in z.files, device=device, max_bytes=max_bytes)
+            volume.tsdf.copy_(torch.from_numpy(z["tsdf"].reshape(-1)))
+            volume.weight.copy_(torch.from_numpy(z["weight"].reshape(-1)))
+            if volume.colour is not None:
+                volume.colour.copy_(torch.from_numpy(z["colour"].reshape(-1, 4)))
+            volume.frames = int(z["frames"]) if "frames" in z.files else 0
+        return volume
+
+
+# ------------------------------------------------------------------------------------------ a directory of tsdf_export
+_FRAME = re.compile(r"^frame-(\d+)\.pose\.txt$")
+
+
+def list_export_directory(directory):
+    """[(number, base path)] of the `frame-%06d.*` triples of a directory written by tsdf_export, in numeric order."""
+    frames = []
+    for name in os.listdir(str(directory)):
+        m = _FRAME.match(name)
+        if m:
+            frames.append((int(m.group(1)), os.path.join(str(directory), name[:-len(".pose.txt")])))
+    return sorted(frames)
+
+
+def read_export_pose(base):
+    """Camera -> world (4, 4) fp32 of one triple.  The pose file holds `inverse(pose)` (utils/util.py:91): it is inverted again, in fp32."""
+    world_to_cam = torch.from_numpy(np.loadtxt(base + ".pose.txt").astype(np.float32)).reshape(4, 4)
+    return torch.inverse(world_to_cam)
+
+
+def read_export_frame(base):
+    """One triple from the files: depth (h, w) int16 centimetres, colour (h, w, 3) uint8 (the decoded JPEG), camera -> world (4, 4)
+    fp32 (`read_export_pose`)."""
+    from PIL import Image
+    with Image.open(base + ".depth.png") as img:
+        depth = np.array(img)
+    with Image.open(base + ".color.jpg") as img:
+        colour = np.array(img.convert("RGB"))
+    return depth.astype(np.uint16).view(np.int16), colour, read_export_pose(base)
+
+
+def fuse_directory(directory, volume=None, voxel_size=0.1, trunc=None, colour=True, max_depth_m=None, bounds=None, device="cuda:0",
+                   max_bytes=8 << 30):
+    """Fuse a directory written by `tsdf_export` (`camera-intrinsics.txt` and the `frame-*` triples in numeric order, read with Pillow)
+    into `volume`, or into a new one over `bounds`, or over `bounds_from_frusta` of the poses and `max_depth_m`.  Only the pose files
+    are read ahead (to size the volume); the images are decoded eight keyframes at a time, one integrate launch each.  The colour
+    comes from the JPEGs, so it differs from that of a live fusion; the depth does not.  Returns the volume."""
+    frames = list_export_directory(directory)
+    if not frames:
+        raise ValueError(f"{directory}: no frame-*.pose.txt files")
+    k = torch.from_numpy(np.loadtxt(os.path.join(str(directory), "camera-intrinsics.txt")).astype(np.float32)).reshape(3, 3)
+    if volume is None:
+        if bounds is None:
+            if max_depth_m is None:
+                raise ValueError("fuse_directory: without a volume and without bounds, max_depth_m is needed to size one")
+            from PIL import Image
+            with Image.open(frames[0][1] + ".depth.png") as img:
+                w, h = img.size
+            bounds = bounds_from_frusta([read_export_pose(base) for _, base in frames], k, h, w, max_depth_m, voxel_size)
+        volume = TSDFVolume(bounds, voxel_size, trunc=trunc, colour=colour, device=device, max_bytes=max_bytes)
+    for lo in range(0, len(frames), MAX_FRAMES):
+        chunk = [read_export_frame(base) for _, base in frames[lo:lo + MAX_FRAMES]]
+        depth = torch.from_numpy(np.stack([f[0] for f in chunk])).to(volume.device)
+        image = torch.from_numpy(np.stack([f[1] for f in chunk])).to(volume.device) if volume.has_colour else None
+        volume.integrate(depth, image, torch.stack([f[2] for f in chunk]), k, max_depth_m)
+    return volume
+
+
+# ------------------------------------------------------------------------------------------ the runner
+def fusion_settings(config):
+    """The fusion keys of a runner config, checked: dict(voxel_size, trunc, bounds, max_bytes, fuse_batch, file_name, save_volume)."""
+    voxel = float(config.get("voxel_size", 0.1))
+    trunc_voxels = float(config.get("trunc_voxels", 5))
+    batch = int(config.get("fuse_batch", 4))
+    if not voxel > 0:
+        raise ValueError(f"monorec_amd.tsdf_fusion: voxel_size {voxel} must be positive")
+    if not trunc_voxels > 0:
+        raise ValueError(f"monorec_amd.tsdf_fusion: trunc_voxels {trunc_voxels} must be positive")
+    if not 1 <= batch <= MAX_FRAMES:
+        raise ValueError(f"monorec_amd.tsdf_fusion: fuse_batch {batch} must be 1 .. {MAX_FRAMES}")
+    bounds = config.get("bounds", None)
+    if bounds is None and config.get("max_d", None) is None:
+        raise ValueError("monorec_amd.tsdf_fusion: the config has neither `bounds` nor `max_d`; one of them is needed to size the volume")
+    if bounds is not None:
+        dims_of_bounds(bounds, voxel)
+    return dict(voxel_size=voxel, trunc=trunc_voxels * voxel, bounds=bounds, max_bytes=int(config.get("tsdf_max_bytes", 8 << 30)),
+                fuse_batch=batch, file_name=config.get("file_name", "tsdf.ply"), save_volume=config.get("save_volume", None))
+
+
+class Fusion:
+    """The stages of `run`, for callers that want them apart (tools/bench_tsdf_fusion.py times them): the constructor builds model,
+    dataset and volume, `fuse()` drives the keyframe loop, `write()` extracts and saves."""
+
+    def __init__(self, config, model=None, dataset=None, device="cuda:0"):
+        self.config, self.settings = config, fusion_settings(config)
+        settings = self.settings
+        self.stream = stream = tx.KeyframeStream(config, model, dataset, (0, 1), device, who="monorec_amd.tsdf_fusion")
+        y0, y1, x0, x1 = tx.crop_box(stream.crop, stream.height, stream.width)
+        self.offset = (y0, x0)
+        ch, cw = y1 - y0, x1 - x0
+        bounds = settings["bounds"]
+        if bounds is None:
+            items = stream.export_items()
+            if not hasattr(stream.dataset, "keyframe_geometry"):
+                raise ValueError("monorec_amd.tsdf_fusion: this dataset cannot hand out its poses ahead of the run; give `bounds` in the config")
+            if not items:
+                raise ValueError("monorec_amd.tsdf_fusion: the window exports no keyframe, nothing to size the volume from; give `bounds`")
+            geometry = [stream.dataset.keyframe_geometry(i) for i in items]
+            bounds = bounds_from_frusta([g[0] for g in geometry], [self.shifted(g[1]) for g in geometry], ch, cw, config["max_d"],
+                                        settings["voxel_size"])
+        self.volume = TSDFVolume(bounds, settings["voxel_size"], trunc=settings["trunc"], colour=True, device=stream.device,
+                                 max_bytes=settings["max_bytes"])
+        depth_bytes, colour_bytes = tx.packed_sizes(1, ch, cw)
+        self._slots = [torch.empty(depth_bytes + colour_bytes, dtype=torch.uint8, device=stream.device) for _ in range(settings["fuse_batch"])]
+
+    def shifted(self, k):
+        """The intrinsics of the cropped image, as `save_intrinsics_for_tsdf` shifts them, on a copy."""
+        k = torch.as_tensor(k).detach().to("cpu", torch.float32)
+        k = k.reshape(k.shape[-2], k.shape[-1]).clone()
+        k[0, 2] -= self.offset[1]
+        k[1, 2] -= self.offset[0]
+        return k
+
+    def fuse(self):
+        config, stream, volume, slots = self.config, self.stream, self.volume, self._slots
+        staged, keep = [], []
+
+        def flush():
+            if staged:
+                volume.integrate_views(staged)
+                del staged[:]
+                del keep[:]
+
+        def emit(number, entry, masks):
+            depth, colour, alive = tx.pack_frames(entry["depth"], entry["keyframe"], stream.crop, config.get("min_d", None),
+                                                  config.get("max_d", None), static_masks=masks, min_hits=1, out=slots[len(staged)])
+            keep.append(alive)
+            staged.append((depth[0], colour[0], _matrix(torch.as_tensor(entry["pose"]).reshape(4, 4), "keyframe_pose"),
+                           self.shifted(entry["intrinsics"])))            # each keyframe's own calibration
+            if len(staged) == len(slots):
+                flush()
+
+        stream.run(emit)
+        flush()
+        return self
+
+    def write(self):
+        out_dir = self.config.get("output_dir", "saved")
+        os.makedirs(out_dir, exist_ok=True)
+        count = self.volume.save_ply(os.path.join(out_dir, self.settings["file_name"]))
+        if self.settings["save_volume"] is not None:
+            self.volume.save(self.settings["save_volume"])
+        return count
+
+
+def run(config, model=None, dataset=None, device="cuda:0"):
+    """Fuse the keyframes of a config of `tsdf_export.run`'s shape (same `data_set`, `arch`, `start` / `end`, `roi`, `min_d` / `max_d`,
+    `use_mask`) and write the surface points to `output_dir/file_name` (default `tsdf.ply`).  Optional keys: `voxel_size` (0.1),
+    `trunc_voxels` (5), `bounds` (else `bounds_from_frusta` over the window's exported keyframe poses and `max_d`; without both it
+    raises), `tsdf_max_bytes`, `fuse_batch` (keyframes per integrate launch, default 4), `save_volume` (a path for `TSDFVolume.save`).
+
+    Per keyframe `pack_frames` (vote, crop, thresholds: the depths are exactly the ones the export writes to the PNG) fills a staging slot
+    on the device; after `fuse_batch` keyframes, or at the end, one integrate launch follows on the same stream.  Every keyframe is
+    integrated with its own intrinsics, shifted by the crop on a copy.  Single-process.  Returns the number of surface points written."""
+    return Fusion(config, model, dataset, device).fuse().write()
+
+
+def main(argv=None):
+    config, device = tx.load_config(argv, prog="python -m monorec_amd.tsdf_fusion",
+                                    description="MonoRec keyframes fused into a TSDF volume on the device; the surface points as a .ply")
+    count = run(config, device=device)
+    print(f"{count} surface points written to {os.path.join(config.get('output_dir', 'saved'), config.get('file_name', 'tsdf.ply'))}")
+
+
+if __name__ == "__main__":
+    main()

@@ -216,6 +216,12 @@ class TUMMonoVODataset:
         }
         return data, self._depth
 
+    def keyframe_geometry(self, index):
+        """(keyframe_pose, keyframe_intrinsics) of sample `index` as `__getitem__` hands them out, without decoding a frame."""
+        if not 0 <= index < self.length:
+            raise IndexError()
+        return self._poses[index + self._offset], self._intrinsics
+
     def close(self):
         if self._frames is not None:
             self._frames.close()
@@ -241,6 +247,13 @@ class TUMMonoVOMultiDataset:
         for dataset in self.datasets:
             if index < len(dataset):
                 return dataset[index]
+            index -= len(dataset)
+        raise IndexError()
+
+    def keyframe_geometry(self, index):
+        for dataset in self.datasets:
+            if index < len(dataset):
+                return dataset.keyframe_geometry(index)
             index -= len(dataset)
         raise IndexError()
 
