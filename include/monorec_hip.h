@@ -747,6 +747,60 @@ int mr_tsdf_extract_f32(const float* tsdf, const float* weight, const uint8_t* c
                         const float* origin, float voxel_size, float min_weight, float* records, int64_t capacity_records,
                         int64_t* cursor, void* stream);
 
+/* The same surface as a welded, indexed triangle mesh (two entries added within ABI 24: the change only adds symbols): marching
+ * tetrahedra over the Kuhn split of every cube of eight voxels.  It has no ambiguous cases, so the mesh is a closed 2-manifold wherever
+ * the voxels are seen; the price is about twice the triangles of marching cubes.
+ *
+ * Edges.  Voxel v = (x, y, z) owns seven edges (v, e) from v to v + d_e:
+ *   d_0 = (1,0,0)  d_1 = (0,1,0)  d_2 = (0,0,1)  d_3 = (1,1,0)  d_4 = (1,0,1)  d_5 = (0,1,1)  d_6 = (1,1,1)
+ * Edge (v, e) is ACTIVE when n = v + d_e is inside the volume, weight[v] > min_weight, weight[n] > min_weight and
+ * (tsdf[v] < 0) != (tsdf[n] < 0); a tsdf of exactly 0 counts as outside.  The 7-bit mask of v has bit e set for every active (v, e).
+ * Every active edge carries one vertex, all fp32, every operation rounded on its own:
+ *   s = tsdf[v] / (tsdf[v] - tsdf[n]);  step = s * voxel_size;  p_k = origin_k + (float)i_k * voxel_size
+ *   pos_k = p_k + step where d_e[k] = 1, p_k elsewhere
+ *   value_c = floorf((float)C_v + s * ((float)C_n - (float)C_v) + .5)                       (0 without a colour volume)
+ * as one record x y z red green blue; for e < 3 it equals the record of mr_tsdf_extract_f32 bit for bit.  Vertices whose positions
+ * coincide (a tsdf of exactly 0) stay distinct.
+ *
+ * Tetrahedra.  The cube at c0 = v, all eight corners inside the volume, is split along its diagonal into one tetrahedron per
+ * permutation (a, b, c) of the axes, with the corners c0, c1 = c0 + e_a, c2 = c1 + e_b, c3 = c2 + e_c = c0 + (1,1,1), in the order
+ *   even: (x,y,z) (y,z,x) (z,x,y)     odd: (x,z,y) (z,y,x) (y,x,z)
+ * Its six edges, each owned by its first corner: E01 = (c0, a), E12 = (c1, b), E23 = (c2, c), E02 = (c0, a + b), E13 = (c1, b + c),
+ * E03 = (c0, d_6), where p + q is the diagonal type of the axis pair: x + y = 3, x + z = 4, y + z = 5.  A tetrahedron emits triangles only
+ * when all four corners have weight > min_weight; then every edge between an inside (tsdf < 0) and an outside corner is active, and
+ * with case = sum of 1 << i over the inside corners c_i an EVEN tetrahedron emits
+ *    1  c0            (E01 E02 E03)                     14  c1 c2 c3      (E01 E03 E02)
+ *    2  c1            (E01 E13 E12)                     13  c0 c2 c3      (E01 E12 E13)
+ *    4  c2            (E02 E12 E23)                     11  c0 c1 c3      (E02 E23 E12)
+ *    8  c3            (E03 E23 E13)                      7  c0 c1 c2      (E03 E13 E23)
+ *    3  c0 c1         (E12 E02 E03) (E12 E03 E13)       12  c2 c3         (E12 E13 E03) (E12 E03 E02)
+ *    5  c0 c2         (E01 E12 E23) (E01 E23 E03)       10  c1 c3         (E01 E03 E23) (E01 E23 E12)
+ *    6  c1 c2         (E01 E13 E23) (E01 E23 E02)        9  c0 c3         (E01 E02 E23) (E01 E23 E13)
+ *    0, 15            nothing
+ * (two inside corners cut a quad: it is split along the diagonal from the first vertex listed).  An ODD tetrahedron - its chain
+ * c1 - c0, c2 - c0, c3 - c0 is left-handed - swaps the last two vertices of every triangle.  So for a triangle (a, b, c) the normal
+ * (b - a) x (c - a) points from the inside (tsdf < 0) to the outside, towards the camera that saw the surface.  Triangles of zero area
+ * are kept: the topology does not depend on the values.
+ *
+ * mr_tsdf_mesh_vertices_f32: one record per active edge into `vertices`, in no particular order, and into vertex_base[idx(v)] (int32,
+ * nx * ny * nz elements, caller-owned) the index of the first vertex of every voxel v that owns one; elements of voxels without an
+ * active edge are left untouched.  The vertices of one voxel are consecutive in the order of e:
+ *   index(v, e) = vertex_base[idx(v)] + popcount(mask(v) & ((1 << e) - 1))
+ * mr_tsdf_mesh_triangles_f32: three int32 vertex indices per triangle into `triangles`, in no particular order; it recomputes the masks
+ * from tsdf / weight / min_weight - which must be those of the vertex call - and reads vertex_base of the owners.
+ * Cursor and capacity as in mr_tsdf_extract_f32: one atomicAdd per workgroup on *cursor (int64, device memory, set by the caller),
+ * records at or beyond the capacity are counted and not written.  vertices / triangles NULL: count only (capacity and vertex_base are
+ * ignored; vertex_base may be NULL).  Indices are int32: a caller whose vertex count reaches 2^31 must not fill.  A workgroup owns
+ * MR_TSDF_TILE_X x _Y x _Z voxels; a tile with no seen negative voxel in reach touches neither vertex_base nor the cursor.
+ * Besides the cases of mr_tsdf_extract_f32: nx * ny * nz >= 2^31, vertex_base / triangles off a 4-byte boundary, an output without
+ * vertex_base, a negative capacity with an output: MR_ERR_BAD_ARGUMENT, nothing is launched. */
+int mr_tsdf_mesh_vertices_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                              const float* origin, float voxel_size, float min_weight, float* vertices, int64_t capacity_vertices,
+                              int32_t* vertex_base, int64_t* cursor, void* stream);
+int mr_tsdf_mesh_triangles_f32(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float min_weight,
+                               const int32_t* vertex_base, int32_t* triangles, int64_t capacity_triangles, int64_t* cursor,
+                               void* stream);
+
 /* ---- input pipeline: KittiOdometryDataset.preprocess_image, kitti_odometry_dataset.py:120-134 ------
  *
  * img.crop(box) -> img.resize((W,H), Image.BILINEAR) -> float32 / 255 - .5 -> CHW (a 1-channel image is stacked 3x),

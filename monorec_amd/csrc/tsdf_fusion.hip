@@ -1,5 +1,5 @@
 // TSDF fusion on the device (monorec_amd/tsdf_fusion.py): a dense voxel volume, the packed keyframes of mr_tsdf_frame_f32 integrated
-// into it by running average, the zero-crossing surface points out.  The arithmetic is the one include/monorec_hip.h spells out -
+// into it by running average, the zero-crossing surface out as points or as a welded triangle mesh.  The arithmetic is the one include/monorec_hip.h spells out -
 // all fp32, every operation rounded on its own (compiled with -ffp-contract=off; `/` is the correctly rounded division) - and
 // tests/tsdf_fusion_ref.py restates it in numpy; the GPU tests compare bit for bit.
 //
@@ -7,6 +7,7 @@
 //   tsdf_integrate_kernel   up to MR_TSDF_MAX_FRAMES keyframes per launch: a voxel is loaded once, updated by the frames in order in
 //                           registers and stored once, and only by a thread one of whose voxels a frame updated
 //   tsdf_extract_kernel     edge crossings as x y z r g b records; with records == nullptr it only counts
+//   tsdf_mesh_vertices_kernel, tsdf_mesh_triangles_kernel   the same surface as an indexed mesh (marching tetrahedra; further down)
 //
 // The integration sweeps the volume: 8 bytes (12 with colour) in and out per voxel and frame BATCH, the depth and colour images are
 // gathered through the caches (a keyframe is a few hundred KB).  Measured kernel time (DESIGN.md section 7, 512 x 512 x 128 voxels,
@@ -251,6 +252,254 @@ __global__ __launch_bounds__(256) void tsdf_extract_kernel(const ExtractArgs a) 
     }
 }
 
+// ---- the surface as a welded triangle mesh: marching tetrahedra over the Kuhn split (include/monorec_hip.h has the rules) ----------
+//
+// Both kernels give a workgroup of 256 threads the integrate kernel's tile of 32 x 8 x 4 voxels, a thread the four voxels (cubes) of
+// one (x, y) column of it, and stage what the tile needs in LDS so that every value is read from memory once per workgroup, not once
+// per edge or tetrahedron that touches it:
+//   tsdf_mesh_vertices_kernel   tsdf (fp32) and a code byte (bit 0 seen, bit 1 seen and negative) of the tile plus one voxel beyond its
+//                               high faces, 33 x 9 x 5 (7.4 KB): the far ends of the seven edges a voxel owns
+//   tsdf_mesh_triangles_kernel  the code byte alone for the tile plus TWO voxels, 34 x 10 x 6 (2 KB): a cube's tetrahedra use edges owned
+//                               by its corners, and the rank of an edge among its owner's vertices needs the owner's whole mask, which
+//                               reaches one voxel beyond the cube.  The masks of the 33 x 9 x 5 owners follow from the codes (1.5 KB).
+// A tile whose staged block holds no seen negative voxel - nearly all of a fused volume: in front of every surface or never seen -
+// leaves at the barrier that ends the staging (__syncthreads_or) and has touched neither vertex_base nor the cursor.
+constexpr int VSX = TX + 1, VSY = TY + 1, VSZ = TZ + 1, VSN = VSX * VSY * VSZ;           // staged block of the vertex kernel
+constexpr int CSX = TX + 2, CSY = TY + 2, CSZ = TZ + 2, CSN = CSX * CSY * CSZ;           // staged codes of the triangle kernel
+constexpr unsigned SEEN = 1u, NEG = 2u;
+
+struct MeshArgs {
+    const float* tsdf;
+    const float* weight;
+    const unsigned* colour;                      // vertices only; r g b 0 per voxel or null
+    int nx, ny, nz;
+    int tiles_x, tiles_y;
+    float ox, oy, oz, voxel, min_weight;
+    float* vertices;                             // null: count only
+    int* vertex_base;                            // written by the vertex kernel, read by the triangle kernel
+    int* triangles;                              // null: count only
+    long long capacity;
+    unsigned long long* cursor;
+};
+
+// exclusive prefix of `mine` over the workgroup and its total: shuffles within the wave, wave totals through LDS (as tsdf_extract_kernel)
+__device__ __forceinline__ int workgroup_prefix(int mine, int* wave_tot, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int incl = mine;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += up;
+    }
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int before = incl - mine;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const int v = wave_tot[w]; if (w < wave) before += v; total += v; }
+    return before;
+}
+
+// the 7-bit active-edge mask of the voxel at `at` of a block of codes with row stride sx and slice stride sxy
+__device__ __forceinline__ unsigned edge_mask(const uint8_t* code, int at, int sx, int sxy) {
+    const unsigned c = code[at];
+    if (!(c & SEEN)) return 0u;
+    const int far[7] = {1, sx, sxy, 1 + sx, 1 + sxy, sx + sxy, 1 + sx + sxy};
+    unsigned mask = 0;
+#pragma unroll
+    for (int e = 0; e < 7; ++e) {
+        const unsigned n = code[at + far[e]];
+        if ((n & SEEN) && ((n ^ c) & NEG)) mask |= 1u << e;
+    }
+    return mask;
+}
+
+__global__ __launch_bounds__(256) void tsdf_mesh_vertices_kernel(const MeshArgs a) {
+    __shared__ float s_t[VSN];
+    __shared__ uint8_t s_code[VSN];
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x, tile = blockIdx.x;
+    const int x0 = (tile % a.tiles_x) * TX, y0 = ((tile / a.tiles_x) % a.tiles_y) * TY, z0 = (tile / (a.tiles_x * a.tiles_y)) * TZ;
+    const long long plane = (long long)a.nx * a.ny;
+    int any_neg = 0;
+    for (int i = tid; i < VSN; i += 256) {
+        const int sx = i % VSX, sy = (i / VSX) % VSY, sz = i / (VSX * VSY);
+        const int gx = x0 + sx, gy = y0 + sy, gz = z0 + sz;
+        float t = 1.0f;
+        unsigned c = 0u;
+        if (gx < a.nx && gy < a.ny && gz < a.nz) {
+            const long long g = (long long)gz * plane + (long long)gy * a.nx + gx;
+            if (a.weight[g] > a.min_weight) {
+                t = a.tsdf[g];
+                c = t < 0.0f ? (SEEN | NEG) : SEEN;
+            }
+        }
+        s_t[i] = t;
+        s_code[i] = (uint8_t)c;
+        any_neg |= (int)(c & NEG);
+    }
+    if (!__syncthreads_or(any_neg)) return;
+
+    const int lx = tid & 31, ly = tid >> 5;
+    unsigned masks = 0;                          // the masks of the thread's four voxels, a byte each
+#pragma unroll
+    for (int j = 0; j < TZ; ++j) masks |= edge_mask(s_code, (j * VSY + ly) * VSX + lx, VSX, VSX * VSY) << (8 * j);
+    const int mine = __popc(masks);
+    int total;
+    const int before = workgroup_prefix(mine, wave_tot, total);
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);       // one per workgroup
+    if (!a.vertices) return;
+    __syncthreads();
+    if (!masks) return;
+    long long rec = (long long)s_base + before;
+    const int gx = x0 + lx, gy = y0 + ly;        // inside the volume: a voxel outside it has no code, hence no mask
+    const float px = a.ox + (float)gx * a.voxel, py = a.oy + (float)gy * a.voxel;
+    const int s_far[7] = {1, VSX, VSX * VSY, 1 + VSX, 1 + VSX * VSY, VSX + VSX * VSY, 1 + VSX + VSX * VSY};
+    const long long g_far[7] = {1, a.nx, plane, 1 + a.nx, 1 + plane, a.nx + plane, 1 + a.nx + plane};
+    constexpr unsigned along[7] = {1u, 2u, 4u, 3u, 5u, 6u, 7u};                   // bit k: the edge advances along axis k
+#pragma unroll
+    for (int j = 0; j < TZ; ++j) {
+        const unsigned mask = (masks >> (8 * j)) & 0xffu;
+        if (!mask) continue;
+        const int gz = z0 + j, at = (j * VSY + ly) * VSX + lx;
+        const long long g = (long long)gz * plane + (long long)gy * a.nx + gx;
+        a.vertex_base[g] = (int)rec;
+        const float p[3] = {px, py, a.oz + (float)gz * a.voxel};
+        const float tv = s_t[at];
+        const unsigned cv = a.colour ? a.colour[g] : 0u;
+#pragma unroll
+        for (int e = 0; e < 7; ++e) {
+            if (!(mask & (1u << e))) continue;
+            if (rec < a.capacity) {
+                const float s = tv / (tv - s_t[at + s_far[e]]);
+                const float step = s * a.voxel;
+                float* o = a.vertices + rec * 6;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) o[k] = (along[e] >> k) & 1u ? p[k] + step : p[k];
+                const unsigned cn = a.colour ? a.colour[g + g_far[e]] : 0u;
+                o[3] = mix_byte(cv & 0xffu, cn & 0xffu, s);
+                o[4] = mix_byte((cv >> 8) & 0xffu, (cn >> 8) & 0xffu, s);
+                o[5] = mix_byte((cv >> 16) & 0xffu, (cn >> 16) & 0xffu, s);
+            }
+            ++rec;
+        }
+    }
+}
+
+// Triangles of an even tetrahedron per case (bit i: corner c_i inside): bits 0-3 the count, then a nibble per vertex naming the
+// tetrahedron's edge 0 E01, 1 E12, 2 E23, 3 E02, 4 E13, 5 E03 - the table of include/monorec_hip.h.  An odd tetrahedron swaps the
+// last two vertices of every triangle.
+constexpr unsigned TET_CASES[16] = {0x00000000u, 0x00005301u, 0x00001401u, 0x04515312u, 0x00002131u, 0x05202102u, 0x03202402u, 0x00002451u,
+                                     0x00004251u, 0x04202302u, 0x01202502u, 0x00001231u, 0x03515412u, 0x00004101u, 0x00003501u, 0x00000000u};
+// the six permutations (a, b, c), the even ones first, two bits per axis
+constexpr unsigned TET_PERMS[6] = {0u | 1u << 2 | 2u << 4, 1u | 2u << 2 | 0u << 4, 2u | 0u << 2 | 1u << 4,
+                                    0u | 2u << 2 | 1u << 4, 2u | 1u << 2 | 0u << 4, 1u | 0u << 2 | 2u << 4};
+
+// the cases of the six tetrahedra of the cube at `at` of the staged codes, four bits each; 0 where a corner is unseen
+__device__ __forceinline__ unsigned cube_cases(const uint8_t* code, int at) {
+    const int unit[3] = {1, CSX, CSX * CSY};
+    const unsigned c0 = code[at], c3 = code[at + 1 + CSX + CSX * CSY];
+    if (!(c0 & c3 & SEEN)) return 0u;
+    unsigned cases = 0;
+#pragma unroll
+    for (int t = 0; t < 6; ++t) {
+        const unsigned perm = TET_PERMS[t];
+        const int a1 = at + unit[perm & 3u];
+        const unsigned c1 = code[a1], c2 = code[a1 + unit[(perm >> 2) & 3u]];
+        if (!(c1 & c2 & SEEN)) continue;
+        cases |= (((c0 & NEG) >> 1) | (c1 & NEG) | ((c2 & NEG) << 1) | ((c3 & NEG) << 2)) << (4 * t);
+    }
+    return cases;
+}
+
+__global__ __launch_bounds__(256) void tsdf_mesh_triangles_kernel(const MeshArgs a) {
+    __shared__ uint8_t s_code[CSN];
+    __shared__ uint8_t s_mask[VSN];
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x, tile = blockIdx.x;
+    const int x0 = (tile % a.tiles_x) * TX, y0 = ((tile / a.tiles_x) % a.tiles_y) * TY, z0 = (tile / (a.tiles_x * a.tiles_y)) * TZ;
+    const long long plane = (long long)a.nx * a.ny;
+    int any_neg = 0;
+    for (int i = tid; i < CSN; i += 256) {
+        const int sx = i % CSX, sy = (i / CSX) % CSY, sz = i / (CSX * CSY);
+        const int gx = x0 + sx, gy = y0 + sy, gz = z0 + sz;
+        unsigned c = 0u;
+        if (gx < a.nx && gy < a.ny && gz < a.nz) {
+            const long long g = (long long)gz * plane + (long long)gy * a.nx + gx;
+            if (a.weight[g] > a.min_weight) c = a.tsdf[g] < 0.0f ? (SEEN | NEG) : SEEN;
+        }
+        s_code[i] = (uint8_t)c;
+        if (sx < VSX && sy < VSY && sz < VSZ) any_neg |= (int)(c & NEG);          // the corners of the tile's cubes
+    }
+    if (!__syncthreads_or(any_neg)) return;
+
+    const int lx = tid & 31, ly = tid >> 5;
+    unsigned cases[TZ];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < TZ; ++j) {
+        cases[j] = cube_cases(s_code, (j * CSY + ly) * CSX + lx);
+#pragma unroll
+        for (int t = 0; t < 6; ++t) mine += (int)(TET_CASES[(cases[j] >> (4 * t)) & 15u] & 15u);
+    }
+    int total;
+    const int before = workgroup_prefix(mine, wave_tot, total);
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);       // one per workgroup
+    if (!a.triangles) return;
+    for (int i = tid; i < VSN; i += 256) {
+        const int sx = i % VSX, sy = (i / VSX) % VSY, sz = i / (VSX * VSY);
+        s_mask[i] = (uint8_t)edge_mask(s_code, (sz * CSY + sy) * CSX + sx, CSX, CSX * CSY);
+    }
+    __syncthreads();
+    if (!mine) return;
+    long long tri = (long long)s_base + before;
+    const auto m_unit = [](int k) { return k == 0 ? 1 : k == 1 ? VSX : VSX * VSY; };
+    const auto g_unit = [&](int k) { return k == 0 ? 1ll : k == 1 ? (long long)a.nx : plane; };
+#pragma unroll
+    for (int j = 0; j < TZ; ++j) {
+        if (!cases[j]) continue;
+        const int m0 = (j * VSY + ly) * VSX + lx;
+        const long long g0 = (long long)(z0 + j) * plane + (long long)(y0 + ly) * a.nx + (x0 + lx);
+#pragma unroll 1
+        for (int t = 0; t < 6; ++t) {
+            unsigned word = TET_CASES[(cases[j] >> (4 * t)) & 15u];
+            const int count = (int)(word & 15u);
+            if (!count) continue;
+            const unsigned perm = TET_PERMS[t];
+            const int pa = perm & 3u, pb = (perm >> 2) & 3u, pc = (perm >> 4) & 3u;
+            // owner (as a step from c0 in the mask block and in the volume) and edge type of the tetrahedron's six edges
+            const int m_own[3] = {m0, m0 + m_unit(pa), m0 + m_unit(pa) + m_unit(pb)};
+            const long long g_own[3] = {g0, g0 + g_unit(pa), g0 + g_unit(pa) + g_unit(pb)};
+            const int owner[6] = {0, 1, 2, 0, 1, 0};
+            const int type[6] = {pa, pb, pc, 2 + pa + pb, 2 + pb + pc, 6};
+            word >>= 4;
+            for (int n = 0; n < count; ++n, ++tri, word >>= 12) {
+                if (tri >= a.capacity) continue;
+                int v[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int edge = (int)((word >> (4 * k)) & 15u);
+                    int own = 0, ty = 0;
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) if (edge == q) { own = owner[q]; ty = type[q]; }
+                    int mo = m_own[0];
+                    long long go = g_own[0];
+                    if (own == 1) { mo = m_own[1]; go = g_own[1]; }
+                    if (own == 2) { mo = m_own[2]; go = g_own[2]; }
+                    v[k] = a.vertex_base[go] + __popc((unsigned)s_mask[mo] & ((1u << ty) - 1u));
+                }
+                int* o = a.triangles + tri * 3;
+                const bool odd = t >= 3;
+                o[0] = v[0]; o[1] = odd ? v[2] : v[1]; o[2] = odd ? v[1] : v[2];
+            }
+        }
+    }
+}
+
 long long voxel_count(int nx, int ny, int nz) {                  // MAX_VOXELS for anything at or beyond the bound, without overflow
     const long long xy = (long long)nx * ny;                     // < 2^62
     if (xy >= MAX_VOXELS || nz > MAX_VOXELS / xy) return MAX_VOXELS;
@@ -370,5 +619,51 @@ extern "C" int mr_tsdf_extract_f32(const float* tsdf, const float* weight, const
     a.records = records; a.capacity = records ? capacity_records : 0;
     a.cursor = reinterpret_cast<unsigned long long*>(cursor);
     hipLaunchKernelGGL(tsdf_extract_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+namespace {
+
+// the checks the two mesh entries share; fills what both kernels read
+int mesh_args(MeshArgs& a, const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, const void* vertex_base,
+              const void* out, long long capacity, int64_t* cursor) {
+    if (bad_volume(tsdf, weight, nx, ny, nz) || !cursor || ((uintptr_t)cursor & 7)) return MR_ERR_BAD_ARGUMENT;
+    if (voxel_count(nx, ny, nz) >= (1ll << 31)) return MR_ERR_BAD_ARGUMENT;                     // vertex indices are int32
+    if (min_weight != min_weight || (out && capacity < 0)) return MR_ERR_BAD_ARGUMENT;
+    if ((((uintptr_t)vertex_base | (uintptr_t)out) & 3) || (out && !vertex_base)) return MR_ERR_BAD_ARGUMENT;
+    a.tsdf = tsdf; a.weight = weight; a.colour = nullptr;
+    a.nx = nx; a.ny = ny; a.nz = nz;
+    a.tiles_x = (nx + TX - 1) / TX; a.tiles_y = (ny + TY - 1) / TY;
+    a.ox = a.oy = a.oz = 0.0f; a.voxel = 1.0f; a.min_weight = min_weight;
+    a.vertices = nullptr; a.triangles = nullptr; a.vertex_base = nullptr;
+    a.capacity = out ? capacity : 0;
+    a.cursor = reinterpret_cast<unsigned long long*>(cursor);
+    return 0;
+}
+
+unsigned mesh_tiles(const MeshArgs& a) { return (unsigned)((long long)a.tiles_x * a.tiles_y * ((a.nz + TZ - 1) / TZ)); }   // < 2^31 voxels
+
+}  // namespace
+
+extern "C" int mr_tsdf_mesh_vertices_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                                         const float* origin, float voxel_size, float min_weight, float* vertices, int64_t capacity_vertices,
+                                         int32_t* vertex_base, int64_t* cursor, void* stream) {
+    MeshArgs a;
+    if (mesh_args(a, tsdf, weight, nx, ny, nz, min_weight, vertex_base, vertices, capacity_vertices, cursor)) return MR_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)colour & 3) || !origin || !(voxel_size > 0.0f)) return MR_ERR_BAD_ARGUMENT;
+    a.colour = reinterpret_cast<const unsigned*>(colour);
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.voxel = voxel_size;
+    a.vertices = vertices; a.vertex_base = vertex_base;
+    hipLaunchKernelGGL(tsdf_mesh_vertices_kernel, dim3(mesh_tiles(a)), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_mesh_triangles_f32(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float min_weight,
+                                          const int32_t* vertex_base, int32_t* triangles, int64_t capacity_triangles, int64_t* cursor,
+                                          void* stream) {
+    MeshArgs a;
+    if (mesh_args(a, tsdf, weight, nx, ny, nz, min_weight, vertex_base, triangles, capacity_triangles, cursor)) return MR_ERR_BAD_ARGUMENT;
+    a.triangles = triangles; a.vertex_base = const_cast<int*>(vertex_base);
+    hipLaunchKernelGGL(tsdf_mesh_triangles_kernel, dim3(mesh_tiles(a)), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

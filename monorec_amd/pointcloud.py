@@ -19,6 +19,7 @@ pointcloud_monorec_tmvo.json) with the data source on the device too:
 import ctypes
 from array import array
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -53,6 +54,25 @@ def write_ply(file, data):
         data.tofile(file)
     else:
         file.write(data.tobytes())
+
+
+def write_mesh_ply(file, vertices, triangles):
+    """A triangle mesh as a binary little-endian .ply: `write_ply`'s six float vertex properties, then `element face M` with
+    `property list uchar int vertex_indices` (13 bytes per triangle).  `vertices`: (n, 6) fp32 numpy array x y z red green blue,
+    `triangles`: (m, 3) integer numpy array of indices into it (what monorec_amd.tsdf_fusion.TSDFVolume.mesh returns, on the host)."""
+    vertices = np.ascontiguousarray(vertices, dtype="<f4").reshape(-1, 6)
+    triangles = np.asarray(triangles).reshape(-1, 3)
+    if len(triangles) and (triangles.min() < 0 or triangles.max() >= len(vertices)):
+        raise ValueError(f"write_mesh_ply: triangle indices outside the {len(vertices)} vertices")
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {len(vertices)}"]
+    lines += [f"property float {name}" for name in ("x", "y", "z", "red", "green", "blue")]
+    lines += [f"element face {len(triangles)}", "property list uchar int vertex_indices", "end_header"]
+    file.write(("\n".join(lines) + "\n").encode("ascii"))
+    file.write(vertices.tobytes())
+    faces = np.empty(len(triangles), dtype=[("n", "u1"), ("v", "<i4", (3,))])
+    faces["n"] = 3
+    faces["v"] = triangles
+    file.write(faces.tobytes())
 
 
 class PLYSaver(torch.nn.Module):

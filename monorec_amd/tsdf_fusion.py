@@ -1,5 +1,5 @@
 """TSDF fusion on the MI355X: the keyframes `tsdf_export` packs, integrated into a dense voxel volume in device memory, and the
-surface points at its zero crossings - the step the export's files were written for, without the files.
+surface at its zero crossings, as points or as a welded triangle mesh - the step the export's files were written for, without the files.
 
     from monorec_amd.tsdf_fusion import TSDFVolume, bounds_from_frusta, fuse_directory, run
     python -m monorec_amd.tsdf_fusion --config configs/test/pointcloud_monorec.json
@@ -11,14 +11,19 @@ surface points at its zero crossings - the step the export's files were written 
 arithmetic - a running average of the truncated signed distance along the camera's z axis - is written out operation by operation in
 include/monorec_hip.h and restated in numpy by tests/tsdf_fusion_ref.py; the device result equals it bit for bit.  `extract()` returns
 the points where an edge of the grid crosses zero between two seen voxels (`mr_tsdf_extract_f32`: count, then fill), as the x y z r g b
-records `pointcloud.PLYSaver` writes.  There is no CPU fallback: CPU tensors raise.
+records `pointcloud.PLYSaver` writes.  `mesh()` returns the same surface as an indexed triangle mesh (`mr_tsdf_mesh_vertices_f32`,
+`mr_tsdf_mesh_triangles_f32`: marching tetrahedra over the Kuhn split of every cube of eight voxels - six tetrahedra per cube, a
+16-case table instead of marching cubes' 256, no ambiguous cases, so the mesh is a closed 2-manifold wherever the voxels are seen,
+at the price of about twice the triangles of marching cubes).  Every vertex lies on one of seven edges its voxel owns, so the mesh
+comes out welded by construction, with no hashing and no sort; the vertices on the three axis edges are `extract()`'s records.  The
+rules are in include/monorec_hip.h, restated in numpy by tests/tsdf_mesh_ref.py.  There is no CPU fallback: CPU tensors raise.
 
 `run(config)` takes the configs of `pointcloud.run` / `tsdf_export.run` and drives the same pipelined loop
 (`tsdf_export.KeyframeStream`): per keyframe one pack launch into a staging slot on the device, per `fuse_batch` keyframes one
 integrate launch on the same stream; nothing is copied to the host before the surface is written.
 
-Not here: a triangle mesh (marching cubes over the saved volume - `save()` writes an .npz a mesher elsewhere can read); sparse or
-hashed volumes (the volume is dense, `max_bytes` bounds it); a cap on the weight; fusing across ranks (`run` is single-process)."""
+Not here: vertex normals, decimation or marching cubes for the mesh; sparse or hashed volumes (the volume is dense, `max_bytes` bounds
+it; `save()` writes it as an .npz); a cap on the weight; fusing across ranks (`run` is single-process)."""
 import ctypes
 import math
 import os
@@ -29,7 +34,7 @@ import torch
 
 from . import _lib
 from . import tsdf_export as tx
-from .pointcloud import write_ply
+from .pointcloud import write_mesh_ply, write_ply
 
 MAX_FRAMES = _lib.MR_TSDF_MAX_FRAMES          # keyframes per integrate launch
 TILE = _lib.MR_TSDF_TILE                      # (x, y, z) voxels of one workgroup of the integrate kernel: the unit of its frustum culling
@@ -266,6 +271,59 @@ class TSDFVolume:
                 write_ply(f, records.reshape(-1))
         return records.shape[0]
 
+    # -- the surface as a mesh
+    def _mesh_launches(self, min_weight, cursor, vertices=None, triangles=None, vertex_base=None):
+        """The two mesh entries on the current stream, the vertex one first: counting (no outputs) or filling."""
+        lib, nothing = _lib.load(), (None, 0)
+        base = vertex_base.data_ptr() if vertex_base is not None else None
+        out = nothing if vertices is None else (vertices.data_ptr(), vertices.shape[0])
+        if vertices is None or vertices.shape[0]:
+            _lib.check(lib.mr_tsdf_mesh_vertices_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), out[0], out[1], base,
+                                                     cursor.data_ptr(), self._stream()), "mr_tsdf_mesh_vertices_f32")
+        out = nothing if triangles is None else (triangles.data_ptr(), triangles.shape[0])
+        if triangles is None or triangles.shape[0]:
+            _lib.check(lib.mr_tsdf_mesh_triangles_f32(self.tsdf.data_ptr(), self.weight.data_ptr(), *self.dims, float(min_weight), base, out[0], out[1],
+                                                      cursor.data_ptr() + 8, self._stream()), "mr_tsdf_mesh_triangles_f32")
+
+    def mesh_counts(self, min_weight=0):
+        """(vertices, triangles) `mesh(min_weight)` would return: the two count launches and one read."""
+        cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._mesh_launches(min_weight, cursor)
+        n, m = cursor.tolist()
+        return int(n), int(m)
+
+    def mesh(self, min_weight=0):
+        """The zero-crossing surface between voxels of weight > min_weight as a welded triangle mesh on the device: vertices (n, 6) fp32
+        x y z red green blue - those on the grid's axis edges are `extract(min_weight)`'s records - and triangles (m, 3) int32 indices
+        into them, wound so that (b - a) x (c - a) points from inside (tsdf < 0) to outside.  Marching tetrahedra: closed wherever the
+        voxels are seen, about twice the triangles of marching cubes.  A count launch per array, one read of both counts, a fill launch per
+        array; 4 bytes per voxel of workspace for the time of the call.  The order of both arrays is unspecified."""
+        n, m = self.mesh_counts(min_weight)
+        if n >= 2 ** 31:
+            raise ValueError(f"monorec_amd.tsdf_fusion: a mesh of {n} vertices does not fit int32 indices; raise min_weight or mesh a part")
+        vertices = torch.empty(n, 6, dtype=torch.float32, device=self.device)
+        triangles = torch.empty(m, 3, dtype=torch.int32, device=self.device)
+        if n:
+            cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
+            vertex_base = torch.empty(self.tsdf.numel(), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                self._mesh_launches(min_weight, cursor, vertices, triangles, vertex_base)
+            if cursor.tolist() != [n, m]:
+                raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launches")
+            del vertex_base
+        return vertices, triangles
+
+    def save_mesh_ply(self, file, min_weight=0):
+        """The mesh as a binary .ply (`pointcloud.write_mesh_ply`) to a path or a binary file object.  Returns (vertices, triangles)."""
+        vertices, triangles = (t.cpu().numpy() for t in self.mesh(min_weight))
+        if hasattr(file, "write"):
+            write_mesh_ply(file, vertices, triangles)
+        else:
+            with open(file, "wb") as f:
+                write_mesh_ply(f, vertices, triangles)
+        return vertices.shape[0], triangles.shape[0]
+
     # -- the volume itself
     def grids(self):
         """Host copies shaped (nz, ny, nx): tsdf, weight, colour (nz, ny, nx, 4) or None."""
@@ -355,7 +413,8 @@ def fuse_directory(directory, volume=None, voxel_size=0.1, trunc=None, colour=Tr
 
 # ------------------------------------------------------------------------------------------ the runner
 def fusion_settings(config):
-    """The fusion keys of a runner config, checked: dict(voxel_size, trunc, bounds, max_bytes, fuse_batch, file_name, save_volume)."""
+    """The fusion keys of a runner config, checked: dict(voxel_size, trunc, bounds, max_bytes, fuse_batch, file_name, mesh_file_name,
+    save_volume)."""
     voxel = float(config.get("voxel_size", 0.1))
     trunc_voxels = float(config.get("trunc_voxels", 5))
     batch = int(config.get("fuse_batch", 4))
@@ -371,7 +430,8 @@ def fusion_settings(config):
     if bounds is not None:
         dims_of_bounds(bounds, voxel)
     return dict(voxel_size=voxel, trunc=trunc_voxels * voxel, bounds=bounds, max_bytes=int(config.get("tsdf_max_bytes", 8 << 30)),
-                fuse_batch=batch, file_name=config.get("file_name", "tsdf.ply"), save_volume=config.get("save_volume", None))
+                fuse_batch=batch, file_name=config.get("file_name", "tsdf.ply"), mesh_file_name=config.get("mesh_file_name", None),
+                save_volume=config.get("save_volume", None))
 
 
 class Fusion:
@@ -399,6 +459,7 @@ class Fusion:
                                  max_bytes=settings["max_bytes"])
         depth_bytes, colour_bytes = tx.packed_sizes(1, ch, cw)
         self._slots = [torch.empty(depth_bytes + colour_bytes, dtype=torch.uint8, device=stream.device) for _ in range(settings["fuse_batch"])]
+        self.mesh_counts = None                                # (vertices, triangles) of the mesh file, once `write()` has written one
 
     def shifted(self, k):
         """The intrinsics of the cropped image, as `save_intrinsics_for_tsdf` shifts them, on a copy."""
@@ -435,6 +496,8 @@ class Fusion:
         out_dir = self.config.get("output_dir", "saved")
         os.makedirs(out_dir, exist_ok=True)
         count = self.volume.save_ply(os.path.join(out_dir, self.settings["file_name"]))
+        if self.settings["mesh_file_name"] is not None:
+            self.mesh_counts = self.volume.save_mesh_ply(os.path.join(out_dir, self.settings["mesh_file_name"]))
         if self.settings["save_volume"] is not None:
             self.volume.save(self.settings["save_volume"])
         return count
@@ -443,7 +506,8 @@ class Fusion:
 def run(config, model=None, dataset=None, device="cuda:0"):
     """Fuse the keyframes of a config of `tsdf_export.run`'s shape (same `data_set`, `arch`, `start` / `end`, `roi`, `min_d` / `max_d`,
     `use_mask`) and write the surface points to `output_dir/file_name` (default `tsdf.ply`).  Optional keys: `voxel_size` (0.1),
-    `trunc_voxels` (5), `bounds` (else `bounds_from_frusta` over the window's exported keyframe poses and `max_d`; without both it
+    `trunc_voxels` (5), `mesh_file_name` (None; a name: the surface is also written as a triangle mesh, `TSDFVolume.save_mesh_ply`, next to
+    the points), `bounds` (else `bounds_from_frusta` over the window's exported keyframe poses and `max_d`; without both it
     raises), `tsdf_max_bytes`, `fuse_batch` (keyframes per integrate launch, default 4), `save_volume` (a path for `TSDFVolume.save`).
 
     Per keyframe `pack_frames` (vote, crop, thresholds: the depths are exactly the ones the export writes to the PNG) fills a staging slot
@@ -455,8 +519,12 @@ def run(config, model=None, dataset=None, device="cuda:0"):
 def main(argv=None):
     config, device = tx.load_config(argv, prog="python -m monorec_amd.tsdf_fusion",
                                     description="MonoRec keyframes fused into a TSDF volume on the device; the surface points as a .ply")
-    count = run(config, device=device)
+    fusion = Fusion(config, device=device).fuse()
+    count = fusion.write()
     print(f"{count} surface points written to {os.path.join(config.get('output_dir', 'saved'), config.get('file_name', 'tsdf.ply'))}")
+    if fusion.mesh_counts is not None:
+        print(f"{fusion.mesh_counts[0]} vertices and {fusion.mesh_counts[1]} triangles written to "
+              f"{os.path.join(config.get('output_dir', 'saved'), config['mesh_file_name'])}")
 
 
 if __name__ == "__main__":

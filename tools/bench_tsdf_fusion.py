@@ -17,7 +17,11 @@ integrate   `mr_tsdf_integrate_f32` alone: 256 x 512 frames into a 512 x 512 x 1
 loop        `tsdf_fusion.Fusion` (the stages of `tsdf_fusion.run`) at c2 (B1 256 x 512 F2 D32, seeded weights) over keyframes
             resident on the device (eight samples, the poses advancing 0.1 m per keyframe), next to `tsdf_export.run(export=False)`
             and the file-writing runner, interleaved, `--repeats` timed runs each after one warm-up run of 24 keyframes; host clock,
-            every stage ended by a device synchronise; median and range of keyframes/s."""
+            every stage ended by a device synchronise; median and range of keyframes/s.  `seconds_last_run` holds the stages of the last
+            run: setup, loop, extract (points to a file) and mesh (`TSDFVolume.mesh()`, on the device).
+mesh        `--mesh-json FILE` alone (profiles/tsdf_mesh_rate.json): the 512 x 512 x 128 volume after eight keyframes of the `culled` camera
+            with the wide intrinsics (a plane across the volume), `extract()` next to `mesh()`: host clock round the whole call, and
+            device events round each launch (direct calls of the C entries), median of `--repeats` after a warm-up."""
 import argparse
 import json
 import os
@@ -206,6 +210,8 @@ def loop_rows(keyframes, repeats):
             lap("loop")
             info["surface_points"] = fusion.write()
             lap("extract")
+            info["mesh"] = [int(t.shape[0]) for t in fusion.volume.mesh()]
+            lap("mesh")
             return n, laps["loop"], laps
 
     runners = {"export_skipped": lambda n: export(n, False), "export_files": lambda n: export(n, True),
@@ -230,9 +236,80 @@ def loop_rows(keyframes, repeats):
     geometry = tsdf_fusion.bounds_from_frusta([datasets[keyframes].keyframe_geometry(i)[0] for i in range(keyframes)],
                                               datasets[keyframes].keyframe_geometry(0)[1], HEIGHT, WIDTH, 30, 0.1)
     return {"shape": "c2: B1 256x512 F2 D32", "keyframes": keyframes, "voxel_size": 0.1, "volume": list(tsdf_fusion.dims_of_bounds(geometry, 0.1)),
-            "surface_points": info.get("surface_points"),
+            "surface_points": info.get("surface_points"), "mesh_vertices_triangles": info.get("mesh"),
             "note": "fuse rows: keyframes / seconds of the loop alone (setup and extraction are in seconds_last_run); export rows: the whole run()",
             "rows": rows}
+
+
+# ------------------------------------------------------------------------------------------ extract and mesh
+def mesh_rows(repeats):
+    from monorec_amd import _lib
+    lib = _lib.load()
+    volume = tsdf_fusion.TSDFVolume(origin=(0.0, 0.0, 0.0), dims=DIMS, voxel_size=VOXEL, colour=True, device=DEV)
+    pose = torch.tensor([[0.0, 0, 1, 25.6], [0, 1, 0, 25.6], [-1, 0, 0, 6.4], [0, 0, 0, 1]])      # at the centre, looking along x
+    k = torch.tensor([[100.0, 0, 255.5], [0, 100.0, 127.5], [0, 0, 1]])
+    gen = torch.Generator().manual_seed(0)
+    images = torch.randint(0, 256, (8, HEIGHT, WIDTH, 3), generator=gen, dtype=torch.uint8).to(DEV)
+    depth = torch.full((8, HEIGHT, WIDTH), 2000, dtype=torch.int16, device=DEV)
+    poses = pose.repeat(8, 1, 1)
+    poses[:, 1, 3] += 0.01 * torch.arange(8)
+    volume.integrate(depth, images, poses, k)
+    voxels = DIMS[0] * DIMS[1] * DIMS[2]
+    points, (n, m) = volume.count(), volume.mesh_counts()
+    stream = torch.cuda.current_stream().cuda_stream
+    cursor = torch.zeros(1, dtype=torch.int64, device=DEV)
+    records = torch.empty(max(points, n), 6, device=DEV)
+    triangles = torch.empty(m, 3, dtype=torch.int32, device=DEV)
+    base = torch.empty(voxels, dtype=torch.int32, device=DEV)
+    common = (*volume._volume_args(), volume._origin, volume.voxel_size, 0.0)
+    plain = (volume.tsdf.data_ptr(), volume.weight.data_ptr(), *DIMS, 0.0)
+    launches = {
+        "extract_count": lambda: lib.mr_tsdf_extract_f32(*common, None, 0, cursor.data_ptr(), stream),
+        "extract_fill": lambda: lib.mr_tsdf_extract_f32(*common, records.data_ptr(), points, cursor.data_ptr(), stream),
+        "mesh_vertices_count": lambda: lib.mr_tsdf_mesh_vertices_f32(*common, None, 0, None, cursor.data_ptr(), stream),
+        "mesh_vertices_fill": lambda: lib.mr_tsdf_mesh_vertices_f32(*common, records.data_ptr(), n, base.data_ptr(), cursor.data_ptr(), stream),
+        "mesh_triangles_count": lambda: lib.mr_tsdf_mesh_triangles_f32(*plain, None, None, 0, cursor.data_ptr(), stream),
+        "mesh_triangles_fill": lambda: lib.mr_tsdf_mesh_triangles_f32(*plain, base.data_ptr(), triangles.data_ptr(), m, cursor.data_ptr(), stream),
+    }
+    tile = tsdf_fusion.TILE
+    staged = {"mesh_vertices": (tile[0] + 1) * (tile[1] + 1) * (tile[2] + 1), "mesh_triangles": (tile[0] + 2) * (tile[1] + 2) * (tile[2] + 2)}
+    rows = []
+    for name, launch in launches.items():
+        times = []
+        for i in range(repeats + 1):                                       # the first is the warm-up
+            cursor.zero_()
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            _lib.check(launch(), name)
+            end.record()
+            end.synchronize()
+            if i:
+                times.append(start.elapsed_time(end) * 1e3)
+        row = {"launch": name, "us_median": round(statistics.median(times), 1), "us_min": round(min(times), 1), "us_max": round(max(times), 1)}
+        kind = name.rsplit("_", 1)[0]
+        if kind in staged:                                                 # formula: tsdf + weight of the tile and its halo, once per workgroup
+            row["bytes_read_per_voxel_formula"] = round(8 * staged[kind] / (tile[0] * tile[1] * tile[2]), 2)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    calls = {"extract": lambda: volume.extract(), "mesh": lambda: volume.mesh()}
+    whole = {}
+    for name, call in calls.items():
+        times = []
+        for i in range(repeats + 1):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            call()
+            torch.cuda.synchronize()
+            if i:
+                times.append((time.perf_counter() - t) * 1e6)
+        whole[name] = {"us_median": round(statistics.median(times), 1), "us_min": round(min(times), 1), "us_max": round(max(times), 1)}
+        print(json.dumps({name: whole[name]}), flush=True)
+    return {"volume": list(DIMS), "voxel_size": VOXEL, "surface_points": points, "mesh_vertices": n, "mesh_triangles": m,
+            "volume_bytes": voxels * 12, "vertex_base_bytes": voxels * 4, "repeats": repeats,
+            "launch_us": "device events round one direct call of the C entry, the stream idle before it", "launches": rows,
+            "call_us": "host clock round the whole Python call (count launches, one read, allocation, fill launches), device synchronised",
+            "calls": whole, "mesh_over_extract": round(whole["mesh"]["us_median"] / whole["extract"]["us_median"], 2),
+            "bytes": "formula, not a counter: 8 bytes (tsdf, weight) per staged voxel; written vertex_base entries, colour reads and the records are not counted"}
 
 
 def main():
@@ -243,7 +320,14 @@ def main():
     ap.add_argument("--skip-loop", action="store_true")
     ap.add_argument("--trace-schedule", default=None, help="a path; alone: make the kernel-trace run's launches and write their schedule there")
     ap.add_argument("--kernel-trace", default=None, help="the *_kernel_trace.csv of that run: kernel times go into the rows")
+    ap.add_argument("--mesh-json", default=None, help="a path; alone: time extract() and mesh() on the 512 x 512 x 128 volume and write the figures there")
     a = ap.parse_args()
+    if a.mesh_json:
+        out = {"device": torch.cuda.get_device_name(0), "mesh": mesh_rows(max(a.repeats, 5))}
+        with open(a.mesh_json, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        return
     if a.trace_schedule and not a.kernel_trace:
         trace_schedule(a.trace_schedule)
         return
