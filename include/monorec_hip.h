@@ -604,7 +604,9 @@ int mr_depth_heads_f32(const mr_head_desc* heads, int32_t num_heads, float act_p
  * (model/metric_functions/sparse_metrics.py:136-252 with utils/util.py:36-118; pred_all_valid=True, no cv-mask):
  * prediction/target (batch,1,H,W) inverse depths; roi = {y0,y1,x0,x1} host ints or NULL; max_distance <= 0 = None.
  * sums: batch x 8 doubles on the device, per sample [n_valid, sum|dp-dg|/dg, sum(dp-dg)^2/dg, sum(dp-dg)^2,
- * sum(log dp - log dg)^2, n(thresh<1.25), n(thresh<1.25^2), n(thresh<1.25^3)]. */
+ * sum(log dp - log dg)^2, n(thresh<1.25), n(thresh<1.25^2), n(thresh<1.25^3)].
+ * relu / clamp_min / max keep NaN like torch (as in mr_metric_stage_sums_f32): a NaN prediction or target at an unmasked pixel makes
+ * the four error sums of its sample NaN and counts for none of the three thresholds - it is not scored as a depth of max_distance. */
 int mr_sparse_metric_sums_f32(const float* prediction, const float* target, int32_t batch, int32_t height,
                               int32_t width, const int32_t* roi, float max_distance, double* sums, void* stream);
 

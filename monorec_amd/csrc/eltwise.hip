@@ -4,6 +4,7 @@
 #include <math.h>
 
 #include "../../include/monorec_hip.h"
+#include "metric_math.h"
 
 namespace {
 
@@ -155,12 +156,12 @@ __global__ __launch_bounds__(1024) void sparse_metric_sums_kernel(const float* _
         float gi = g[y * W + x], pi = p[y * W + x];
         const bool masked = gi == 0.f || (inv_max_dist > 0.f && gi < inv_max_dist);
         if (masked) continue;
-        pi = fmaxf(pi, 0.f); gi = fmaxf(gi, 0.f);                               // get_positive_depth
-        if (inv_max_dist > 0.f) { pi = fmaxf(pi, inv_max_dist); gi = fmaxf(gi, inv_max_dist); }   // clamp_min
+        pi = relu_keep_nan(pi); gi = relu_keep_nan(gi);                         // get_positive_depth: a NaN stays a NaN, like torch.relu
+        if (inv_max_dist > 0.f) { pi = clamp_keep_nan(pi, inv_max_dist); gi = clamp_keep_nan(gi, inv_max_dist); }   // clamp_min
         const float dp = 1.0f / pi, dg = 1.0f / gi;                             // get_absolute_depth
         const float d = dp - dg;
         const float lg = logf(dp) - logf(dg);
-        const float th = fmaxf(dg / dp, dp / dg);
+        const float th = max_keep_nan(dg / dp, dp / dg);                        // torch.max keeps NaN
         acc[0] += 1.0;
         acc[1] += (double)(fabsf(d) / dg);
         acc[2] += (double)((d * d) / dg);

@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "../../include/monorec_hip.h"
+#include "metric_math.h"
 
 namespace {
 
@@ -188,10 +189,6 @@ struct StageArgs {
     int col[MR_MAX_METRIC_STAGES];
 };
 
-// relu and clamp_min as torch computes them: NaN passes through (fmaxf would drop it)
-__device__ inline float relu_keep_nan(float x) { return x != x ? x : fmaxf(x, 0.f); }
-__device__ inline float clamp_keep_nan(float x, float lo) { return x != x ? x : fmaxf(x, lo); }
-
 // One 1024-thread workgroup per sample, fp32 per element, fp64 accumulation, fixed reduction order.
 __global__ __launch_bounds__(kThreads) void metric_stage_sums_kernel(const float* __restrict__ pred, const float* __restrict__ gt,
                                                                       int H, int W, int y0, int y1, int x0, int x1,
@@ -236,7 +233,7 @@ __global__ __launch_bounds__(kThreads) void metric_stage_sums_kernel(const float
                         case 4: { const float lg = logf(dp) - logf(dg); q = lg * lg; break; }
                         default: {
                             const float a = dg / dp, c = dp / dg;
-                            const float th = (a != a || c != c) ? __uint_as_float(0x7fc00000u) : fmaxf(a, c);   // torch.max keeps NaN
+                            const float th = max_keep_nan(a, c);                       // torch.max keeps NaN
                             const float t = (col & 0xff) == 5 ? t1 : ((col & 0xff) == 6 ? t2 : t3);
                             q = th < t ? 1.f : 0.f;
                         }
