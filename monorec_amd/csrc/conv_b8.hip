@@ -23,13 +23,15 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdlib.h>
 #include <string.h>
 #include <type_traits>
+#ifdef MR_B8_ABLATE
+#include <stdlib.h>           // getenv: MR_B8_DBG / MR_B8_WGS
+#endif
 
 #include "../../include/monorec_hip.h"
+#include "conv_host.h"
 #include "lds_dma.h"
-#include "wino_host.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
@@ -71,14 +73,6 @@ struct B8Args {
 #else
 #define B8_DBG(bit) 0
 #endif
-
-__device__ __forceinline__ float act1(float v, int act, float p0) {
-    switch (act) {
-        case MR_ACT_RELU: return v > 0.f ? v : 0.f;
-        case MR_ACT_LEAKY_RELU: return v > 0.f ? v : v * p0;
-        default: return v;
-    }
-}
 
 __device__ __forceinline__ unsigned pack2(float a, float b) {          // two floats -> two bf16 (round to nearest even), a in the low half
     const bf16x2 h = __builtin_convertvector((f32x2){a, b}, bf16x2);
@@ -679,22 +673,11 @@ int launch8_mb(const B8Derived& dv, hipStream_t stream) {
     }
 }
 
-uint16_t bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x007fffffu)) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
 }  // namespace
 
 extern "C" size_t mr_b8_packed_weight_bytes(int32_t out_channels, const int32_t* src_channels, int32_t num_src, int32_t kh, int32_t kw, int32_t mb) {
     if (!src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mb8(mb) || out_channels < 1 || kh < 1 || kw < 1) return 0;
-    int nchunks = 0;
-    for (int s = 0; s < num_src; ++s) nchunks += ((src_channels[s] + 7) / 8 + 3) / 4;
-    const int groups = ((out_channels + 15) / 16 + mb - 1) / mb;
-    return (size_t)groups * nchunks * kh * kw * mb * 1024;
+    return conv_packed_fragments<32, 32>(out_channels, src_channels, num_src, kh, kw, mb) * 1024;
 }
 
 // weight: (out_channels, sum(src_channels), kh, kw) fp32, nn.Conv2d layout.  Stream: [cout group of 16 mb][chunk of 32 channels, source-major]
@@ -704,29 +687,10 @@ extern "C" int mr_b8_pack_weights(const float* weight, int32_t out_channels, con
                                   int32_t mb, void* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES || !valid_mb8(mb) || out_channels < 1 || kh < 1 || kw < 1)
         return MR_ERR_BAD_ARGUMENT;
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
-    const int taps = kh * kw;
-    const int groups = ((out_channels + 15) / 16 + mb - 1) / mb;
     uint16_t* o = (uint16_t*)dst;
-    for (int g = 0; g < groups; ++g) {
-        int cin_off = 0;
-        for (int s = 0; s < num_src; ++s) {
-            const int nch = ((src_channels[s] + 7) / 8 + 3) / 4;
-            for (int q = 0; q < nch; ++q)
-                for (int tap = 0; tap < taps; ++tap)
-                    for (int m = 0; m < mb; ++m)
-                        for (int lane = 0; lane < 64; ++lane)
-                            for (int e = 0; e < 8; ++e) {
-                                const int cout = (g * mb + m) * 16 + (lane & 15);
-                                const int cl = q * 32 + (lane >> 4) * 8 + e;
-                                float v = 0.f;
-                                if (cout < out_channels && cl < src_channels[s]) v = weight[((size_t)cout * cin_total + (cin_off + cl)) * taps + tap];
-                                *o++ = bf16_rne(v);
-                            }
-            cin_off += src_channels[s];
-        }
-    }
+    conv_pack_walk<32, 32>(weight, out_channels, src_channels, num_src, kh, kw, mb, 32, [&](int blk, auto w) {
+        for (int e = 0; e < 8; ++e) *o++ = bf16_rne(w(blk * 8 + e));
+    });
     return 0;
 }
 

@@ -27,14 +27,6 @@
 MR_HD static inline int mr_pad4(int c) { return (c + 3) & ~3; }
 MR_HD static inline int mr_ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// number of K chunks for a source with `c` real channels when chunks hold `ck` channels
-MR_HD static inline int mr_chunks_of(int c, int ck) { return mr_ceil_div(mr_pad4(c), ck); }
-
-// floats of packed weights of one (cout group, chunk): `ckq` = channels of this chunk (multiple of 4)
-MR_HD static inline int64_t mr_chunk_weight_floats(int ckq, int taps, int mb) {
-    return (int64_t)taps * (ckq / 4) * mb * 64;
-}
-
 // ---- bf16 MFMA mode (v_mfma_f32_16x16x16_bf16: weights stored as bf16, activations rounded to bf16 when the B fragment is
 // formed, fp32 accumulate).  One k-step = 16 input channels of one tap; sources are padded to multiples of 16.  Lane
 // (l&15 = cout, g = l>>4) holds, as its 4 consecutive k elements j = 0..3, channels c0 + 16*c16 + 4*j + g - element j of

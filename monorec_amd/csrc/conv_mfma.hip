@@ -28,14 +28,14 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string.h>
-#include <stdlib.h>
-#include <atomic>
 #include <type_traits>
+#ifdef MR_CONV_TIMELINE
+#include <stdlib.h>           // getenv: MR_CONV_DBG
+#endif
 
 #include "../../include/monorec_hip.h"
-#include "conv_layout.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "conv_host.h"
+#include "lds_dma.h"          // the *_raw DMA forms: this file passes the scalar operands as they are
 
 #define MR_MAX_PPT 6   // tile positions staged per thread (ceil(IH*IW / 256))
 #define MR_MAX_G4 4    // 16-byte groups per lane per channel plane in the dwordx4 DMA path
@@ -145,34 +145,22 @@ __device__ __forceinline__ void kstep(f32x4 (&acc)[MB][NB], const float* __restr
         for (int i = 0; i < NB; ++i) acc[m][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[m], bv[i], acc[m][i], 0, 0, 0);
 }
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+// the [MB][NB] accumulator tiles
+template <int MB, int NB>
+__device__ __forceinline__ void acc_zero(f32x4 (&acc)[MB][NB]) {
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) acc[m][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+}
+template <int MB, int NB>
+__device__ __forceinline__ void acc_add(f32x4 (&acc)[MB][NB], const f32x4 (&other)[MB][NB]) {
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) acc[m][i] += other[m][i];
+}
 
-// ---- LDS-DMA, issued through inline asm (why, and what the statements pad for: lds_dma.h) ------------------
-// This file keeps its own helpers: they pass the scalar operands as they are, without the readfirstlane of lds_dma.h.
-__device__ __forceinline__ void dma_buffer_dword(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dword %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-__device__ __forceinline__ void dma_global_x1(unsigned lds_byte_addr, const float* g) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
 // Ablation / timeline switches exist only in the diagnostic library (python -m monorec_amd.build --timeline, -DMR_CONV_TIMELINE):
 // in the product kernel MR_DBG(bit) is a compile-time 0 - carried as run-time tests they cost ~3 % keyframes/s.
 #ifdef MR_CONV_TIMELINE
@@ -194,18 +182,6 @@ __device__ __forceinline__ void dbg_stamp(const ConvKArgs& a, int k) {
         ((unsigned long long*)base)[wg * 12 + k] = (k == 9 || k == 10) ? clock64() : wall_clock64();
     }
 #endif
-}
-
-__device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ i32x4 make_srd(const void* base, int bytes) {
-    const unsigned long long p = (unsigned long long)base;
-    i32x4 r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)p);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(p >> 32) & 0xffffu));
-    r.z = __builtin_amdgcn_readfirstlane(bytes);
-    r.w = 0x00020000;
-    return r;
 }
 
 // K-chunk cursor over the concatenated sources (chunks never straddle two sources).
@@ -237,9 +213,9 @@ __device__ __forceinline__ void issue_chunk(const ConvKArgs& a, const ChunkCurso
     const int wfloats = T * ck * MB * (a.bf16 ? 8 : 16);
     const float* wsrc = wgrp + c.woff;
     const int n1k = MR_DBG(4) ? 0 : wfloats >> 8;   // 1 KiB pieces (64 lanes x 16 B)
-    for (int kb = wave; kb < n1k; kb += nwave) dma_global_x4(ldsW_addr + kb * 1024, wsrc + kb * 256 + lane * 4);
+    for (int kb = wave; kb < n1k; kb += nwave) dma_global_x4_raw(ldsW_addr + kb * 1024, wsrc + kb * 256 + lane * 4);
     const int nfrag = MR_DBG(4) ? 0 : wfloats >> 6; // tail: 256 B pieces (64 lanes x 4 B)
-    for (int fr = (n1k << 2) + wave; fr < nfrag; fr += nwave) dma_global_x1(ldsW_addr + fr * 256, wsrc + fr * 64 + lane);
+    for (int fr = (n1k << 2) + wave; fr < nfrag; fr += nwave) dma_global_x1_raw(ldsW_addr + fr * 256, wsrc + fr * 64 + lane);
 
     const int creal = a.src_c[c.s] - c.c0;                            // real (unpadded) channels left
     const int sbase_bytes = (b * a.src_c[c.s] + c.c0) * HsWs * 4;     // byte offset of channel c0 of sample b
@@ -255,7 +231,7 @@ __device__ __forceinline__ void issue_chunk(const ConvKArgs& a, const ChunkCurso
 #pragma unroll
             for (int i = 0; i < MR_MAX_G4; ++i) {
                 if (i < a.g4pt && voff4[i] != -2)                      // -2: lane beyond the tile rows (EXEC off)
-                    dma_buffer_x4(lplane + i * 1024, cok ? voff4[i] : -1, srd, so);
+                    dma_buffer_x4_raw(lplane + i * 1024, cok ? voff4[i] : -1, srd, so);
             }
         }
     } else if (DMA_IN) {
@@ -267,7 +243,7 @@ __device__ __forceinline__ void issue_chunk(const ConvKArgs& a, const ChunkCurso
                 const unsigned lrow = ldsI_addr + (wave * 64 + 256 * j) * 4;   // wave-uniform; lane l lands at +4l
                 for (int cc = 0; cc < ck; ++cc) {
                     const int vo = cc < creal ? voff : -1;            // padded channels read as zero
-                    dma_buffer_dword(lrow + cc * a.PLANE * 4, vo, srd, sbase_bytes + cc * HsWs * 4);
+                    dma_buffer_dword_raw(lrow + cc * a.PLANE * 4, vo, srd, sbase_bytes + cc * HsWs * 4);
                 }
             }
         }
@@ -298,12 +274,7 @@ __device__ __forceinline__ void sweep_chunk(const ConvKArgs& a, f32x4 (&acc)[MB]
     // (even / odd channel quads) keep two MFMAs in flight; they are added once per chunk.
     constexpr bool DUAL = MB * NB == 1;
     f32x4 acc2[MB][NB];
-    if (DUAL) {
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int i = 0; i < NB; ++i) acc2[m][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
+    if (DUAL) acc_zero(acc2);
     for (int kh = 0; kh < KH; ++kh) {
         for (int kw = 0; kw < KW; ++kw) {
             const int tapoff = kh * a.IWa + kw;
@@ -318,12 +289,7 @@ __device__ __forceinline__ void sweep_chunk(const ConvKArgs& a, f32x4 (&acc)[MB]
             for (; c4 < ck4; ++c4) kstep<MB, NB>(acc, wt, ldsI, lbase, c4, c4 * 4 * a.PLANE + tapoff);
         }
     }
-    if (DUAL) {
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int i = 0; i < NB; ++i) acc[m][i] += acc2[m][i];
-    }
+    if (DUAL) acc_add(acc, acc2);
 }
 
 // ---- software-pipelined fp32 sweep (round 6) -----------------------------------------------------------------------
@@ -406,12 +372,7 @@ __device__ __forceinline__ void sweep_chunk_pipe_pl(const ConvKArgs& a, f32x4 (&
                                                     const int (&lbase)[NB], int ck4, int lane, int KH, int KW) {
     constexpr bool DUAL = MB * NB == 1;
     f32x4 acc2[MB][NB];
-    if (DUAL) {
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int i = 0; i < NB; ++i) acc2[m][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
+    if (DUAL) acc_zero(acc2);
     const int nq = ck4 >> 2;
     const int ngroups = KH * KW * nq;
     const int plane4 = PL ? 4 * PL : 4 * a.PLANE, plane16 = 4 * plane4;
@@ -448,12 +409,7 @@ __device__ __forceinline__ void sweep_chunk_pipe_pl(const ConvKArgs& a, f32x4 (&
     } else {
         kgroup_mma<MB, NB, DUAL>(acc, acc2, f0);
     }
-    if (DUAL) {
-#pragma unroll
-        for (int m = 0; m < MB; ++m)
-#pragma unroll
-            for (int i = 0; i < NB; ++i) acc[m][i] += acc2[m][i];
-    }
+    if (DUAL) acc_add(acc, acc2);
 }
 
 // plane pitches with their own instantiation of the sweep: the pitches of the c2 / c3 tables' direct-kernel schedules by multiply-adds
@@ -492,7 +448,6 @@ __device__ __forceinline__ void sweep_chunk_kws(const ConvKArgs& a, f32x4 (&acc)
 
 // ---- bf16 MFMA sweep: one v_mfma_f32_16x16x16_bf16 per (cout block, pixel block) and 16 input channels of a tap -------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ s16x4 pack_bf16x4(float x0, float x1, float x2, float x3) {   // round to nearest even
@@ -502,6 +457,10 @@ __device__ __forceinline__ s16x4 pack_bf16x4(float x0, float x1, float x2, float
     u.h[0] = lo; u.h[1] = hi;
     return u.v;
 }
+__device__ __forceinline__ s16x4 pack_bf16x4(f32x4 x) { return pack_bf16x4(x[0], x[1], x[2], x[3]); }
+
+// B fragment of a 16-channel step as fp32: p = channel (lane >> 4) = g of the step; the lane's four k elements are channels g, 4+g, 8+g, 12+g
+__device__ __forceinline__ f32x4 bfrag4(const float* p, int plane4) { return (f32x4){p[0], p[plane4], p[2 * plane4], p[3 * plane4]}; }
 
 template <int MB, int NB>
 __device__ __forceinline__ void kstep_bf16(f32x4 (&acc)[MB][NB], const float* __restrict__ wt, const float* __restrict__ ldsI,
@@ -515,10 +474,7 @@ __device__ __forceinline__ void kstep_bf16(f32x4 (&acc)[MB][NB], const float* __
         av[m] = u.v;
     }
 #pragma unroll
-    for (int i = 0; i < NB; ++i) {
-        const float* p = ldsI + lbase[i] + off;                            // channel (lane >> 4) of this 16-channel step
-        bv[i] = pack_bf16x4(p[0], p[plane4], p[2 * plane4], p[3 * plane4]);   // channels g, 4+g, 8+g, 12+g
-    }
+    for (int i = 0; i < NB; ++i) bv[i] = pack_bf16x4(bfrag4(ldsI + lbase[i] + off, plane4));
 #pragma unroll
     for (int m = 0; m < MB; ++m)
 #pragma unroll
@@ -544,9 +500,9 @@ __device__ __forceinline__ void kstep_bf16_k32(f32x4 (&acc)[MB][NB], const float
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-        const float* p = ldsI + lbase[i] + off;                            // channel (lane >> 4) of step c16; step c16 + 1 is 16 planes on
-        const s16x4 lo = pack_bf16x4(p[0], p[plane4], p[2 * plane4], p[3 * plane4]);
-        const s16x4 hi = pack_bf16x4(p[4 * plane4], p[5 * plane4], p[6 * plane4], p[7 * plane4]);
+        const float* p = ldsI + lbase[i] + off;                            // step c16; step c16 + 1 is 16 planes on
+        const s16x4 lo = pack_bf16x4(bfrag4(p, plane4));
+        const s16x4 hi = pack_bf16x4(bfrag4(p + 4 * plane4, plane4));
         bv[i] = (s16x8v){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     }
 #pragma unroll
@@ -554,23 +510,6 @@ __device__ __forceinline__ void kstep_bf16_k32(f32x4 (&acc)[MB][NB], const float
 #pragma unroll
         for (int i = 0; i < NB; ++i)
             acc[m][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av[m]), __builtin_bit_cast(bf16x8, bv[i]), acc[m][i], 0, 0, 0);
-}
-
-template <int MB, int NB>
-__device__ __forceinline__ void sweep_chunk_bf16(const ConvKArgs& a, f32x4 (&acc)[MB][NB], const float* ldsI, const float* ldsW,
-                                                 const int (&lbase)[NB], int ck16, int lane, int KH, int KW) {
-    const float* wl = ldsW + lane * 2;
-    const int plane4 = 4 * a.PLANE;
-    for (int kh = 0; kh < KH; ++kh) {
-        for (int kw = 0; kw < KW; ++kw) {
-            const int tapoff = kh * a.IWa + kw;
-            const float* wt = wl + (kh * KW + kw) * ck16 * (MB * 128);
-            int c16 = 0;
-            for (; c16 + 2 <= ck16; c16 += 2)       // pairs of 16-channel steps on the K = 32 instruction
-                kstep_bf16_k32<MB, NB>(acc, wt, ldsI, lbase, c16, c16 * 16 * a.PLANE + tapoff, plane4);
-            for (; c16 < ck16; ++c16) kstep_bf16<MB, NB>(acc, wt, ldsI, lbase, c16, c16 * 16 * a.PLANE + tapoff, plane4);
-        }
-    }
 }
 
 // ---- bf16x3 sweep (MR_COMPUTE_BF16X3): fp32-class accuracy on the bf16 matrix cores ------------------------------------------
@@ -598,11 +537,10 @@ __device__ __forceinline__ void kstep_bf16x3(f32x4 (&acc)[MB][NB], const float* 
     }
 #pragma unroll
     for (int i = 0; i < NB; ++i) {
-        const float* p = ldsI + lbase[i] + off;
-        const float x0 = p[0], x1 = p[plane4], x2 = p[2 * plane4], x3 = p[3 * plane4];
-        bh[i] = pack_bf16x4(x0, x1, x2, x3);
-        bl[i] = pack_bf16x4(x0 - bf16_bits_to_f32(bh[i][0]), x1 - bf16_bits_to_f32(bh[i][1]),
-                            x2 - bf16_bits_to_f32(bh[i][2]), x3 - bf16_bits_to_f32(bh[i][3]));
+        const f32x4 x = bfrag4(ldsI + lbase[i] + off, plane4);
+        bh[i] = pack_bf16x4(x);
+        bl[i] = pack_bf16x4(x[0] - bf16_bits_to_f32(bh[i][0]), x[1] - bf16_bits_to_f32(bh[i][1]),
+                            x[2] - bf16_bits_to_f32(bh[i][2]), x[3] - bf16_bits_to_f32(bh[i][3]));
     }
 #pragma unroll
     for (int m = 0; m < MB; ++m)
@@ -614,16 +552,25 @@ __device__ __forceinline__ void kstep_bf16x3(f32x4 (&acc)[MB][NB], const float* 
         }
 }
 
-template <int MB, int NB>
-__device__ __forceinline__ void sweep_chunk_bf16x3(const ConvKArgs& a, f32x4 (&acc)[MB][NB], const float* ldsI, const float* ldsW,
-                                                   const int (&lbase)[NB], int ck16, int lane, int KH, int KW) {
-    const float* wl = ldsW + lane * 4;
+// The sweep of both bf16 modes: X3 false = bf16 (A fragments of 128 floats, pairs of 16-channel steps on the K = 32 instruction),
+// true = bf16x3 (A fragments of 256 floats: hi and lo)
+template <int MB, int NB, bool X3>
+__device__ __forceinline__ void sweep_chunk_bf16(const ConvKArgs& a, f32x4 (&acc)[MB][NB], const float* ldsI, const float* ldsW,
+                                                 const int (&lbase)[NB], int ck16, int lane, int KH, int KW) {
+    constexpr int FRAG = X3 ? 256 : 128;
+    const float* wl = ldsW + lane * (FRAG / 64);
     const int plane4 = 4 * a.PLANE;
     for (int kh = 0; kh < KH; ++kh) {
         for (int kw = 0; kw < KW; ++kw) {
             const int tapoff = kh * a.IWa + kw;
-            const float* wt = wl + (kh * KW + kw) * ck16 * (MB * 256);
-            for (int c16 = 0; c16 < ck16; ++c16) kstep_bf16x3<MB, NB>(acc, wt, ldsI, lbase, c16, c16 * 16 * a.PLANE + tapoff, plane4);
+            const float* wt = wl + (kh * KW + kw) * ck16 * (MB * FRAG);
+            if (X3) {
+                for (int c16 = 0; c16 < ck16; ++c16) kstep_bf16x3<MB, NB>(acc, wt, ldsI, lbase, c16, c16 * 16 * a.PLANE + tapoff, plane4);
+            } else {
+                int c16 = 0;
+                for (; c16 + 2 <= ck16; c16 += 2) kstep_bf16_k32<MB, NB>(acc, wt, ldsI, lbase, c16, c16 * 16 * a.PLANE + tapoff, plane4);
+                for (; c16 < ck16; ++c16) kstep_bf16<MB, NB>(acc, wt, ldsI, lbase, c16, c16 * 16 * a.PLANE + tapoff, plane4);
+            }
         }
     }
 }
@@ -715,7 +662,7 @@ __global__ __launch_bounds__(WV * 64) void conv_mfma_kernel(const ConvKArgs a) {
 
     f32x4 acc[MB][NB];
     f32x4 acck[MB][NB];                                // KWS: second partial sum (alternating k-steps keep two MFMA chains in flight)
-#pragma unroll
+#pragma unroll                                         // (not acc_zero: through the helper the register allocation of every kernel moves)
     for (int m = 0; m < MB; ++m)
 #pragma unroll
         for (int i = 0; i < NB; ++i) { acc[m][i] = (f32x4){0.f, 0.f, 0.f, 0.f}; acck[m][i] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
@@ -750,8 +697,7 @@ __global__ __launch_bounds__(WV * 64) void conv_mfma_kernel(const ConvKArgs a) {
         if (stamp) dbg_stamp(a, 5);
         if (!MR_DBG(1)) {
             if (KWS) sweep_chunk_kws<MB, NB, WV>(a, acc, acck, bcur, bcur + ioff, lbase, ck4, lane, wave, KH, KW);
-            else if (BF16 == 2) sweep_chunk_bf16x3<MB, NB>(a, acc, bcur, bcur + ioff, lbase, ck4 >> 2, lane, KH, KW);
-            else if (BF16 == 1) sweep_chunk_bf16<MB, NB>(a, acc, bcur, bcur + ioff, lbase, ck4 >> 2, lane, KH, KW);
+            else if (BF16) sweep_chunk_bf16<MB, NB, BF16 == 2>(a, acc, bcur, bcur + ioff, lbase, ck4 >> 2, lane, KH, KW);
             else if ((ck4 & 3) == 0) sweep_chunk_pipe<MB, NB>(a, acc, bcur, bcur + ioff, lbase, ck4, lane, KH, KW);
             else sweep_chunk<MB, NB>(a, acc, bcur, bcur + ioff, lbase, ck4, lane, KH, KW);
         }
@@ -769,7 +715,7 @@ __global__ __launch_bounds__(WV * 64) void conv_mfma_kernel(const ConvKArgs a) {
         for (int m = 0; m < MB; ++m)
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
-                acc[m][i] += acck[m][i];
+                acc[m][i] += acck[m][i];               // (not acc_add ahead of the loop: that moves the register allocation of the KWS kernels)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) lds[((wave * (MB * NB) + m * NB + i) * 4 + r) * 64 + lane] = acc[m][i][r];
             }
@@ -952,6 +898,16 @@ struct Derived {
 bool valid_mb(int mb) { return mb == 1 || mb == 2 || mb == 3 || mb == 4 || mb == 6; }
 bool valid_ck(int ck) { return ck == 8 || ck == 16 || ck == 32 || ck == 64 || ck == 128; }
 
+// LDS pitch of a channel plane and staging positions per thread of the IH x IWa tile
+void set_plane(ConvKArgs& k) {
+    int plane = k.IH * k.IWa;
+    if (k.SW == 1) { while ((plane & 31) != 16) ++plane; }
+    else if (k.dma_x4) { plane = (plane + 3) & ~3; }          // 16-byte rows win over the odd-stride bank trick
+    else { plane |= 1; }
+    k.PLANE = plane;
+    k.ppt = mr_ceil_div(k.IH * k.IWa, 256);
+}
+
 int derive(const mr_conv_desc* d, Derived* out) {
     if (!d || d->num_src < 1 || d->num_src > MR_MAX_SOURCES) return MR_ERR_BAD_ARGUMENT;
     if (d->batch < 1 || d->kh < 1 || d->kw < 1 || d->stride_h < 1 || d->stride_w < 1) return MR_ERR_BAD_ARGUMENT;
@@ -1046,17 +1002,16 @@ int derive(const mr_conv_desc* d, Derived* out) {
         if (k.xsh[p] > xsh_max) xsh_max = k.xsh[p];
     }
     k.IWa = k.dma_x4 ? ((xsh_max + k.IW + 3) & ~3) : k.IW;
-    int plane = k.IH * k.IWa;
-    if (k.SW == 1) { while ((plane & 31) != 16) ++plane; }
-    else if (k.dma_x4) { plane = (plane + 3) & ~3; }          // 16-byte rows win over the odd-stride bank trick
-    else { plane |= 1; }
-    k.PLANE = plane;
-    k.ppt = mr_ceil_div(k.IH * k.IWa, 256);
+    set_plane(k);
     k.g4pt = mr_ceil_div(k.IH * (k.IWa >> 2), 64);
-    if (!(k.dma_x4 && k.g4pt <= MR_MAX_G4) && k.ppt > MR_MAX_PPT) return MR_ERR_UNSUPPORTED;   // per-position staging only
-    if (k.dma_x4 && k.g4pt > MR_MAX_G4) { k.dma_x4 = 0; k.IWa = k.IW; for (int p = 0; p < 4; ++p) k.xsh[p] = 0;
-        plane = k.IH * k.IW; if (k.SW == 1) { while ((plane & 31) != 16) ++plane; } else { plane |= 1; }
-        k.PLANE = plane; k.ppt = mr_ceil_div(k.IH * k.IW, 256); if (k.ppt > MR_MAX_PPT) return MR_ERR_UNSUPPORTED; }
+    const bool x4_fits = k.dma_x4 && k.g4pt <= MR_MAX_G4;
+    if (!x4_fits && k.ppt > MR_MAX_PPT) return MR_ERR_UNSUPPORTED;   // per-position staging only
+    if (k.dma_x4 && !x4_fits) {                       // too many 16-byte groups per lane: the dword form of the unaligned tile (never more positions than the aligned one)
+        k.dma_x4 = 0;
+        k.IWa = k.IW;
+        for (int p = 0; p < 4; ++p) k.xsh[p] = 0;
+        set_plane(k);
+    }
     k.ksplit = d->split_k; k.nchunks = nchunks; k.batch = d->batch; k.ws = d->workspace;
     const int taps = k.KH * k.KW;
     for (int p = 0; p < nphase; ++p) k.wgroup_stride[p] = (long long)k.KHp[p] * k.KWp[p] * cpad_total * mb * (bf16 == 1 ? 8 : 16);
@@ -1071,7 +1026,7 @@ int derive(const mr_conv_desc* d, Derived* out) {
     // ring's bookkeeping costs the one-chunk layers 1 %: the two-buffer loop is 4 % faster over the direct launches of a c2 keyframe, also on
     // the layers whose table entries had chosen 3 buffers; tools/sessions/r06_s4.sh, r06_s19.sh.)
     const int nbuf = mr_ceil_div(nchunks, d->split_k) > 1 ? 2 : 1;
-    out->lds_bytes = nbuf * ((size_t)k.CK * plane + (size_t)k.wmax_floats) * sizeof(float);
+    out->lds_bytes = nbuf * ((size_t)k.CK * k.PLANE + (size_t)k.wmax_floats) * sizeof(float);
     if (kws && out->lds_bytes < (size_t)wv * mb * nb * 1024) out->lds_bytes = (size_t)wv * mb * nb * 1024;   // reduction scratch
     if (out->lds_bytes > 160 * 1024) return MR_ERR_LDS_BUDGET;
     k.gpr_magic = 65536u / (unsigned)(k.IWa >> 2 > 0 ? k.IWa >> 2 : 1) + 1u;
@@ -1095,20 +1050,7 @@ int derive(const mr_conv_desc* d, Derived* out) {
 
 template <int MB, int NB, bool DMA_IN, int WV, int BF16, bool KWS = false>
 int launch(const Derived& dv, hipStream_t stream) {
-    // raise the dynamic-LDS ceiling once per instantiation AND device (the attribute lives in the device's code object:
-    // a process that drives several GPUs - nn.DataParallel replicas - must set it on each)
-    static std::atomic<unsigned long long> attr_set{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<MB, NB, DMA_IN, WV, BF16, KWS>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, DMA_IN, WV, BF16, KWS>), dv.grid, dim3(WV * 64), dv.lds_bytes, stream, dv.k);
-    return (int)hipGetLastError();
+    return launch_lds_ceiling<conv_mfma_kernel<MB, NB, DMA_IN, WV, BF16, KWS>>(160 * 1024, dv.grid, dim3(WV * 64), dv.lds_bytes, stream, dv.k);
 }
 
 template <int MB, int NB>
@@ -1144,95 +1086,31 @@ int launch_nb(const Derived& dv, hipStream_t stream) {
 extern "C" size_t mr_conv_packed_weight_floats(int32_t out_channels, const int32_t* src_channels, int32_t num_src,
                                                int32_t kh, int32_t kw, int32_t mb, int32_t ck) {
     if (!src_channels || num_src < 1 || !valid_mb(mb) || !valid_ck(ck)) return 0;
-    const int groups = mr_ceil_div(mr_ceil_div(out_channels, 16), mb);
-    int cpad_total = 0;
-    for (int s = 0; s < num_src; ++s) cpad_total += mr_pad4(src_channels[s]);
-    return (size_t)groups * kh * kw * (cpad_total / 4) * mb * 64;
+    return conv_packed_fragments<4, 4>(out_channels, src_channels, num_src, kh, kw, mb) * 64;
 }
 
 extern "C" int mr_conv_pack_weights_f32(const float* weight, int32_t out_channels, const int32_t* src_channels,
                                         int32_t num_src, int32_t kh, int32_t kw, int32_t mb, int32_t ck, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES) return MR_ERR_BAD_ARGUMENT;
     if (!valid_mb(mb) || !valid_ck(ck)) return MR_ERR_BAD_ARGUMENT;
-    const int groups = mr_ceil_div(mr_ceil_div(out_channels, 16), mb);
-    const int taps = kh * kw;
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
-    size_t o = 0;
-    for (int g = 0; g < groups; ++g) {
-        int cin_off = 0;
-        for (int s = 0; s < num_src; ++s) {
-            const int cpad = mr_pad4(src_channels[s]);
-            for (int c0 = 0; c0 < cpad; c0 += ck) {
-                const int ckq = cpad - c0 < ck ? cpad - c0 : ck;
-                for (int tap = 0; tap < taps; ++tap)
-                    for (int c4 = 0; c4 < ckq / 4; ++c4)
-                        for (int m = 0; m < mb; ++m)
-                            for (int lane = 0; lane < 64; ++lane) {
-                                const int cout = (g * mb + m) * 16 + (lane & 15);
-                                const int cl = c0 + c4 * 4 + (lane >> 4);
-                                float v = 0.f;
-                                if (cout < out_channels && cl < src_channels[s])
-                                    v = weight[((size_t)cout * cin_total + (cin_off + cl)) * taps + tap];
-                                dst[o++] = v;
-                            }
-            }
-            cin_off += src_channels[s];
-        }
-    }
+    conv_pack_walk<4, 4>(weight, out_channels, src_channels, num_src, kh, kw, mb, ck, [&](int g, auto w) { *dst++ = w(g); });
     return 0;
 }
-
-namespace {
-uint16_t bf16_rne(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7f800000u) == 0x7f800000u && (u & 0x007fffffu)) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-}  // namespace
 
 extern "C" size_t mr_conv_packed_weight_floats_bf16(int32_t out_channels, const int32_t* src_channels, int32_t num_src,
                                                     int32_t kh, int32_t kw, int32_t mb, int32_t ck) {
     if (!src_channels || num_src < 1 || !valid_mb(mb) || !valid_ck(ck) || ck < 16) return 0;
-    const int groups = mr_ceil_div(mr_ceil_div(out_channels, 16), mb);
-    int cpad_total = 0;
-    for (int s = 0; s < num_src; ++s) cpad_total += mr_pad16(src_channels[s]);
-    return (size_t)groups * kh * kw * (cpad_total / 16) * mb * 128;
+    return conv_packed_fragments<16, 16>(out_channels, src_channels, num_src, kh, kw, mb) * 128;
 }
 
 extern "C" int mr_conv_pack_weights_bf16(const float* weight, int32_t out_channels, const int32_t* src_channels,
                                          int32_t num_src, int32_t kh, int32_t kw, int32_t mb, int32_t ck, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES) return MR_ERR_BAD_ARGUMENT;
     if (!valid_mb(mb) || !valid_ck(ck) || ck < 16) return MR_ERR_BAD_ARGUMENT;
-    const int groups = mr_ceil_div(mr_ceil_div(out_channels, 16), mb);
-    const int taps = kh * kw;
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
     uint16_t* o = (uint16_t*)dst;
-    for (int g = 0; g < groups; ++g) {
-        int cin_off = 0;
-        for (int s = 0; s < num_src; ++s) {
-            const int cpad = mr_pad16(src_channels[s]);
-            for (int c0 = 0; c0 < cpad; c0 += ck) {
-                const int ckq = cpad - c0 < ck ? cpad - c0 : ck;
-                for (int tap = 0; tap < taps; ++tap)
-                    for (int c16 = 0; c16 < ckq / 16; ++c16)
-                        for (int m = 0; m < mb; ++m)
-                            for (int lane = 0; lane < 64; ++lane)
-                                for (int j = 0; j < 4; ++j) {
-                                    const int cout = (g * mb + m) * 16 + (lane & 15);
-                                    const int cl = c0 + c16 * 16 + 4 * j + (lane >> 4);     // element j of lane group g: channel 4j+g
-                                    float v = 0.f;
-                                    if (cout < out_channels && cl < src_channels[s])
-                                        v = weight[((size_t)cout * cin_total + (cin_off + cl)) * taps + tap];
-                                    *o++ = bf16_rne(v);
-                                }
-            }
-            cin_off += src_channels[s];
-        }
-    }
+    conv_pack_walk<16, 16>(weight, out_channels, src_channels, num_src, kh, kw, mb, ck, [&](int g, auto w) {
+        for (int j = 0; j < 4; ++j) *o++ = bf16_rne(w(4 * j + g));      // element j of lane group g: channel 4j+g
+    });
     return 0;
 }
 
@@ -1245,41 +1123,18 @@ extern "C" int mr_conv_pack_weights_bf16x3(const float* weight, int32_t out_chan
                                            int32_t num_src, int32_t kh, int32_t kw, int32_t mb, int32_t ck, float* dst) {
     if (!weight || !dst || !src_channels || num_src < 1 || num_src > MR_MAX_SOURCES) return MR_ERR_BAD_ARGUMENT;
     if (!valid_mb(mb) || !valid_ck(ck) || ck < 16) return MR_ERR_BAD_ARGUMENT;
-    const int groups = mr_ceil_div(mr_ceil_div(out_channels, 16), mb);
-    const int taps = kh * kw;
-    int cin_total = 0;
-    for (int s = 0; s < num_src; ++s) cin_total += src_channels[s];
     uint16_t* o = (uint16_t*)dst;
-    for (int g = 0; g < groups; ++g) {
-        int cin_off = 0;
-        for (int s = 0; s < num_src; ++s) {
-            const int cpad = mr_pad16(src_channels[s]);
-            for (int c0 = 0; c0 < cpad; c0 += ck) {
-                const int ckq = cpad - c0 < ck ? cpad - c0 : ck;
-                for (int tap = 0; tap < taps; ++tap)
-                    for (int c16 = 0; c16 < ckq / 16; ++c16)
-                        for (int m = 0; m < mb; ++m)
-                            for (int lane = 0; lane < 64; ++lane) {
-                                uint16_t hi[4], lo[4];                       // same element order as the bf16 layout
-                                for (int j = 0; j < 4; ++j) {
-                                    const int cout = (g * mb + m) * 16 + (lane & 15);
-                                    const int cl = c0 + c16 * 16 + 4 * j + (lane >> 4);
-                                    float v = 0.f;
-                                    if (cout < out_channels && cl < src_channels[s])
-                                        v = weight[((size_t)cout * cin_total + (cin_off + cl)) * taps + tap];
-                                    hi[j] = bf16_rne(v);
-                                    const uint32_t hb = (uint32_t)hi[j] << 16;
-                                    float hf;
-                                    memcpy(&hf, &hb, 4);
-                                    lo[j] = bf16_rne(v - hf);
-                                }
-                                for (int j = 0; j < 4; ++j) *o++ = hi[j];
-                                for (int j = 0; j < 4; ++j) *o++ = lo[j];
-                            }
-            }
-            cin_off += src_channels[s];
+    conv_pack_walk<16, 16>(weight, out_channels, src_channels, num_src, kh, kw, mb, ck, [&](int g, auto w) {
+        for (int j = 0; j < 4; ++j) {                                    // 4 hi then 4 lo, both in the element order of the bf16 layout
+            const float v = w(4 * j + g);
+            o[j] = bf16_rne(v);
+            const uint32_t hb = (uint32_t)o[j] << 16;
+            float hf;
+            memcpy(&hf, &hb, 4);
+            o[4 + j] = bf16_rne(v - hf);
         }
-    }
+        o += 8;
+    });
     return 0;
 }
 

@@ -1,7 +1,8 @@
-// LDS-DMA, buffer descriptor, LDS pair read and the branch-free activation shared by the reduced-multiply kernels (conv_wino.hip,
-// convt_wino.hip, conv1d_wino.hip, conv_wino44{,s,w}.hip) and the bf16 kernel (conv_b8.hip).  Device code only; everything is
+// LDS-DMA, buffer descriptor, LDS pair read and the branch-free activation shared by the direct kernels (conv_mfma.hip, conv_b8.hip) and
+// the reduced-multiply ones (conv_wino.hip, convt_wino.hip, conv1d_wino.hip, conv_wino44{,s,w}.hip).  Device code only; everything is
 // force-inlined, so a translation unit pays for what it calls and nothing else.
-// (conv_mfma.hip keeps its own DMA helpers: they pass the scalar operands without readfirstlane, and its sweeps were tuned on that code.)
+// (conv_mfma.hip, conv_b8.hip and splitk_epilogue4_kernel keep the activation written out where they store, keep / slope hoisted ahead of
+// the store loops: with act_max in its place hipcc clones those loops.)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,30 +17,32 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // *other* pipeline buffer, which serialises load and compute.  Inline asm is invisible to that pass; the kernel waits itself
 // (dma_wait_all / dma_wait_upto) right before the barrier that publishes the buffer.  M0 (LDS base of the DMA) is saved / restored
 // inside the statement; `s_nop 4` covers the SALU/VALU-write -> VMEM-SGPR-read hazard the compiler does not pad for asm operands.
-// The scalar operands go through readfirstlane: values derived from the wave index are uniform, but the compiler may hold them in
-// VGPRs, which the "s" constraints of the asm do not fix up.
+// The *_raw forms pass the scalar operands as they are (conv_mfma.hip, whose sweeps were tuned on that code).  The others send them
+// through readfirstlane first: values derived from the wave index are uniform, but the compiler may hold them in VGPRs, which the "s"
+// constraints of the asm do not fix up.
+#define MR_LDS_DMA(INSN) "s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t" INSN "\n\ts_mov_b32 m0, %0"
+__device__ __forceinline__ void dma_buffer_dword_raw(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
+    unsigned keep;
+    asm volatile(MR_LDS_DMA("buffer_load_dword %2, %3, %4 offen lds") : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
+}
+__device__ __forceinline__ void dma_buffer_x4_raw(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
+    unsigned keep;
+    asm volatile(MR_LDS_DMA("buffer_load_dwordx4 %2, %3, %4 offen lds") : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
+}
+__device__ __forceinline__ void dma_global_x4_raw(unsigned lds_byte_addr, const void* g) {
+    unsigned keep;
+    asm volatile(MR_LDS_DMA("global_load_lds_dwordx4 %2, off") : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
+}
+__device__ __forceinline__ void dma_global_x1_raw(unsigned lds_byte_addr, const void* g) {
+    unsigned keep;
+    asm volatile(MR_LDS_DMA("global_load_lds_dword %2, off") : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
+}
+#undef MR_LDS_DMA
 __device__ __forceinline__ void dma_buffer_x4(unsigned lds_byte_addr, int voff, i32x4 srd, int soff) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    soff = __builtin_amdgcn_readfirstlane(soff);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "buffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
+    dma_buffer_x4_raw(__builtin_amdgcn_readfirstlane(lds_byte_addr), voff, srd, __builtin_amdgcn_readfirstlane(soff));
 }
-__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const void* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
-__device__ __forceinline__ void dma_global_x1(unsigned lds_byte_addr, const void* g) {
-    unsigned keep;
-    lds_byte_addr = __builtin_amdgcn_readfirstlane(lds_byte_addr);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\t"
-                 "global_load_lds_dword %2, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "s"(lds_byte_addr), "v"(g) : "memory");
-}
+__device__ __forceinline__ void dma_global_x4(unsigned lds_byte_addr, const void* g) { dma_global_x4_raw(__builtin_amdgcn_readfirstlane(lds_byte_addr), g); }
+__device__ __forceinline__ void dma_global_x1(unsigned lds_byte_addr, const void* g) { dma_global_x1_raw(__builtin_amdgcn_readfirstlane(lds_byte_addr), g); }
 __device__ __forceinline__ void dma_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // s_waitcnt vmcnt(N) takes an immediate: wait until at most `n` (wave-uniform) of this wave's VMEM instructions are outstanding (rounding down is safe)
 #define MR_VMCNT_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;

@@ -1,13 +1,12 @@
 // Host side shared by the reduced-multiply kernels (conv_wino.hip, convt_wino.hip, conv1d_wino.hip, conv_wino44{,s,w}.hip): descriptor
-// checks, the "LDS ceiling once per device, then launch" helper (conv_b8.hip too) and the packer of the standard weight-stream order.
+// checks and the packer of the standard weight-stream order (launch_lds_ceiling: conv_host.h, shared with the direct kernels).
 // What differs between the kernels stays at their call sites: this header makes none of them behave like another.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
-#include <atomic>
 
 #include "../../include/monorec_hip.h"
-#include "conv_layout.h"
+#include "conv_host.h"
 #include "cooktoom_1d.h"
 
 static inline int pad8(int c) { return (c + 7) & ~7; }
@@ -80,22 +79,6 @@ int wino_fill_args(const mr_wino_desc* d, int ck, long long plane_floats, int vi
     k.Cout = d->out_channels;
     k.w = d->packed_weights;
     return 0;
-}
-
-// Raises the dynamic-LDS ceiling of `Kernel` to `ceiling_bytes` once per device (the mask is per instantiation, i.e. per kernel), then launches it.
-template <auto Kernel, class KArgs>
-int launch_lds_ceiling(int ceiling_bytes, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const KArgs& k) {
-    static std::atomic<unsigned long long> attr_set{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return (int)hipGetLastError();
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ceiling_bytes);
-        if (e != hipSuccess) return (int)e;
-        attr_set.fetch_or(bit, std::memory_order_release);
-    }
-    hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, stream, k);
-    return (int)hipGetLastError();
 }
 
 // One weight stream in the standard order: [cout group of `blocks` 16-channel blocks][source][chunk of 8 channels][position < npos]

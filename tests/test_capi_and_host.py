@@ -1526,3 +1526,155 @@ def test_reduced_conv_descriptor_errors(hip_lib):
     for name, row in expected.items():
         assert got[name] == row, (name, [(b, g, e) for (b, _), g, e in zip(_REDUCED_CONV_BREAKS, got[name], row) if g != e])
     assert sorted(got) == sorted(expected) and len(expected) == 7
+
+
+# ------------------------------------------------------------------------------------------ packed streams and derivation of the direct kernels, pinned
+_PACK_SHAPES = [          # (source channels, out_channels, kh, kw): 1-3 sources, channels off every padding unit (4 / 16 / 32), couts off 16 * mb,
+    ([3], 16, 1, 1),      # chunk sizes beyond a padded source, taps from 1x1 to 7x7
+    ([5, 44], 40, 3, 2),
+    ([17, 4, 33], 50, 2, 2),
+    ([130], 24, 1, 3),
+    ([7], 100, 7, 7),
+    ([32, 64], 96, 3, 3),
+    ([1, 1, 1], 1, 1, 2),
+]
+_PACK_BAD = [             # (source channels, num_src, out_channels, kh, kw, mb, ck): refused, or an empty stream
+    ([8], 1, 16, 3, 3, 5, 16), ([8], 1, 16, 3, 3, 2, 12), ([8], 0, 16, 3, 3, 2, 16), ([8, 8, 8, 8], 4, 16, 3, 3, 2, 16),
+    ([8], 1, 0, 3, 3, 2, 16), ([8], 1, 16, 0, 3, 2, 16), ([8], 1, 16, 3, 0, 2, 16), ([8], 1, 16, 3, 3, 0, 16), ([8], 1, 16, 3, 3, 2, 8),
+]
+
+
+def _pack_weight_values(n, seed):
+    """n fp32 weights: seeded normals, with the values that exercise the bf16 rounding (ties, carries into the exponent, NaN, infinities,
+    denormals, signed zeros) spliced in at fixed places."""
+    w = np.random.RandomState(seed).standard_normal(n).astype(np.float32)
+    special = np.array([0x3f808000, 0x3f818000, 0x3f7fffff, 0x7f7fffff, 0x7fc00001, 0x7f800001, 0x7f800000, 0xff800000, 0x00000001, 0x807fffff,
+                        0x80000000, 0x3f80ffff, 0xbf808000, 0x477fe000], dtype=np.uint32).view(np.float32)
+    w[::37][:len(special)] = special[:len(w[::37])]
+    return w
+
+
+def _conv_pack_digest_lines(lib):
+    """One line per packer case - entry point, parameters, return code, stream size in bytes and the SHA-256 of the stream."""
+    import hashlib
+    kinds = [("f32", lib.mr_conv_packed_weight_floats, lib.mr_conv_pack_weights_f32, 4, (8, 16, 32, 64, 128)),
+             ("bf16", lib.mr_conv_packed_weight_floats_bf16, lib.mr_conv_pack_weights_bf16, 4, (16, 32, 64, 128)),
+             ("bf16x3", lib.mr_conv_packed_weight_floats_bf16x3, lib.mr_conv_pack_weights_bf16x3, 4, (16, 32, 64, 128)),
+             ("b8", lib.mr_b8_packed_weight_bytes, lib.mr_b8_pack_weights, 1, (None,))]
+    lines = []
+    for kind, size_fn, pack_fn, unit, cks in kinds:
+        good = [(srcs, len(srcs), cout, kh, kw, mb, ck) for mb in ((1, 2, 3, 4) if kind == "b8" else (1, 2, 3, 4, 6)) for ck in cks
+                for srcs, cout, kh, kw in _PACK_SHAPES]
+        bad = [c for c in _PACK_BAD if kind != "b8" or c[6] == 16]
+        for seed, (srcs, nsrc, cout, kh, kw, mb, ck) in enumerate(good + bad):
+            sc = (ctypes.c_int32 * len(srcs))(*srcs)
+            tail = (mb,) if kind == "b8" else (mb, ck)
+            nbytes = int(size_fn(cout, sc, nsrc, kh, kw, *tail)) * unit
+            w = _pack_weight_values(max(cout, 1) * sum(srcs) * max(kh * kw, 1), seed)
+            dst = np.full(nbytes + 64, 0xA5, dtype=np.uint8)                 # 64 guard bytes: a stream never runs past its size
+            rc = int(pack_fn(w.ctypes.data, cout, sc, nsrc, kh, kw, *tail, dst.ctypes.data))
+            assert (dst[nbytes:] == 0xA5).all(), (kind, srcs, cout, kh, kw, mb, ck)
+            lines.append(f"{kind} src={','.join(map(str, srcs))} nsrc={nsrc} cout={cout} k={kh}x{kw} mb={mb} ck={ck} rc={rc} bytes={nbytes} "
+                         f"sha256={hashlib.sha256(dst[:nbytes].tobytes()).hexdigest()}")
+    return lines
+
+
+def _conv_derivation_answers(lib, n=100000, seed=20):
+    """(mr_conv2d_lds_bytes, mr_conv2d_b8_lds_bytes) over n seeded random descriptors each: coherent ones (a destination that holds the
+    output, known enums) with single and multiple fields broken - the functions only derive, no pointer is followed."""
+    rs = np.random.RandomState(seed)
+
+    def pick(good, bad=(), shape=None, p=2):
+        """a value of `good` per descriptor (and array element); p % of them take one of `bad` instead"""
+        size = (n,) if shape is None else (n, shape)
+        v = np.asarray(good)[rs.randint(0, len(good), size=size)]
+        if len(bad):
+            v = np.where(rs.randint(0, 100, size=size) < p, np.asarray(bad)[rs.randint(0, len(bad), size=size)], v)
+        return v
+
+    ptr = lambda shape=None: (pick([1], [0], shape) << 20).astype(np.uint64)
+    slope = np.array([0.0, 0.1, 0.2, 1.0, 1.5, -0.1, np.nan], dtype=np.float32)
+
+    def common(d):
+        d["num_src"] = pick([1, 1, 1, 2, 2, 3], [0, 4])
+        d["src"] = ptr(3)
+        d["src_channels"] = pick([1, 3, 4, 5, 8, 16, 17, 32, 33, 64, 100, 128, 256], [0, -1], 3, p=1)
+        d["batch"] = pick([1, 1, 1, 2, 4, 8], [0, 70000, 20000])
+        for f in ("src_h", "src_w"):
+            d[f] = pick([2, 7, 8, 16, 30, 32, 33, 64, 100, 128, 256], [4096])
+        for f in ("kh", "kw"):
+            d[f] = pick([1, 1, 2, 3, 3, 3, 4, 5, 7], [0])
+        for f in ("stride_h", "stride_w"):
+            d[f] = pick([1, 1, 1, 2], [3, 0])
+        for f in ("out_h", "out_w"):
+            d[f] = pick([1, 2, 8, 15, 16, 31, 32, 33, 64, 100, 256], [0, 5000])
+        d["dst"] = ptr()
+        d["out_channels"] = pick([1, 8, 16, 17, 32, 48, 64, 100], [0])
+        for f in ("out_step_h", "out_step_w"):
+            d[f] = pick([1, 1, 1, 2], [0])
+        d["phase_out_off_h"], d["phase_out_off_w"] = pick([0, 0, 1], [-1], 4, p=1), pick([0, 0, 1], [-1], 4, p=1)
+        for f, o, s in (("dst_plane_h", "out_h", "out_step_h"), ("dst_plane_w", "out_w", "out_step_w")):      # the output just fits (or misses by one)
+            d[f] = (d[o] - 1) * np.maximum(d[s], 1) + 2 + pick([0, 0, 3], [-2])
+        d["bias"] = pick([0, 1]).astype(np.uint64) << 20
+        d["activation"] = pick([0, 1, 2, 2], [3, 4, 5], p=5)
+        d["act_p0"] = slope[pick([0, 1, 2, 3], [4, 5, 6], p=5)]
+        d["cout_blocks_per_wg"] = pick([1, 2, 3, 4], [6, 5, 0], p=6)
+        d["pixel_blocks_per_wave"] = pick([1, 2, 4], [3])
+        d["waves_per_wg"] = pick([4, 4, 8], [0, 2], p=4)
+        d["num_phases"] = pick([0, 1, 1, 4], [2])
+        d["phase_weights"] = ptr(4)
+        d["phase_pad_top"], d["phase_pad_left"] = pick([0, 1, 2], shape=4), pick([0, 1, 2, 3], shape=4)
+        for f in ("phase_kh", "phase_kw"):                                    # 0: the common size; never more than it, unless broken
+            d[f] = np.where(pick([0], [1], 4, p=1) == 1, 9, np.minimum(pick([0, 0, 1, 2, 3], shape=4), d[f[-2:]][:, None]))
+
+    def answers(struct, fn, fill):
+        d = np.zeros(n, dtype=np.dtype(struct))
+        fill(d)
+        descs = (struct * n).from_buffer(d)
+        return np.array([fn(ctypes.byref(descs[i])) for i in range(n)], dtype=np.int64)
+
+    def direct(d):
+        common(d)
+        d["in_mode"], d["in_transform"] = pick([0, 0, 0, 0, 1, 2], [3]), pick([0, 0, 0, 1])
+        d["pad_top"], d["pad_left"] = pick([0, 1, 2, 3]), pick([0, 1, 2, 3])
+        extra = pick([0, 0, 16])
+        d["dst_total_channels"] = d["out_channels"] + extra
+        d["dst_channel_offset"] = np.where(pick([0], [1]) == 1, pick([17, -1]), pick([0, 1]) * extra)
+        d["out_off_h"], d["out_off_w"] = pick([0, 0, 1], [-1]), pick([0, 0, 1], [-1])
+        d["packed_weights"], d["residual"], d["workspace"] = ptr(), pick([0, 1]).astype(np.uint64) << 20, ptr()
+        d["act_p1"] = 0.5
+        d["chunk_channels"] = pick([8, 16, 16, 32, 64, 128], [12])
+        d["split_k"] = pick([1, 1, 1, 2, 4], [3, 8, 0, 100], p=4)
+        d["compute_dtype"] = pick([0, 0, 0, 1, 2], [3])
+        d["k_split_waves"] = pick([0, 0, 0, 1])
+
+    def b8(d):
+        common(d)
+        d["src_layout"] = pick([0, 1, 1, 1], [2], 3, p=1)
+        d["dst_layout"] = pick([0, 1, 1], [2])
+
+    return answers(_lib.ConvDesc, lib.mr_conv2d_lds_bytes, direct), answers(_lib.B8ConvDesc, lib.mr_conv2d_b8_lds_bytes, b8)
+
+
+def _conv_pack_fixture_text(lib):
+    import hashlib
+    direct, b8 = _conv_derivation_answers(lib)
+    summary = lambda a: f"n={len(a)} accepted={int((a > 0).sum())} bad_argument={int((a == -1).sum())} unsupported={int((a == -2).sum())} " \
+                        f"lds_budget={int((a == -3).sum())} sha256={hashlib.sha256(a.astype('<i8').tobytes()).hexdigest()}"
+    return "\n".join(_conv_pack_digest_lines(lib) + ["derive mr_conv2d_lds_bytes " + summary(direct), "derive mr_conv2d_b8_lds_bytes " + summary(b8)]) + "\n"
+
+
+def test_conv_packed_streams_and_derivation_match_the_recorded_digests(hip_lib):
+    """The four packers of the direct kernels (csrc/conv_mfma.hip, conv_b8.hip; one walk in csrc/conv_host.h) and the two derive functions,
+    against tests/golden/conv_pack_digests.txt - what the library answered BEFORE the packers and the LDS-ceiling launch became shared code
+    (_conv_pack_fixture_text of that library, written out as it is).  Per packer: every valid mb and ck over _PACK_SHAPES, and the refused /
+    empty cases of _PACK_BAD; the stream must have the recorded size and SHA-256 and stay inside its size.  Per derive function: the answers
+    (LDS bytes or error code) to 10^5 seeded random descriptors, invalid and multi-error ones included, as one digest; the counts beside it say
+    how many of them the function accepted."""
+    recorded = open(os.path.join(GOLDEN, "conv_pack_digests.txt")).read().splitlines()
+    got = _conv_pack_fixture_text(hip_lib).splitlines()
+    assert len(got) == len(recorded)
+    for g, r in zip(got, recorded):
+        assert g == r
+    accepted = {r.split()[1]: int(re.search(r"accepted=(\d+)", r).group(1)) for r in recorded if r.startswith("derive ")}
+    assert len(accepted) == 2 and all(v >= 10000 for v in accepted.values()), accepted     # at least a tenth of the descriptors pass every check
