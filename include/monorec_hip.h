@@ -43,6 +43,9 @@ extern "C" {
 #define MR_TSDF_TILE_X 32     /* voxels of one workgroup of mr_tsdf_integrate_f32 - the unit of its frustum culling */
 #define MR_TSDF_TILE_Y 8
 #define MR_TSDF_TILE_Z 4
+#ifndef MR_TSDF_BRICK         /* (a build with -DMR_TSDF_BRICK=8 exists for tools/bench_tsdf_render.py --brick 8 alone) */
+#define MR_TSDF_BRICK 4       /* edge, in voxels, of one brick of mr_tsdf_skip_grid_u8: 4 or 8, 4 by measurement */
+#endif
 
 /* ---- activation codes for mr_conv2d_f32 (epilogue, applied after bias [+ residual]) ---- */
 enum {
@@ -802,6 +805,65 @@ int mr_tsdf_mesh_vertices_f32(const float* tsdf, const float* weight, const uint
 int mr_tsdf_mesh_triangles_f32(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float min_weight,
                                const int32_t* vertex_base, int32_t* triangles, int64_t capacity_triangles, int64_t* cursor,
                                void* stream);
+
+/* The volume seen from a camera (two entries added within ABI 24: the change only adds symbols): every pixel's ray is marched through
+ * the volume in steps of `step` metres of camera z - the depth mr_tsdf_integrate_f32 fuses - until the trilinear tsdf turns from
+ * non-negative to negative between two valid samples; the crossing's depth, the surface normal and the colour there come out.
+ *
+ * mr_tsdf_skip_grid_u8: one byte per brick of MR_TSDF_BRICK^3 voxels, ceil(n_a / MR_TSDF_BRICK) bricks per axis, x fastest.  With
+ * B = MR_TSDF_BRICK the byte of brick (b_x, b_y, b_z) is 1 when some voxel with weight > min_weight and tsdf < 0 lies in
+ * [B b_a, B b_a + B] on every axis (INCLUSIVE: one voxel of halo on the + side, because the corners of a cell reach i + 1), clipped to
+ * the volume; otherwise 0.  One sweep of the volume, behind a clear of the bytes on the same stream.  Besides the volume cases of
+ * mr_tsdf_volume_reset_f32: NaN min_weight, bricks NULL: MR_ERR_BAD_ARGUMENT, nothing is launched. */
+int mr_tsdf_skip_grid_u8(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float min_weight, uint8_t* bricks,
+                         void* stream);
+
+/* One view of mr_tsdf_render_f32, passed by value in the launch arguments. */
+typedef struct mr_tsdf_ray_view {
+    float m[12];                 /* camera -> world, 3 x 4 row-major: R[a][j] = m[4a + j], c_a = m[4a + 3].  Nothing is inverted anywhere. */
+    float fx, fy, cx, cy;        /* pixel intrinsics of the rendered image */
+    float* depth;                /* height x width, device memory: camera-z metres, 0 = no surface */
+    float* normal;               /* height x width x 3, device memory, may be NULL: unit normal in world axes, towards positive tsdf */
+    uint8_t* colour;             /* height x width x 3 interleaved r g b, device memory, may be NULL; all 0 when the volume has no colour */
+} mr_tsdf_ray_view;
+
+/* Render views[0 .. num_views) (HOST array, 1 <= num_views <= MR_TSDF_MAX_FRAMES), all height x width, of the volume: the result equals
+ * num_views launches of one view bit for bit.  All fp32, every operation rounded on its own:
+ *   inv = 1 / voxel_size
+ *   per view:   o_a = (c_a - origin_a) * inv
+ *   per pixel (u, v):   rx = ((float)u - cx) / fx;  ry = ((float)v - cy) / fy
+ *                       d_a = (R[a][0] * rx + R[a][1] * ry) + R[a][2];  e_a = d_a * inv
+ *   sample k = 0, 1, ... while t_k <= t_max:
+ *     t_k = t_min + (float)k * step
+ *     g_a = o_a + t_k * e_a;  i_a = floorf(g_a);  f_a = g_a - i_a
+ *     VALID iff 0 <= i_a and i_a + 1 <= n_a - 1 for all a, and the weights of all 8 corners i + {0, 1}^3 are > min_weight
+ *     F_k = the trilinear interpolant of the 8 corner tsdf, every lerp in the form a + f * (b - a), along x, then y, then z
+ *   state (prev_valid, F_prev), initially not valid, walked in the order of k:
+ *     VALID and prev_valid and !(F_prev < 0) and  (F_k < 0)   HIT at k
+ *     VALID and prev_valid and  (F_prev < 0) and !(F_k < 0)   the ray ends without a hit: it left the surface through a back face
+ *     not VALID                                               prev_valid = false
+ *     otherwise                                               prev = (valid, F_k)
+ *   HIT:     s = F_prev / (F_prev - F_k);  depth = (t_min + (float)(k - 1) * step) + s * step
+ *   no hit:  depth = 0, normal = 0 0 0, colour = 0 0 0
+ * Normal and colour are taken in the cell and at the fractions f of sample k.  The normal is the analytic gradient of the interpolant:
+ *   g_x = the lerp along z of the lerps along y of the four differences T[1][y][z] - T[0][y][z]           (T[x][y][z]: the corners)
+ *   g_y = the lerp along z of the lerps along x of the four differences T[x][1][z] - T[x][0][z]
+ *   g_z = the lerp along y of the lerps along x of the four differences T[x][y][1] - T[x][y][0]
+ *   len = sqrtf((g_x * g_x + g_y * g_y) + g_z * g_z);  n = g / len if len > 0, else 0 0 0
+ * in world axes, towards positive tsdf: out of the surface.  colour_c = (uint8)fminf(255, floorf(x + .5)), x the same trilinear
+ * interpolant of the corners' bytes as floats.
+ * bricks: NULL, or the bytes mr_tsdf_skip_grid_u8 wrote for THIS volume and THIS min_weight.  A sample whose cell base i lies in a
+ * brick of byte 0 is not VALID, or VALID with F_k >= 0 (no corner is seen and negative, and a + f * (b - a) of non-negative a, b with
+ * 0 <= f <= 1 is never negative in fp32), so it is neither a hit nor, unless F_prev < 0, the end of the ray; such samples cost one
+ * byte load instead of 16 gathers, except that a sample is always evaluated in full while prev is valid and negative, and that the
+ * sample before an evaluated one is evaluated in full as its prev.  The bricks change no bit of any output.  Rays are clipped to the
+ * volume's box first, by a margin wider than fp32 can move a sample: samples outside it are not VALID anyway.
+ * Besides the cases of mr_tsdf_extract_f32's volume: views NULL, num_views outside 1 .. MR_TSDF_MAX_FRAMES, a view without depth,
+ * depth / normal off a 4-byte boundary, fx or fy 0 or NaN, height / width < 1, step <= 0 (or NaN), t_min < 0, t_max < t_min, either
+ * not finite, more than 2^20 samples per ray, NaN min_weight: MR_ERR_BAD_ARGUMENT, nothing is launched. */
+int mr_tsdf_render_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                       const float* origin, float voxel_size, float min_weight, const uint8_t* bricks, const mr_tsdf_ray_view* views,
+                       int32_t num_views, int32_t height, int32_t width, float t_min, float t_max, float step, void* stream);
 
 /* ---- input pipeline: KittiOdometryDataset.preprocess_image, kitti_odometry_dataset.py:120-134 ------
  *

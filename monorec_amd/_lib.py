@@ -106,6 +106,15 @@ class TsdfView(ctypes.Structure):
                 ("depth_cm", ctypes.c_void_p), ("colour", ctypes.c_void_p)]
 
 
+MR_TSDF_BRICK = 4              # edge of one brick of mr_tsdf_skip_grid_u8 in voxels
+
+
+class TsdfRayView(ctypes.Structure):
+    """mirror of `mr_tsdf_ray_view` (include/monorec_hip.h): m is camera -> world."""
+    _fields_ = [("m", ctypes.c_float * 12), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("colour", ctypes.c_void_p)]
+
+
 class LaunchItem(ctypes.Structure):
     """mirror of `mr_launch_item` (include/monorec_hip.h)."""
     _fields_ = [("kind", ctypes.c_int32), ("arg", ctypes.c_int32), ("desc", ctypes.c_void_p)]
@@ -282,6 +291,11 @@ ABI = {
                                                  ctypes.c_void_p, ctypes.c_void_p]),
     "mr_tsdf_mesh_triangles_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_skip_grid_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_render_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                          _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.POINTER(TsdfRayView), ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
     "mr_resample_ksize_bilinear": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "mr_resample_coeffs_bilinear": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_void_p]),

@@ -667,3 +667,305 @@ extern "C" int mr_tsdf_mesh_triangles_f32(const float* tsdf, const float* weight
     hipLaunchKernelGGL(tsdf_mesh_triangles_kernel, dim3(mesh_tiles(a)), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
+
+// ---- the volume seen from a camera: ray-cast depth, normal and colour (include/monorec_hip.h has the arithmetic) --------------------
+//
+// tsdf_skip_grid_kernel   one byte per brick of MR_TSDF_BRICK^3 voxels (plus a voxel of halo on the + side): does it hold a seen negative
+//                         voxel?  The integrate kernel's tile and 16-byte loads; a thread that finds one stores 1 into the (up to
+//                         eight) bricks whose inclusive range holds it.  The bytes are cleared by a memset ahead of the launch; every
+//                         store writes the same value, so their order does not matter.
+// tsdf_render_kernel      a thread per pixel, a wave a compact 8 x 8 pixel tile, a workgroup 16 x 16 pixels of one view (blockIdx.z):
+//                         neighbouring rays walk neighbouring cells, so the 16 gathers of a sample (8 corner weights, 8 corner tsdf)
+//                         of a wave fall into few cache lines.  A ray is clipped to the volume's box, then marched; with the bricks a
+//                         sample in an empty brick costs one byte load (the grid of a 512 x 512 x 128 volume is 512 KB: it stays in
+//                         cache).
+namespace {
+
+constexpr int BRICK = MR_TSDF_BRICK;
+static_assert(BRICK % 4 == 0 && BRICK >= 4, "the four voxels of a thread of the skip-grid sweep share a brick");
+constexpr int MAX_SAMPLES = 1 << 20;
+
+struct SkipArgs {
+    const float* tsdf;
+    const float* weight;
+    int nx, ny, nz;
+    int tiles_x, tiles_y;
+    int bricks_x, bricks_y;
+    float min_weight;
+    uint8_t* bricks;
+};
+
+__global__ __launch_bounds__(256) void tsdf_skip_grid_kernel(const SkipArgs a) {
+    const int tile = blockIdx.x, tid = threadIdx.x;
+    const int x = (tile % a.tiles_x) * TX + (tid & 7) * 4, y = ((tile / a.tiles_x) % a.tiles_y) * TY + ((tid >> 3) & 7);
+    const int z = (tile / (a.tiles_x * a.tiles_y)) * TZ + (tid >> 6);
+    if (x >= a.nx || y >= a.ny || z >= a.nz) return;
+    const int n = a.nx - x < 4 ? a.nx - x : 4;
+    const long long idx = ((long long)z * a.ny + y) * a.nx + x;
+    const float* tp = a.tsdf + idx;
+    const float* wp = a.weight + idx;
+    float t[4], wgt[4];
+    if (n == 4 && (((uintptr_t)tp | (uintptr_t)wp) & 15) == 0) {
+        const float4 tv = *reinterpret_cast<const float4*>(tp);
+        const float4 wv = *reinterpret_cast<const float4*>(wp);
+        t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
+        wgt[0] = wv.x; wgt[1] = wv.y; wgt[2] = wv.z; wgt[3] = wv.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            t[j] = j < n ? tp[j] : 1.0f;
+            wgt[j] = j < n ? wp[j] : 0.0f;
+        }
+    }
+    bool any = false, first = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const bool neg = wgt[j] > a.min_weight && t[j] < 0.0f;
+        any = any || neg;
+        if (j == 0) first = neg;
+    }
+    if (!any) return;
+    // x .. x + 3 lie in brick x / BRICK; voxel B b also closes the inclusive range of brick b - 1
+    const int bx = x / BRICK, by = y / BRICK, bz = z / BRICK;
+    const int lx = (first && x % BRICK == 0 && bx > 0) ? 1 : 0, ly = (y % BRICK == 0 && by > 0) ? 1 : 0, lz = (z % BRICK == 0 && bz > 0) ? 1 : 0;
+    for (int dz = 0; dz <= lz; ++dz)
+        for (int dy = 0; dy <= ly; ++dy)
+            for (int dx = 0; dx <= lx; ++dx)
+                a.bricks[((long long)(bz - dz) * a.bricks_y + (by - dy)) * a.bricks_x + (bx - dx)] = 1;
+}
+
+struct RayView {
+    float r[9];                                  // camera -> world rotation, row-major
+    float o[3];                                  // the camera centre in voxel units: (c - origin) * inv
+    float fx, fy, cx, cy;
+    float* depth;
+    float* normal;
+    uint8_t* colour;
+};
+
+struct RenderArgs {
+    const float* tsdf;
+    const float* weight;
+    const unsigned* colour;                      // r g b 0 per voxel or null
+    const uint8_t* bricks;                       // null: every sample is evaluated
+    int nx, ny, nz;
+    int bricks_x, bricks_y;
+    float lim[3];                                // the largest float <= n_a - 2: the last cell base along each axis
+    float inv, min_weight, t_min, step;
+    int last;                                    // index of the last sample with t_k <= t_max
+    int h, w, tiles_x;
+    RayView v[MR_TSDF_MAX_FRAMES];
+};
+
+__device__ __forceinline__ float lerp(float a, float b, float f) { return a + f * (b - a); }
+
+__device__ __forceinline__ float trilinear(const float c[8], float fx, float fy, float fz) {   // c[x + 2 y + 4 z]
+    const float y0 = lerp(lerp(c[0], c[1], fx), lerp(c[2], c[3], fx), fy);
+    const float y1 = lerp(lerp(c[4], c[5], fx), lerp(c[6], c[7], fx), fy);
+    return lerp(y0, y1, fz);
+}
+
+struct Cell {
+    float f[3];
+    int i[3];
+    bool inside;                                 // all 8 corners are voxels of the volume
+};
+
+__device__ __forceinline__ Cell cell_of(const RenderArgs& a, const float o[3], const float e[3], int k) {
+    const float t = a.t_min + (float)k * a.step;
+    Cell c;
+    c.inside = true;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const float g = o[q] + t * e[q];
+        const float fl = floorf(g);
+        c.f[q] = g - fl;
+        const bool in = fl >= 0.0f && fl <= a.lim[q];                      // NaN: outside
+        c.inside = c.inside && in;
+        c.i[q] = in ? (int)fl : 0;
+    }
+    return c;
+}
+
+// the 8 corner tsdf of an inside cell into T; false when a corner's weight is not above min_weight
+__device__ __forceinline__ bool corners_of(const RenderArgs& a, const Cell& c, float T[8], long long& base) {
+    const long long plane = (long long)a.nx * a.ny;
+    base = (long long)c.i[2] * plane + (long long)c.i[1] * a.nx + c.i[0];
+    float W[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const long long at = base + (j & 1) + ((j >> 1) & 1) * (long long)a.nx + (j >> 2) * plane;
+        W[j] = a.weight[at];
+        T[j] = a.tsdf[at];
+    }
+    bool seen = true;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) seen = seen && (W[j] > a.min_weight);
+    return seen;
+}
+
+__global__ __launch_bounds__(256) void tsdf_render_kernel(const RenderArgs a) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int u = (blockIdx.x % a.tiles_x) * 16 + (wave & 1) * 8 + (lane & 7);
+    const int v = (blockIdx.x / a.tiles_x) * 16 + (wave >> 1) * 8 + (lane >> 3);
+    if (u >= a.w || v >= a.h) return;
+    const RayView& view = a.v[blockIdx.z];
+    const float rx = ((float)u - view.cx) / view.fx, ry = ((float)v - view.cy) / view.fy;
+    float o[3], e[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        o[q] = view.o[q];
+        e[q] = ((view.r[3 * q] * rx + view.r[3 * q + 1] * ry) + view.r[3 * q + 2]) * a.inv;
+    }
+
+    // Clip to the box 0 <= g_a <= n_a in t, then in k.  Only an optimisation, so it only has to be conservative: no sample outside
+    // [k_lo, k_hi] may be valid.  The crossing times t_a = (bound - o_a) / e_a are a few ulp of max(|t_a|) off, and so is the t at which
+    // the fp32 g_a = o_a + t_k * e_a crosses the bound (|o_a| / |e_a| is one of the two |t_a|); the range is widened by 1e-5 of the
+    // larger |t_a| (more than 80 ulp) and by one step, and the k range by one more sample for the roundings of (t - t_min) / step and of
+    // (float)k * step (k < 2^20: 0.07 of a sample each).  fmaxf / fminf drop a NaN, which leaves the range as it was.
+    float t_lo = a.t_min, t_hi = a.t_min + (float)a.last * a.step;
+    bool empty = false;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const float top = a.lim[q] + 2.0f;                                  // n_a (or just below): beyond the last valid g_a
+        if (e[q] == 0.0f) {
+            empty = empty || !(o[q] >= 0.0f && o[q] <= top);                // g_a = o_a all along the ray
+            continue;
+        }
+        const float ta = (0.0f - o[q]) / e[q], tb = (top - o[q]) / e[q];
+        const float slack = 1e-5f * fmaxf(fabsf(ta), fabsf(tb)) + a.step;
+        t_lo = fmaxf(t_lo, fminf(ta, tb) - slack);
+        t_hi = fminf(t_hi, fmaxf(ta, tb) + slack);
+    }
+    int k_lo = (int)fminf(fmaxf(floorf((t_lo - a.t_min) / a.step) - 1.0f, 0.0f), (float)a.last + 1.0f);
+    int k_hi = (int)fminf(fmaxf(ceilf((t_hi - a.t_min) / a.step) + 1.0f, -1.0f), (float)a.last);
+    if (empty) k_hi = -1;
+
+    // prev: 0 not valid, 1 valid with F_prev, 2 skipped (in a brick of byte 0: not valid, or valid and not negative - evaluated in full
+    // before the next sample that is)
+    int prev = 0, hit_k = -1;
+    float F_prev = 0.0f, F_hit = 0.0f, T[8], f[3] = {0.0f, 0.0f, 0.0f};
+    long long base = 0;
+    for (int k = k_lo; k <= k_hi; ++k) {
+        const Cell c = cell_of(a, o, e, k);
+        if (!c.inside) { prev = 0; continue; }
+        if (a.bricks && !(prev == 1 && F_prev < 0.0f)) {                   // never skip behind a negative sample: the back-face stop
+            const long long b = ((long long)(c.i[2] / BRICK) * a.bricks_y + c.i[1] / BRICK) * a.bricks_x + c.i[0] / BRICK;
+            if (!a.bricks[b]) { prev = 2; continue; }
+        }
+        if (prev == 2) {                                                    // k - 1 was skipped: it is inside, and cannot end the ray
+            const Cell p = cell_of(a, o, e, k - 1);
+            float P[8];
+            long long unused;
+            prev = corners_of(a, p, P, unused) ? 1 : 0;
+            F_prev = trilinear(P, p.f[0], p.f[1], p.f[2]);
+        }
+        if (!corners_of(a, c, T, base)) { prev = 0; continue; }
+        const float F = trilinear(T, c.f[0], c.f[1], c.f[2]);
+        if (prev == 1) {
+            if (!(F_prev < 0.0f) && F < 0.0f) { hit_k = k; F_hit = F; f[0] = c.f[0]; f[1] = c.f[1]; f[2] = c.f[2]; break; }
+            if (F_prev < 0.0f && !(F < 0.0f)) break;
+        }
+        prev = 1;
+        F_prev = F;
+    }
+
+    const long long pix = (long long)v * a.w + u;
+    float depth = 0.0f, n[3] = {0.0f, 0.0f, 0.0f};
+    unsigned rgb[3] = {0u, 0u, 0u};
+    if (hit_k >= 0) {
+        const float s = F_prev / (F_prev - F_hit);
+        depth = (a.t_min + (float)(hit_k - 1) * a.step) + s * a.step;
+        if (view.normal) {
+            const float gx = lerp(lerp(T[1] - T[0], T[3] - T[2], f[1]), lerp(T[5] - T[4], T[7] - T[6], f[1]), f[2]);
+            const float gy = lerp(lerp(T[2] - T[0], T[3] - T[1], f[0]), lerp(T[6] - T[4], T[7] - T[5], f[0]), f[2]);
+            const float gz = lerp(lerp(T[4] - T[0], T[5] - T[1], f[0]), lerp(T[6] - T[2], T[7] - T[3], f[0]), f[1]);
+            const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
+            if (len > 0.0f) { n[0] = gx / len; n[1] = gy / len; n[2] = gz / len; }
+        }
+        if (view.colour && a.colour) {
+            const long long plane = (long long)a.nx * a.ny;
+            unsigned C[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) C[j] = a.colour[base + (j & 1) + ((j >> 1) & 1) * (long long)a.nx + (j >> 2) * plane];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                float B[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) B[j] = (float)((C[j] >> (8 * ch)) & 0xffu);
+                rgb[ch] = (unsigned)fminf(255.0f, floorf(trilinear(B, f[0], f[1], f[2]) + 0.5f));
+            }
+        }
+    }
+    view.depth[pix] = depth;
+    if (view.normal) { float* o3 = view.normal + pix * 3; o3[0] = n[0]; o3[1] = n[1]; o3[2] = n[2]; }
+    if (view.colour) { uint8_t* c3 = view.colour + pix * 3; c3[0] = (uint8_t)rgb[0]; c3[1] = (uint8_t)rgb[1]; c3[2] = (uint8_t)rgb[2]; }
+}
+
+float t_of(float t_min, float step, long long k) { return t_min + (float)k * step; }
+
+}  // namespace
+
+extern "C" int mr_tsdf_skip_grid_u8(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float min_weight,
+                                    uint8_t* bricks, void* stream) {
+    if (bad_volume(tsdf, weight, nx, ny, nz) || min_weight != min_weight || !bricks) return MR_ERR_BAD_ARGUMENT;
+    SkipArgs a;
+    a.tsdf = tsdf; a.weight = weight; a.nx = nx; a.ny = ny; a.nz = nz; a.min_weight = min_weight; a.bricks = bricks;
+    a.tiles_x = (nx + TX - 1) / TX; a.tiles_y = (ny + TY - 1) / TY;
+    const long long tiles = (long long)a.tiles_x * a.tiles_y * ((nz + TZ - 1) / TZ);
+    if (tiles > 0x7fffffffLL) return MR_ERR_BAD_ARGUMENT;
+    a.bricks_x = (nx + BRICK - 1) / BRICK; a.bricks_y = (ny + BRICK - 1) / BRICK;
+    const long long count = (long long)a.bricks_x * a.bricks_y * ((nz + BRICK - 1) / BRICK);
+    const hipError_t cleared = hipMemsetAsync(bricks, 0, (size_t)count, (hipStream_t)stream);
+    if (cleared != hipSuccess) return (int)cleared;
+    hipLaunchKernelGGL(tsdf_skip_grid_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_render_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                                  const float* origin, float voxel_size, float min_weight, const uint8_t* bricks,
+                                  const mr_tsdf_ray_view* views, int32_t num_views, int32_t height, int32_t width, float t_min, float t_max,
+                                  float step, void* stream) {
+    if (bad_volume(tsdf, weight, nx, ny, nz) || ((uintptr_t)colour & 3) || !origin || !views) return MR_ERR_BAD_ARGUMENT;
+    if (!(voxel_size > 0.0f) || min_weight != min_weight) return MR_ERR_BAD_ARGUMENT;
+    if (num_views < 1 || num_views > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return MR_ERR_BAD_ARGUMENT;
+    if (!(step > 0.0f) || !(t_min >= 0.0f) || !(t_max >= t_min) || !isfinite(t_min) || !isfinite(t_max)) return MR_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < num_views; ++i) {
+        const mr_tsdf_ray_view& s = views[i];
+        if (!s.depth || (((uintptr_t)s.depth | (uintptr_t)s.normal) & 3)) return MR_ERR_BAD_ARGUMENT;
+        if (s.fx == 0.0f || s.fy == 0.0f || s.fx != s.fx || s.fy != s.fy) return MR_ERR_BAD_ARGUMENT;
+    }
+    // the last k with t_k <= t_max, t_k as the kernel rounds it (non-decreasing in k): an estimate in double, then stepped into place
+    const double estimate = floor(((double)t_max - (double)t_min) / (double)step);
+    if (!(estimate < (double)MAX_SAMPLES + 2.0)) return MR_ERR_BAD_ARGUMENT;
+    long long last = (long long)estimate;
+    while (last > 0 && t_of(t_min, step, last) > t_max) --last;
+    while (last + 1 <= MAX_SAMPLES && t_of(t_min, step, last + 1) <= t_max) ++last;
+    if (last + 1 > MAX_SAMPLES) return MR_ERR_BAD_ARGUMENT;
+    RenderArgs a;
+    a.tsdf = tsdf; a.weight = weight; a.colour = reinterpret_cast<const unsigned*>(colour); a.bricks = bricks;
+    a.nx = nx; a.ny = ny; a.nz = nz;
+    a.bricks_x = (nx + BRICK - 1) / BRICK; a.bricks_y = (ny + BRICK - 1) / BRICK;
+    const int dims[3] = {nx, ny, nz};
+    for (int q = 0; q < 3; ++q) {
+        float lim = (float)(dims[q] - 2);                                   // -1 for a single layer of voxels: no cell, no valid sample
+        if ((double)lim > (double)(dims[q] - 2)) lim = nextafterf(lim, 0.0f);
+        a.lim[q] = lim;
+    }
+    a.inv = 1.0f / voxel_size; a.min_weight = min_weight; a.t_min = t_min; a.step = step; a.last = (int)last;
+    a.h = height; a.w = width; a.tiles_x = (width + 15) / 16;
+    const long long tiles = (long long)a.tiles_x * ((height + 15) / 16);
+    if (tiles > 0x7fffffffLL) return MR_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < MR_TSDF_MAX_FRAMES; ++i) {
+        const mr_tsdf_ray_view& s = views[i < num_views ? i : 0];
+        RayView& d = a.v[i];
+        for (int q = 0; q < 3; ++q) {
+            for (int j = 0; j < 3; ++j) d.r[3 * q + j] = s.m[4 * q + j];
+            d.o[q] = (s.m[4 * q + 3] - origin[q]) * a.inv;
+        }
+        d.fx = s.fx; d.fy = s.fy; d.cx = s.cx; d.cy = s.cy;
+        d.depth = s.depth; d.normal = s.normal; d.colour = s.colour;
+    }
+    hipLaunchKernelGGL(tsdf_render_kernel, dim3((unsigned)tiles, 1, (unsigned)num_views), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}

@@ -16,13 +16,20 @@ records `pointcloud.PLYSaver` writes.  `mesh()` returns the same surface as an i
 16-case table instead of marching cubes' 256, no ambiguous cases, so the mesh is a closed 2-manifold wherever the voxels are seen,
 at the price of about twice the triangles of marching cubes).  Every vertex lies on one of seven edges its voxel owns, so the mesh
 comes out welded by construction, with no hashing and no sort; the vertices on the three axis edges are `extract()`'s records.  The
-rules are in include/monorec_hip.h, restated in numpy by tests/tsdf_mesh_ref.py.  There is no CPU fallback: CPU tensors raise.
+rules are in include/monorec_hip.h, restated in numpy by tests/tsdf_mesh_ref.py.  `render()` casts the volume back into one camera or a
+batch (`mr_tsdf_render_f32`: a thread per pixel marches its ray in camera-z steps to the first crossing from non-negative to negative
+trilinear tsdf) and returns depth, the unit surface normal (the interpolant's gradient, in world axes) and colour per pixel;
+`render_result()` is that depth as the model's inverse-depth `result`, 0 where nothing was hit, for `metrics.*_sparse_onlyvalid_metric`.
+`skip_grid()` (`mr_tsdf_skip_grid_u8`) is a byte per brick of 4^3 voxels that lets the march pass empty space with one load per sample
+and changes no bit of the result; header and tests/tsdf_render_ref.py as above.  There is no CPU fallback: CPU tensors raise.
 
 `run(config)` takes the configs of `pointcloud.run` / `tsdf_export.run` and drives the same pipelined loop
 (`tsdf_export.KeyframeStream`): per keyframe one pack launch into a staging slot on the device, per `fuse_batch` keyframes one
-integrate launch on the same stream; nothing is copied to the host before the surface is written.
+integrate launch on the same stream; nothing is copied to the host before the surface is written.  With `fused_metrics` in the config,
+`Fusion.score()` renders the fused volume into every exported keyframe again and scores it against the dataset's targets; with
+`render_dir`, `write()` also writes those views as 16-bit centimetre PNGs and JPEGs.
 
-Not here: vertex normals, decimation or marching cubes for the mesh; sparse or hashed volumes (the volume is dense, `max_bytes` bounds
+Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; sparse or hashed volumes (the volume is dense, `max_bytes` bounds
 it; `save()` writes it as an .npz); a cap on the weight; fusing across ranks (`run` is single-process)."""
 import ctypes
 import math
@@ -38,6 +45,7 @@ from .pointcloud import write_mesh_ply, write_ply
 
 MAX_FRAMES = _lib.MR_TSDF_MAX_FRAMES          # keyframes per integrate launch
 TILE = _lib.MR_TSDF_TILE                      # (x, y, z) voxels of one workgroup of the integrate kernel: the unit of its frustum culling
+BRICK = _lib.MR_TSDF_BRICK                    # edge of one brick of `TSDFVolume.skip_grid` in voxels
 
 
 def _need_cuda(t, what):
@@ -150,6 +158,7 @@ class TSDFVolume:
                 self.colour = None
         self._origin = (ctypes.c_float * 3)(*self.origin)
         self._keep = None
+        self._skip = {}                                        # min_weight -> skip_grid(min_weight), dropped by whatever writes the volume
         self.frames = 0                                        # keyframes integrated so far
         self.reset()
 
@@ -163,6 +172,7 @@ class TSDFVolume:
         with torch.cuda.device(self.device):
             _lib.check(_lib.load().mr_tsdf_volume_reset_f32(*self._volume_args(), self._stream()), "mr_tsdf_volume_reset_f32")
         self.frames = 0
+        self.drop_skip_grids()
 
     # -- integrate
     def integrate(self, depth_cm, colour, cam_to_world, intrinsics, max_depth_m=None):
@@ -232,6 +242,7 @@ class TSDFVolume:
                 _lib.check(lib.mr_tsdf_integrate_f32(*self._volume_args(), self._origin, self.voxel_size, self.trunc, limit, array, len(array),
                                                      prepared["size"][0], prepared["size"][1], self._stream()), "mr_tsdf_integrate_f32")
         self._keep = prepared["keep"]                          # alive until the launches have run (same stream: the next call may drop them)
+        self.drop_skip_grids()
         self.frames += prepared["count"]
 
     # -- surface
@@ -324,6 +335,78 @@ class TSDFVolume:
                 write_mesh_ply(f, vertices, triangles)
         return vertices.shape[0], triangles.shape[0]
 
+    # -- the volume seen from a camera
+    def skip_grid(self, min_weight=0):
+        """(bz, by, bx) uint8 on the device, one byte per brick of `BRICK`^3 voxels: 1 where a voxel of weight > min_weight and negative
+        tsdf lies in the brick or on its + faces (`mr_tsdf_skip_grid_u8`: one sweep of the volume).  Cached per `min_weight` until the
+        volume is written through this object (`integrate*`, `reset`, `load`); call `drop_skip_grids()` after writing the arrays directly."""
+        key = float(np.float32(min_weight))
+        if key != key:
+            raise ValueError("skip_grid: min_weight is NaN")
+        grid = self._skip.get(key)
+        if grid is None:
+            shape = tuple((d + BRICK - 1) // BRICK for d in reversed(self.dims))
+            grid = torch.empty(shape, dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().mr_tsdf_skip_grid_u8(self.tsdf.data_ptr(), self.weight.data_ptr(), *self.dims, key, grid.data_ptr(),
+                                                            self._stream()), "mr_tsdf_skip_grid_u8")
+            self._skip[key] = grid
+        return grid
+
+    def drop_skip_grids(self):
+        self._skip = {}
+
+    def render(self, cam_to_world, intrinsics, height, width, t_min=0.0, t_max=None, step=None, min_weight=0, normals=True, colour=True,
+               skip=True):
+        """Ray-cast the volume into one camera or a batch: cam_to_world (4, 4) / (B, 4, 4) anywhere, intrinsics one 3 x 3 / 4 x 4 matrix
+        or one per pose, images of height x width.  Every ray is sampled at camera-z depths t_min, t_min + step, ... <= t_max metres
+        (`step` defaults to the voxel size, `t_max` to t_min plus the volume's diagonal) and ends at the first crossing from
+        non-negative to negative tsdf between two samples whose 8 corners all have weight > min_weight (`mr_tsdf_render_f32`; the
+        arithmetic is in include/monorec_hip.h).  Launches of at most 8 views on the current stream.  Returns
+        dict(depth (B, h, w) fp32 metres, 0 where nothing was hit, normal (B, h, w, 3) fp32 unit vectors in world axes pointing out
+        of the surface | None, colour (B, h, w, 3) uint8 | None) on the device.  `skip`: march with `skip_grid(min_weight)`, which
+        changes no bit of the result."""
+        poses = torch.as_tensor(cam_to_world).detach().to("cpu", torch.float32).reshape(-1, 4, 4)
+        ks = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32)
+        ks = ks.reshape(-1, ks.shape[-2], ks.shape[-1])
+        b, height, width = poses.shape[0], int(height), int(width)
+        if b < 1 or ks.shape[0] not in (1, b):
+            raise ValueError(f"render: {b} poses, {ks.shape[0]} intrinsics (one, or one per pose)")
+        if height < 1 or width < 1:
+            raise ValueError(f"render: an image of {height} x {width}")
+        t_min = float(t_min)
+        step = self.voxel_size if step is None else float(step)
+        if t_max is None:
+            t_max = t_min + self.voxel_size * math.sqrt(sum(d * d for d in self.dims))
+        depth = torch.empty(b, height, width, dtype=torch.float32, device=self.device)
+        normal = torch.empty(b, height, width, 3, dtype=torch.float32, device=self.device) if normals else None
+        image = torch.empty(b, height, width, 3, dtype=torch.uint8, device=self.device) if colour else None
+        views = []
+        for i in range(b):
+            k = ks[i if ks.shape[0] == b else 0]
+            view = _lib.TsdfRayView()
+            view.m[:] = [float(v) for v in poses[i][:3, :4].reshape(-1)]
+            view.fx, view.fy, view.cx, view.cy = float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+            view.depth = depth[i].data_ptr()
+            view.normal = normal[i].data_ptr() if normals else None
+            view.colour = image[i].data_ptr() if colour else None
+            views.append(view)
+        bricks = self.skip_grid(min_weight).data_ptr() if skip else None
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            for lo in range(0, b, MAX_FRAMES):
+                chunk = views[lo:lo + MAX_FRAMES]
+                _lib.check(lib.mr_tsdf_render_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), bricks,
+                                                  (_lib.TsdfRayView * len(chunk))(*chunk), len(chunk), height, width, t_min, float(t_max), step,
+                                                  self._stream()), "mr_tsdf_render_f32")
+        return dict(depth=depth, normal=normal, colour=image)
+
+    def render_result(self, cam_to_world, intrinsics, height, width, **kwargs):
+        """The rendered depth in the model's `result` convention: (B, 1, h, w) inverse depth, 0 where nothing was hit - what
+        `metrics.*_sparse_onlyvalid_metric` (`pred_all_valid=False`) scores.  Keywords as `render` (normals and colour are not rendered)."""
+        depth = self.render(cam_to_world, intrinsics, height, width, **dict(kwargs, normals=False, colour=False))["depth"]
+        return torch.where(depth > 0, 1.0 / depth, torch.zeros_like(depth)).unsqueeze(1)
+
     # -- the volume itself
     def grids(self):
         """Host copies shaped (nz, ny, nx): tsdf, weight, colour (nz, ny, nx, 4) or None."""
@@ -350,6 +433,7 @@ class TSDFVolume:
             if volume.colour is not None:
                 volume.colour.copy_(torch.from_numpy(z["colour"].reshape(-1, 4)))
             volume.frames = int(z["frames"]) if "frames" in z.files else 0
+            volume.drop_skip_grids()
         return volume
 
 
@@ -412,9 +496,13 @@ def fuse_directory(directory, volume=None, voxel_size=0.1, trunc=None, colour=Tr
 
 
 # ------------------------------------------------------------------------------------------ the runner
+# the metrics `Fusion.score()` can report, in metrics.metrics_from_sums' order: the onlyvalid variants leave out what a render did not hit
+FUSED_METRICS = tuple(f"{base}_sparse_onlyvalid_metric" for base in ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3"))
+
+
 def fusion_settings(config):
     """The fusion keys of a runner config, checked: dict(voxel_size, trunc, bounds, max_bytes, fuse_batch, file_name, mesh_file_name,
-    save_volume)."""
+    save_volume, fused_metrics, render_dir)."""
     voxel = float(config.get("voxel_size", 0.1))
     trunc_voxels = float(config.get("trunc_voxels", 5))
     batch = int(config.get("fuse_batch", 4))
@@ -429,9 +517,14 @@ def fusion_settings(config):
         raise ValueError("monorec_amd.tsdf_fusion: the config has neither `bounds` nor `max_d`; one of them is needed to size the volume")
     if bounds is not None:
         dims_of_bounds(bounds, voxel)
+    fused_metrics = config.get("fused_metrics", None)
+    fused_metrics = [] if fused_metrics is None else fused_metrics
+    if not isinstance(fused_metrics, (list, tuple)) or any(name not in FUSED_METRICS for name in fused_metrics):
+        raise ValueError(f"monorec_amd.tsdf_fusion: fused_metrics {fused_metrics!r} must be a list of *_sparse_onlyvalid_metric names "
+                         f"({', '.join(FUSED_METRICS)}): a render is 0 where no surface was hit, which only they leave out")
     return dict(voxel_size=voxel, trunc=trunc_voxels * voxel, bounds=bounds, max_bytes=int(config.get("tsdf_max_bytes", 8 << 30)),
                 fuse_batch=batch, file_name=config.get("file_name", "tsdf.ply"), mesh_file_name=config.get("mesh_file_name", None),
-                save_volume=config.get("save_volume", None))
+                save_volume=config.get("save_volume", None), fused_metrics=list(fused_metrics), render_dir=config.get("render_dir", None))
 
 
 class Fusion:
@@ -500,7 +593,67 @@ class Fusion:
             self.mesh_counts = self.volume.save_mesh_ply(os.path.join(out_dir, self.settings["mesh_file_name"]))
         if self.settings["save_volume"] is not None:
             self.volume.save(self.settings["save_volume"])
+        if self.settings["render_dir"] is not None:
+            self.write_renders(self.settings["render_dir"])
         return count
+
+    # -- the fused volume seen from the keyframes again
+    def _render_range(self):
+        max_d = self.config.get("max_d", None)
+        return dict(t_min=0.0, t_max=None if max_d is None else float(max_d))
+
+    def score(self, roi=None, max_distance=None):
+        """A second pass over the exported keyframes, without the model: the volume rendered into every keyframe's camera
+        (`keyframe_pose`, the uncropped `keyframe_intrinsics`, the dataset's `target_image_size`; eight views per launch) and scored
+        against the sample's target with the config's `fused_metrics`.  The metric sums stay on the device until the end.  `roi` /
+        `max_distance`: as the metric functions take them.  Returns dict(metrics {name: value} - each what the metric function of that
+        name returns for all samples as one batch -, coverage: the share of target pixels the render hit, samples)."""
+        from . import metrics
+        stream, volume = self.stream, self.volume
+        items = stream.export_items()
+        height, width = stream.height, stream.width
+        sums, hit, have = [], torch.zeros((), dtype=torch.int64, device=volume.device), torch.zeros((), dtype=torch.int64, device=volume.device)
+        for lo in range(0, len(items), MAX_FRAMES):
+            samples = [stream.dataset[i] for i in items[lo:lo + MAX_FRAMES]]
+            target = torch.stack([torch.as_tensor(t).to(volume.device).reshape(1, height, width) for _, t in samples])
+            result = volume.render_result(torch.stack([_matrix(d["keyframe_pose"], "keyframe_pose") for d, _ in samples]),
+                                          torch.stack([_matrix(d["keyframe_intrinsics"], "keyframe_intrinsics") for d, _ in samples]),
+                                          height, width, **self._render_range())
+            sums.append(metrics.sparse_metric_sums_device(dict(result=result, target=target), roi, max_distance, pred_all_valid=False))
+            have += (target > 0).sum()
+            hit += ((target > 0) & (result != 0)).sum()
+        if not sums:
+            return dict(metrics={name: float("nan") for name in self.settings["fused_metrics"]}, coverage=float("nan"), samples=0)
+        values = metrics.metrics_from_sums(torch.cat(sums).cpu())
+        have = int(have.item())
+        return dict(metrics={name: float(values[FUSED_METRICS.index(name)]) for name in self.settings["fused_metrics"]},
+                    coverage=int(hit.item()) / have if have else float("nan"), samples=len(items))
+
+    def write_renders(self, directory):
+        """Per exported keyframe the fused depth and colour as the export would have written them - the crop's size and shifted
+        intrinsics, `frame-%06d.fused.depth.png` (16 bit, centimetres, 0: nothing) and `frame-%06d.fused.color.jpg`, names that sort
+        next to the export's.  After the fusion and synchronous: not a stage of the loop.  Returns the number of keyframes."""
+        from PIL import Image
+        stream, volume = self.stream, self.volume
+        os.makedirs(str(directory), exist_ok=True)
+        items = stream.export_items()
+        y0, y1, x0, x1 = tx.crop_box(stream.crop, stream.height, stream.width)
+        first = stream.plan["exports"][0]
+        for lo in range(0, len(items), MAX_FRAMES):
+            chunk = items[lo:lo + MAX_FRAMES]
+            if hasattr(stream.dataset, "keyframe_geometry"):
+                geometry = [stream.dataset.keyframe_geometry(i) for i in chunk]
+            else:
+                geometry = [(d["keyframe_pose"], d["keyframe_intrinsics"]) for d, _ in (stream.dataset[i] for i in chunk)]
+            views = volume.render(torch.stack([_matrix(g[0], "keyframe_pose") for g in geometry]), torch.stack([self.shifted(g[1]) for g in geometry]),
+                                  y1 - y0, x1 - x0, normals=False, **self._render_range())
+            depth_cm = (views["depth"] * 100.0).clamp_(0.0, 65535.0).to(torch.int32).cpu().numpy().astype(np.uint16)
+            colour = views["colour"].cpu().numpy()
+            for j in range(len(chunk)):
+                base = os.path.join(str(directory), f"frame-{first + lo + j:06d}.fused")
+                Image.fromarray(depth_cm[j]).save(base + ".depth.png")
+                Image.fromarray(colour[j]).save(base + ".color.jpg")
+        return len(items)
 
 
 def run(config, model=None, dataset=None, device="cuda:0"):
@@ -508,7 +661,8 @@ def run(config, model=None, dataset=None, device="cuda:0"):
     `use_mask`) and write the surface points to `output_dir/file_name` (default `tsdf.ply`).  Optional keys: `voxel_size` (0.1),
     `trunc_voxels` (5), `mesh_file_name` (None; a name: the surface is also written as a triangle mesh, `TSDFVolume.save_mesh_ply`, next to
     the points), `bounds` (else `bounds_from_frusta` over the window's exported keyframe poses and `max_d`; without both it
-    raises), `tsdf_max_bytes`, `fuse_batch` (keyframes per integrate launch, default 4), `save_volume` (a path for `TSDFVolume.save`).
+    raises), `tsdf_max_bytes`, `fuse_batch` (keyframes per integrate launch, default 4), `save_volume` (a path for `TSDFVolume.save`),
+    `render_dir` (a directory for `Fusion.write_renders`), `fused_metrics` (names for `Fusion.score()`; `main` prints its result).
 
     Per keyframe `pack_frames` (vote, crop, thresholds: the depths are exactly the ones the export writes to the PNG) fills a staging slot
     on the device; after `fuse_batch` keyframes, or at the end, one integrate launch follows on the same stream.  Every keyframe is
@@ -525,6 +679,13 @@ def main(argv=None):
     if fusion.mesh_counts is not None:
         print(f"{fusion.mesh_counts[0]} vertices and {fusion.mesh_counts[1]} triangles written to "
               f"{os.path.join(config.get('output_dir', 'saved'), config['mesh_file_name'])}")
+    if fusion.settings["render_dir"] is not None:
+        print(f"fused depth and colour of every exported keyframe written to {fusion.settings['render_dir']}")
+    if fusion.settings["fused_metrics"]:
+        scored = fusion.score()
+        for name, value in scored["metrics"].items():
+            print(f"{name}: {value:.6f}")
+        print(f"fused coverage: {scored['coverage']:.4f} of the target pixels of {scored['samples']} keyframes")
 
 
 if __name__ == "__main__":
