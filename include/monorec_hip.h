@@ -743,11 +743,15 @@ int mr_tsdf_integrate_f32(float* tsdf, float* weight, uint8_t* colour, int32_t n
  * when weight[v] > min_weight, weight[n] > min_weight and (tsdf[v] < 0) != (tsdf[n] < 0):
  *   s = tsdf[v] / (tsdf[v] - tsdf[n]);  pos_a = (origin_a + (float)i_a * voxel_size) + s * voxel_size, the other two coordinates p of v
  *   value_c = floorf((float)C_v + s * ((float)C_n - (float)C_v) + .5)                       (0 without a colour volume)
- * One record of 6 floats x y z red green blue per point, the record of mr_pointcloud_append_f32, in no particular order.  Every
- * workgroup draws its range of records with one atomicAdd on *cursor (int64 in device memory, set by the caller, normally to 0) and
- * writes those below capacity_records; *cursor ends advanced by the number of points whatever the capacity.  records NULL: count only
- * (capacity_records is ignored) - count, allocate exactly, zero the cursor, fill.  cursor NULL, capacity_records < 0, NaN min_weight:
- * MR_ERR_BAD_ARGUMENT. */
+ * One record of 6 floats x y z red green blue per point, the record of mr_pointcloud_append_f32, in no particular order.  A workgroup
+ * owns a tile of MR_TSDF_TILE_X x _Y x _Z voxels (the vertex kernel of the mesh below, over the three axis edges of a voxel alone); it
+ * draws its range of records with one atomicAdd on *cursor (int64 in device memory, set by the caller, normally to 0) and writes those
+ * below capacity_records; *cursor ends advanced by the number of points whatever the capacity.  A tile with no seen negative voxel
+ * in reach (its own voxels and one beyond its high faces) touches neither the records nor the cursor.  records NULL: count only
+ * (capacity_records is ignored) - count, allocate exactly, zero the cursor, fill.  Voxel indices are 64 bit: volumes of 2^31 voxels
+ * and more are served.  The launch has one workgroup per tile, so 2^31 tiles or more (it was: 2^31 blocks of 256 voxels) are
+ * MR_ERR_BAD_ARGUMENT, as for mr_tsdf_integrate_f32, and so is - here and for the two mesh entries - nx > 2^31 - 35, ny > 2^31 - 11
+ * or nz > 2^31 - 7, where the halo staged with the last tile would leave the int32 range.  cursor NULL, capacity_records < 0, NaN min_weight: MR_ERR_BAD_ARGUMENT. */
 int mr_tsdf_extract_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
                         const float* origin, float voxel_size, float min_weight, float* records, int64_t capacity_records,
                         int64_t* cursor, void* stream);

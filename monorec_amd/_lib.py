@@ -384,3 +384,9 @@ def check(code, what=""):
     if code != 0:
         msg = load().mr_error_string(int(code))
         raise RuntimeError(f"{what}: {msg.decode() if msg else code} (code {code})")
+
+
+def need_cuda(module, t, what):
+    """Raise for module `monorec_amd.<module>` unless the tensor `t`, `what` in the message, is on a device."""
+    if not t.is_cuda:
+        raise RuntimeError(f"monorec_amd.{module}: {what} must be a CUDA (HIP) tensor - there is no CPU fallback")

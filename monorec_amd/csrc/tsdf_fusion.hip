@@ -6,8 +6,12 @@
 //   tsdf_reset_kernel       tsdf = 1, weight = 0, colour = 0
 //   tsdf_integrate_kernel   up to MR_TSDF_MAX_FRAMES keyframes per launch: a voxel is loaded once, updated by the frames in order in
 //                           registers and stored once, and only by a thread one of whose voxels a frame updated
-//   tsdf_extract_kernel     edge crossings as x y z r g b records; with records == nullptr it only counts
-//   tsdf_mesh_vertices_kernel, tsdf_mesh_triangles_kernel   the same surface as an indexed mesh (marching tetrahedra; further down)
+//   tsdf_mesh_vertices_kernel<3>   edge crossings on the three axis edges of a voxel as x y z r g b records (mr_tsdf_extract_f32); with
+//                           no output it only counts
+//   tsdf_mesh_vertices_kernel<7>, tsdf_mesh_triangles_kernel   the same surface as an indexed mesh (marching tetrahedra; further down):
+//                           the same kernel over all seven edges a voxel owns, which also writes vertex_base, and the triangles
+//   tsdf_skip_grid_kernel, tsdf_render_kernel   the volume seen from a camera (at the end)
+// All but reset and render sweep the volume in one tile, decoded from blockIdx by tile_of_block.
 //
 // The integration sweeps the volume: 8 bytes (12 with colour) in and out per voxel and frame BATCH, the depth and colour images are
 // gathered through the caches (a keyframe is a few hundred KB).  Measured kernel time (DESIGN.md section 7, 512 x 512 x 128 voxels,
@@ -63,13 +67,22 @@ __device__ __forceinline__ unsigned blend_byte(unsigned old, unsigned pix, float
     return (unsigned)c;
 }
 
-__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs a) {
+// The workgroup's tile from blockIdx.  <TX, TY, TZ>: its first voxel; <1, 1, 1>: its index in tiles per axis, for the kernels that
+// multiply at each use (they did before the decode was shared, and keep their instruction order that way).
+struct Tile { int x, y, z; };
+
+template <int UX, int UY, int UZ>
+__device__ __forceinline__ Tile tile_of_block(int tiles_x, int tiles_y) {
     const int tile = blockIdx.x;
-    const int bx = tile % a.tiles_x, by = (tile / a.tiles_x) % a.tiles_y, bz = tile / (a.tiles_x * a.tiles_y);
+    return {(tile % tiles_x) * UX, ((tile / tiles_x) % tiles_y) * UY, (tile / (tiles_x * tiles_y)) * UZ};
+}
+
+__global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs a) {
+    const Tile b = tile_of_block<1, 1, 1>(a.tiles_x, a.tiles_y);
     // which frames can reach this tile: the centre of the (full) tile against the five planes of each frame
-    const float ccx = a.ox + ((float)(bx * TX) + 0.5f * (TX - 1)) * a.voxel;
-    const float ccy = a.oy + ((float)(by * TY) + 0.5f * (TY - 1)) * a.voxel;
-    const float ccz = a.oz + ((float)(bz * TZ) + 0.5f * (TZ - 1)) * a.voxel;
+    const float ccx = a.ox + ((float)(b.x * TX) + 0.5f * (TX - 1)) * a.voxel;
+    const float ccy = a.oy + ((float)(b.y * TY) + 0.5f * (TY - 1)) * a.voxel;
+    const float ccz = a.oz + ((float)(b.z * TZ) + 0.5f * (TZ - 1)) * a.voxel;
     unsigned live = 0;
     for (int fi = 0; fi < a.num_frames; ++fi) {
         bool out = false;
@@ -84,7 +97,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
     if (live == 0) return;
 
     const int tid = threadIdx.x;
-    const int x = bx * TX + (tid & 7) * 4, y = by * TY + ((tid >> 3) & 7), z = bz * TZ + (tid >> 6);
+    const int x = b.x * TX + (tid & 7) * 4, y = b.y * TY + ((tid >> 3) & 7), z = b.z * TZ + (tid >> 6);
     if (x >= a.nx || y >= a.ny || z >= a.nz) return;
     const int n = a.nx - x < 4 ? a.nx - x : 4;
     const long long idx = ((long long)z * a.ny + y) * a.nx + x;
@@ -172,98 +185,20 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
     }
 }
 
-struct ExtractArgs {
-    const float* tsdf;
-    const float* weight;
-    const unsigned* colour;                      // r g b 0 per voxel or null
-    int nx, ny, nz;
-    long long voxels;
-    float ox, oy, oz, voxel, min_weight;
-    float* records;                              // null: count only
-    long long capacity;
-    unsigned long long* cursor;
-};
-
-__device__ __forceinline__ float mix_byte(unsigned cv, unsigned cn, float s) {
-    const float fv = (float)cv, fn = (float)cn;
-    return floorf(fv + s * (fn - fv) + 0.5f);
-}
-
-__global__ __launch_bounds__(256) void tsdf_extract_kernel(const ExtractArgs a) {
-    __shared__ int wave_tot[4];
-    __shared__ unsigned long long s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long i = (long long)blockIdx.x * 256 + tid;
-    const long long plane = (long long)a.nx * a.ny;
-    int x = 0, y = 0, z = 0, hits = 0;
-    float tv = 0.f, tn[3] = {0.f, 0.f, 0.f};
-    long long step[3] = {1, a.nx, plane};
-    if (i < a.voxels) {
-        z = (int)(i / plane);
-        const long long r = i - (long long)z * plane;
-        y = (int)(r / a.nx);
-        x = (int)(r - (long long)y * a.nx);
-        if (a.weight[i] > a.min_weight) {
-            tv = a.tsdf[i];
-            const bool inside[3] = {x + 1 < a.nx, y + 1 < a.ny, z + 1 < a.nz};
-#pragma unroll
-            for (int e = 0; e < 3; ++e) {
-                if (!inside[e] || !(a.weight[i + step[e]] > a.min_weight)) continue;
-                tn[e] = a.tsdf[i + step[e]];
-                if ((tv < 0.0f) != (tn[e] < 0.0f)) hits |= 1 << e;
-            }
-        }
-    }
-    const int mine = __popc(hits);
-    // exclusive prefix of `mine` over the workgroup: shuffles within the wave, wave totals through LDS
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int before = incl - mine, total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const int v = wave_tot[w]; if (w < wave) before += v; total += v; }
-    if (total == 0) return;
-    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);       // one per workgroup
-    if (!a.records) return;
-    __syncthreads();
-    if (!hits) return;
-    long long rec = (long long)s_base + before;
-    const float p[3] = {a.ox + (float)x * a.voxel, a.oy + (float)y * a.voxel, a.oz + (float)z * a.voxel};
-    const unsigned cv = a.colour ? a.colour[i] : 0u;
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        if (!(hits & (1 << e))) continue;
-        if (rec < a.capacity) {
-            const float s = tv / (tv - tn[e]);
-            float* o = a.records + rec * 6;
-            o[0] = p[0]; o[1] = p[1]; o[2] = p[2];
-            o[e] = p[e] + s * a.voxel;
-            const unsigned cn = a.colour ? a.colour[i + step[e]] : 0u;
-            o[3] = mix_byte(cv & 0xffu, cn & 0xffu, s);
-            o[4] = mix_byte((cv >> 8) & 0xffu, (cn >> 8) & 0xffu, s);
-            o[5] = mix_byte((cv >> 16) & 0xffu, (cn >> 16) & 0xffu, s);
-        }
-        ++rec;
-    }
-}
-
-// ---- the surface as a welded triangle mesh: marching tetrahedra over the Kuhn split (include/monorec_hip.h has the rules) ----------
+// ---- the surface: points on the grid's axis edges, or a welded triangle mesh by marching tetrahedra over the Kuhn split -------------
+// (include/monorec_hip.h has the rules)
 //
-// Both kernels give a workgroup of 256 threads the integrate kernel's tile of 32 x 8 x 4 voxels, a thread the four voxels (cubes) of
+// The kernels give a workgroup of 256 threads the integrate kernel's tile of 32 x 8 x 4 voxels, a thread the four voxels (cubes) of
 // one (x, y) column of it, and stage what the tile needs in LDS so that every value is read from memory once per workgroup, not once
 // per edge or tetrahedron that touches it:
 //   tsdf_mesh_vertices_kernel   tsdf (fp32) and a code byte (bit 0 seen, bit 1 seen and negative) of the tile plus one voxel beyond its
-//                               high faces, 33 x 9 x 5 (7.4 KB): the far ends of the seven edges a voxel owns
+//                               high faces, 33 x 9 x 5 (7.4 KB): the far ends of the edges a voxel owns - all seven for the mesh, the
+//                               three along the axes for the points, whose records are the mesh's vertices on those edges bit for bit
 //   tsdf_mesh_triangles_kernel  the code byte alone for the tile plus TWO voxels, 34 x 10 x 6 (2 KB): a cube's tetrahedra use edges owned
 //                               by its corners, and the rank of an edge among its owner's vertices needs the owner's whole mask, which
 //                               reaches one voxel beyond the cube.  The masks of the 33 x 9 x 5 owners follow from the codes (1.5 KB).
 // A tile whose staged block holds no seen negative voxel - nearly all of a fused volume: in front of every surface or never seen -
-// leaves at the barrier that ends the staging (__syncthreads_or) and has touched neither vertex_base nor the cursor.
+// leaves at the barrier that ends the staging (__syncthreads_or) and has touched neither its output, nor vertex_base, nor the cursor.
 constexpr int VSX = TX + 1, VSY = TY + 1, VSZ = TZ + 1, VSN = VSX * VSY * VSZ;           // staged block of the vertex kernel
 constexpr int CSX = TX + 2, CSY = TY + 2, CSZ = TZ + 2, CSN = CSX * CSY * CSZ;           // staged codes of the triangle kernel
 constexpr unsigned SEEN = 1u, NEG = 2u;
@@ -276,13 +211,13 @@ struct MeshArgs {
     int tiles_x, tiles_y;
     float ox, oy, oz, voxel, min_weight;
     float* vertices;                             // null: count only
-    int* vertex_base;                            // written by the vertex kernel, read by the triangle kernel
+    int* vertex_base;                            // written by the 7-edge vertex kernel, read by the triangle kernel
     int* triangles;                              // null: count only
     long long capacity;
     unsigned long long* cursor;
 };
 
-// exclusive prefix of `mine` over the workgroup and its total: shuffles within the wave, wave totals through LDS (as tsdf_extract_kernel)
+// exclusive prefix of `mine` over the workgroup and its total: shuffles within the wave, wave totals through LDS
 __device__ __forceinline__ int workgroup_prefix(int mine, int* wave_tot, int& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     int incl = mine;
@@ -300,27 +235,42 @@ __device__ __forceinline__ int workgroup_prefix(int mine, int* wave_tot, int& to
     return before;
 }
 
-// the 7-bit active-edge mask of the voxel at `at` of a block of codes with row stride sx and slice stride sxy
+// red green blue of a record, between the packed colours cv and cn of the edge's two voxels
+__device__ __forceinline__ void write_colour(float* o, unsigned cv, unsigned cn, float s) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float fv = (float)((cv >> (8 * c)) & 0xffu), fn = (float)((cn >> (8 * c)) & 0xffu);
+        o[3 + c] = floorf(fv + s * (fn - fv) + 0.5f);
+    }
+}
+
+// the active-edge mask, over the first EDGES of the seven, of the voxel at `at` of a block of codes with row stride sx and slice stride sxy
+template <int EDGES>
 __device__ __forceinline__ unsigned edge_mask(const uint8_t* code, int at, int sx, int sxy) {
     const unsigned c = code[at];
     if (!(c & SEEN)) return 0u;
     const int far[7] = {1, sx, sxy, 1 + sx, 1 + sxy, sx + sxy, 1 + sx + sxy};
     unsigned mask = 0;
 #pragma unroll
-    for (int e = 0; e < 7; ++e) {
+    for (int e = 0; e < EDGES; ++e) {
         const unsigned n = code[at + far[e]];
         if ((n & SEEN) && ((n ^ c) & NEG)) mask |= 1u << e;
     }
     return mask;
 }
 
+// EDGES = 7: the vertices of the mesh, and vertex_base.  EDGES = 3: the axis edges alone, the points of mr_tsdf_extract_f32; nothing
+// of it indexes with int32, so it serves volumes past 2^31 voxels.
+template <int EDGES>
 __global__ __launch_bounds__(256) void tsdf_mesh_vertices_kernel(const MeshArgs a) {
+    static_assert(EDGES == 3 || EDGES == 7, "the axis edges, or all a voxel owns");
     __shared__ float s_t[VSN];
     __shared__ uint8_t s_code[VSN];
     __shared__ int wave_tot[4];
     __shared__ unsigned long long s_base;
-    const int tid = threadIdx.x, tile = blockIdx.x;
-    const int x0 = (tile % a.tiles_x) * TX, y0 = ((tile / a.tiles_x) % a.tiles_y) * TY, z0 = (tile / (a.tiles_x * a.tiles_y)) * TZ;
+    const int tid = threadIdx.x;
+    const Tile o = tile_of_block<TX, TY, TZ>(a.tiles_x, a.tiles_y);
+    const int x0 = o.x, y0 = o.y, z0 = o.z;
     const long long plane = (long long)a.nx * a.ny;
     int any_neg = 0;
     for (int i = tid; i < VSN; i += 256) {
@@ -344,7 +294,7 @@ __global__ __launch_bounds__(256) void tsdf_mesh_vertices_kernel(const MeshArgs 
     const int lx = tid & 31, ly = tid >> 5;
     unsigned masks = 0;                          // the masks of the thread's four voxels, a byte each
 #pragma unroll
-    for (int j = 0; j < TZ; ++j) masks |= edge_mask(s_code, (j * VSY + ly) * VSX + lx, VSX, VSX * VSY) << (8 * j);
+    for (int j = 0; j < TZ; ++j) masks |= edge_mask<EDGES>(s_code, (j * VSY + ly) * VSX + lx, VSX, VSX * VSY) << (8 * j);
     const int mine = __popc(masks);
     int total;
     const int before = workgroup_prefix(mine, wave_tot, total);
@@ -365,23 +315,20 @@ __global__ __launch_bounds__(256) void tsdf_mesh_vertices_kernel(const MeshArgs 
         if (!mask) continue;
         const int gz = z0 + j, at = (j * VSY + ly) * VSX + lx;
         const long long g = (long long)gz * plane + (long long)gy * a.nx + gx;
-        a.vertex_base[g] = (int)rec;
+        if constexpr (EDGES == 7) a.vertex_base[g] = (int)rec;
         const float p[3] = {px, py, a.oz + (float)gz * a.voxel};
         const float tv = s_t[at];
         const unsigned cv = a.colour ? a.colour[g] : 0u;
 #pragma unroll
-        for (int e = 0; e < 7; ++e) {
+        for (int e = 0; e < EDGES; ++e) {
             if (!(mask & (1u << e))) continue;
             if (rec < a.capacity) {
                 const float s = tv / (tv - s_t[at + s_far[e]]);
                 const float step = s * a.voxel;
-                float* o = a.vertices + rec * 6;
+                float* r = a.vertices + rec * 6;
 #pragma unroll
-                for (int k = 0; k < 3; ++k) o[k] = (along[e] >> k) & 1u ? p[k] + step : p[k];
-                const unsigned cn = a.colour ? a.colour[g + g_far[e]] : 0u;
-                o[3] = mix_byte(cv & 0xffu, cn & 0xffu, s);
-                o[4] = mix_byte((cv >> 8) & 0xffu, (cn >> 8) & 0xffu, s);
-                o[5] = mix_byte((cv >> 16) & 0xffu, (cn >> 16) & 0xffu, s);
+                for (int k = 0; k < 3; ++k) r[k] = (along[e] >> k) & 1u ? p[k] + step : p[k];
+                write_colour(r, cv, a.colour ? a.colour[g + g_far[e]] : 0u, s);
             }
             ++rec;
         }
@@ -419,8 +366,9 @@ __global__ __launch_bounds__(256) void tsdf_mesh_triangles_kernel(const MeshArgs
     __shared__ uint8_t s_mask[VSN];
     __shared__ int wave_tot[4];
     __shared__ unsigned long long s_base;
-    const int tid = threadIdx.x, tile = blockIdx.x;
-    const int x0 = (tile % a.tiles_x) * TX, y0 = ((tile / a.tiles_x) % a.tiles_y) * TY, z0 = (tile / (a.tiles_x * a.tiles_y)) * TZ;
+    const int tid = threadIdx.x;
+    const Tile o = tile_of_block<TX, TY, TZ>(a.tiles_x, a.tiles_y);
+    const int x0 = o.x, y0 = o.y, z0 = o.z;
     const long long plane = (long long)a.nx * a.ny;
     int any_neg = 0;
     for (int i = tid; i < CSN; i += 256) {
@@ -452,7 +400,7 @@ __global__ __launch_bounds__(256) void tsdf_mesh_triangles_kernel(const MeshArgs
     if (!a.triangles) return;
     for (int i = tid; i < VSN; i += 256) {
         const int sx = i % VSX, sy = (i / VSX) % VSY, sz = i / (VSX * VSY);
-        s_mask[i] = (uint8_t)edge_mask(s_code, (sz * CSY + sy) * CSX + sx, CSX, CSX * CSY);
+        s_mask[i] = (uint8_t)edge_mask<7>(s_code, (sz * CSY + sy) * CSX + sx, CSX, CSX * CSY);
     }
     __syncthreads();
     if (!mine) return;
@@ -492,9 +440,9 @@ __global__ __launch_bounds__(256) void tsdf_mesh_triangles_kernel(const MeshArgs
                     if (own == 2) { mo = m_own[2]; go = g_own[2]; }
                     v[k] = a.vertex_base[go] + __popc((unsigned)s_mask[mo] & ((1u << ty) - 1u));
                 }
-                int* o = a.triangles + tri * 3;
+                int* r = a.triangles + tri * 3;
                 const bool odd = t >= 3;
-                o[0] = v[0]; o[1] = odd ? v[2] : v[1]; o[2] = odd ? v[1] : v[2];
+                r[0] = v[0]; r[1] = odd ? v[2] : v[1]; r[2] = odd ? v[1] : v[2];
             }
         }
     }
@@ -506,10 +454,21 @@ long long voxel_count(int nx, int ny, int nz) {                  // MAX_VOXELS f
     return xy * nz;
 }
 
-bool bad_volume(const void* tsdf, const void* weight, int nx, int ny, int nz) {
-    if (!tsdf || !weight || nx < 1 || ny < 1 || nz < 1) return true;
-    if (((uintptr_t)tsdf | (uintptr_t)weight) & 3) return true;
+// The checks the entries share: the volume, and - where an entry takes them; the defaults pass - origin, voxel_size and min_weight.
+constexpr float NO_ORIGIN[3] = {0.0f, 0.0f, 0.0f};
+bool bad_volume(const void* tsdf, const void* weight, const void* colour, int nx, int ny, int nz, const float* origin = NO_ORIGIN,
+                float voxel_size = 1.0f, float min_weight = 0.0f) {
+    if (!tsdf || !weight || nx < 1 || ny < 1 || nz < 1 || !origin) return true;
+    if (((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)colour) & 3) return true;
+    if (!(voxel_size > 0.0f) || min_weight != min_weight) return true;
     return voxel_count(nx, ny, nz) >= MAX_VOXELS;
+}
+
+// The tiles per axis of a sweep and the launch's grid; 0 when that does not fit 2^31 - 1.  For a checked volume (under 2^40 voxels).
+unsigned tile_grid(int nx, int ny, int nz, int& tiles_x, int& tiles_y) {
+    tiles_x = (nx - 1) / TX + 1; tiles_y = (ny - 1) / TY + 1;
+    const long long tiles = (long long)tiles_x * tiles_y * ((nz - 1) / TZ + 1);
+    return tiles > 0x7fffffffLL ? 0u : (unsigned)tiles;
 }
 
 // The near and four side planes of one view in world space, in double.  A voxel can pass the kernel's cam_2 > 0 and image-bounds
@@ -548,7 +507,7 @@ void view_planes(const mr_tsdf_view& f, int h, int w, float out[5][4]) {
 }  // namespace
 
 extern "C" int mr_tsdf_volume_reset_f32(float* tsdf, float* weight, uint8_t* colour, int32_t nx, int32_t ny, int32_t nz, void* stream) {
-    if (bad_volume(tsdf, weight, nx, ny, nz) || ((uintptr_t)colour & 3)) return MR_ERR_BAD_ARGUMENT;
+    if (bad_volume(tsdf, weight, colour, nx, ny, nz)) return MR_ERR_BAD_ARGUMENT;
     const long long voxels = voxel_count(nx, ny, nz);
     long long blocks = (voxels + 255) / 256;
     if (blocks > 65536) blocks = 65536;                          // grid-stride beyond that
@@ -560,18 +519,17 @@ extern "C" int mr_tsdf_volume_reset_f32(float* tsdf, float* weight, uint8_t* col
 extern "C" int mr_tsdf_integrate_f32(float* tsdf, float* weight, uint8_t* colour, int32_t nx, int32_t ny, int32_t nz, const float* origin,
                                      float voxel_size, float trunc, float max_depth_m, const mr_tsdf_view* frames, int32_t num_frames,
                                      int32_t height, int32_t width, void* stream) {
-    if (bad_volume(tsdf, weight, nx, ny, nz) || ((uintptr_t)colour & 3) || !origin || !frames) return MR_ERR_BAD_ARGUMENT;
+    if (bad_volume(tsdf, weight, colour, nx, ny, nz, origin, voxel_size) || !frames) return MR_ERR_BAD_ARGUMENT;
     if (num_frames < 1 || num_frames > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return MR_ERR_BAD_ARGUMENT;
-    if (!(voxel_size > 0.0f) || !(trunc > 0.0f) || max_depth_m != max_depth_m) return MR_ERR_BAD_ARGUMENT;
+    if (!(trunc > 0.0f) || max_depth_m != max_depth_m) return MR_ERR_BAD_ARGUMENT;
     if ((long long)height * width * 3 >= (1ll << 40)) return MR_ERR_BAD_ARGUMENT;
     for (int i = 0; i < num_frames; ++i)
         if (!frames[i].depth_cm || (colour && !frames[i].colour)) return MR_ERR_BAD_ARGUMENT;
     IntegrateArgs a;
     a.tsdf = tsdf; a.weight = weight; a.colour = colour;
     a.nx = nx; a.ny = ny; a.nz = nz;
-    a.tiles_x = (nx + TX - 1) / TX; a.tiles_y = (ny + TY - 1) / TY;
-    const long long tiles = (long long)a.tiles_x * a.tiles_y * ((nz + TZ - 1) / TZ);
-    if (tiles > 0x7fffffffLL) return MR_ERR_BAD_ARGUMENT;
+    const unsigned tiles = tile_grid(nx, ny, nz, a.tiles_x, a.tiles_y);
+    if (!tiles) return MR_ERR_BAD_ARGUMENT;
     a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
     a.voxel = voxel_size; a.trunc = trunc; a.max_depth = max_depth_m;
     a.num_frames = num_frames; a.h = height; a.w = width;
@@ -599,62 +557,58 @@ extern "C" int mr_tsdf_integrate_f32(float* tsdf, float* weight, uint8_t* colour
     const double radius = 0.5 * v * sqrt((double)((TX - 1) * (TX - 1) + (TY - 1) * (TY - 1) + (TZ - 1) * (TZ - 1)));
     const double cull = radius + 1e-3 * v + 64.0 * 5.97e-8 * reach;
     a.cull_radius = isfinite(cull) ? nextafterf((float)cull, INFINITY) : INFINITY;       // infinite: `dist < -inf` never holds
-    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
-    return (int)hipGetLastError();
-}
-
-extern "C" int mr_tsdf_extract_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
-                                   const float* origin, float voxel_size, float min_weight, float* records, int64_t capacity_records,
-                                   int64_t* cursor, void* stream) {
-    if (bad_volume(tsdf, weight, nx, ny, nz) || ((uintptr_t)colour & 3) || !origin || !cursor) return MR_ERR_BAD_ARGUMENT;
-    const long long voxels = voxel_count(nx, ny, nz);
-    if (!(voxel_size > 0.0f) || min_weight != min_weight || (records && capacity_records < 0)) return MR_ERR_BAD_ARGUMENT;
-    if (((uintptr_t)records & 3) || ((uintptr_t)cursor & 7)) return MR_ERR_BAD_ARGUMENT;
-    const long long blocks = (voxels + 255) / 256;
-    if (blocks > 0x7fffffffLL) return MR_ERR_BAD_ARGUMENT;
-    ExtractArgs a;
-    a.tsdf = tsdf; a.weight = weight; a.colour = reinterpret_cast<const unsigned*>(colour);
-    a.nx = nx; a.ny = ny; a.nz = nz; a.voxels = voxels;
-    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.voxel = voxel_size; a.min_weight = min_weight;
-    a.records = records; a.capacity = records ? capacity_records : 0;
-    a.cursor = reinterpret_cast<unsigned long long*>(cursor);
-    hipLaunchKernelGGL(tsdf_extract_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
 namespace {
 
-// the checks the two mesh entries share; fills what both kernels read
-int mesh_args(MeshArgs& a, const float* tsdf, const float* weight, int nx, int ny, int nz, float min_weight, const void* vertex_base,
-              const void* out, long long capacity, int64_t* cursor) {
-    if (bad_volume(tsdf, weight, nx, ny, nz) || !cursor || ((uintptr_t)cursor & 7)) return MR_ERR_BAD_ARGUMENT;
-    if (voxel_count(nx, ny, nz) >= (1ll << 31)) return MR_ERR_BAD_ARGUMENT;                     // vertex indices are int32
-    if (min_weight != min_weight || (out && capacity < 0)) return MR_ERR_BAD_ARGUMENT;
-    if ((((uintptr_t)vertex_base | (uintptr_t)out) & 3) || (out && !vertex_base)) return MR_ERR_BAD_ARGUMENT;
-    a.tsdf = tsdf; a.weight = weight; a.colour = nullptr;
+// What the three surface entries share: the checks of volume, output and cursor, the kernels' arguments and, in `tiles`, the grid.
+// The triangle entry has no colour and no positions (NO_ORIGIN, a voxel of 1).  True: a bad argument.
+bool surface_args(MeshArgs& a, unsigned& tiles, const float* tsdf, const float* weight, const uint8_t* colour, int nx, int ny, int nz,
+                  const float* origin, float voxel_size, float min_weight, const void* out, long long capacity, int64_t* cursor) {
+    if (bad_volume(tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight)) return true;
+    if (!cursor || ((uintptr_t)cursor & 7) || ((uintptr_t)out & 3) || (out && capacity < 0)) return true;
+    if (nx > 0x7fffffff - CSX || ny > 0x7fffffff - CSY || nz > 0x7fffffff - CSZ) return true;   // x0 + sx of a staged block stays an int
+    a.tsdf = tsdf; a.weight = weight; a.colour = reinterpret_cast<const unsigned*>(colour);
     a.nx = nx; a.ny = ny; a.nz = nz;
-    a.tiles_x = (nx + TX - 1) / TX; a.tiles_y = (ny + TY - 1) / TY;
-    a.ox = a.oy = a.oz = 0.0f; a.voxel = 1.0f; a.min_weight = min_weight;
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.voxel = voxel_size; a.min_weight = min_weight;
     a.vertices = nullptr; a.triangles = nullptr; a.vertex_base = nullptr;
     a.capacity = out ? capacity : 0;
     a.cursor = reinterpret_cast<unsigned long long*>(cursor);
-    return 0;
+    tiles = tile_grid(nx, ny, nz, a.tiles_x, a.tiles_y);
+    return tiles == 0;
 }
 
-unsigned mesh_tiles(const MeshArgs& a) { return (unsigned)((long long)a.tiles_x * a.tiles_y * ((a.nz + TZ - 1) / TZ)); }   // < 2^31 voxels
+// beyond those, of the two mesh entries (a checked volume): vertex indices are int32, and an output needs vertex_base
+bool bad_mesh(int nx, int ny, int nz, const void* vertex_base, const void* out) {
+    return voxel_count(nx, ny, nz) >= (1ll << 31) || ((uintptr_t)vertex_base & 3) || (out && !vertex_base);
+}
 
 }  // namespace
+
+extern "C" int mr_tsdf_extract_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                                   const float* origin, float voxel_size, float min_weight, float* records, int64_t capacity_records,
+                                   int64_t* cursor, void* stream) {
+    MeshArgs a;
+    unsigned tiles;
+    if (surface_args(a, tiles, tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight, records, capacity_records, cursor))
+        return MR_ERR_BAD_ARGUMENT;
+    a.vertices = records;
+    hipLaunchKernelGGL(tsdf_mesh_vertices_kernel<3>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
 
 extern "C" int mr_tsdf_mesh_vertices_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
                                          const float* origin, float voxel_size, float min_weight, float* vertices, int64_t capacity_vertices,
                                          int32_t* vertex_base, int64_t* cursor, void* stream) {
     MeshArgs a;
-    if (mesh_args(a, tsdf, weight, nx, ny, nz, min_weight, vertex_base, vertices, capacity_vertices, cursor)) return MR_ERR_BAD_ARGUMENT;
-    if (((uintptr_t)colour & 3) || !origin || !(voxel_size > 0.0f)) return MR_ERR_BAD_ARGUMENT;
-    a.colour = reinterpret_cast<const unsigned*>(colour);
-    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.voxel = voxel_size;
+    unsigned tiles;
+    if (surface_args(a, tiles, tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight, vertices, capacity_vertices, cursor) ||
+        bad_mesh(nx, ny, nz, vertex_base, vertices))
+        return MR_ERR_BAD_ARGUMENT;
     a.vertices = vertices; a.vertex_base = vertex_base;
-    hipLaunchKernelGGL(tsdf_mesh_vertices_kernel, dim3(mesh_tiles(a)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tsdf_mesh_vertices_kernel<7>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -662,9 +616,12 @@ extern "C" int mr_tsdf_mesh_triangles_f32(const float* tsdf, const float* weight
                                           const int32_t* vertex_base, int32_t* triangles, int64_t capacity_triangles, int64_t* cursor,
                                           void* stream) {
     MeshArgs a;
-    if (mesh_args(a, tsdf, weight, nx, ny, nz, min_weight, vertex_base, triangles, capacity_triangles, cursor)) return MR_ERR_BAD_ARGUMENT;
+    unsigned tiles;
+    if (surface_args(a, tiles, tsdf, weight, nullptr, nx, ny, nz, NO_ORIGIN, 1.0f, min_weight, triangles, capacity_triangles, cursor) ||
+        bad_mesh(nx, ny, nz, vertex_base, triangles))
+        return MR_ERR_BAD_ARGUMENT;
     a.triangles = triangles; a.vertex_base = const_cast<int*>(vertex_base);
-    hipLaunchKernelGGL(tsdf_mesh_triangles_kernel, dim3(mesh_tiles(a)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tsdf_mesh_triangles_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -696,9 +653,9 @@ struct SkipArgs {
 };
 
 __global__ __launch_bounds__(256) void tsdf_skip_grid_kernel(const SkipArgs a) {
-    const int tile = blockIdx.x, tid = threadIdx.x;
-    const int x = (tile % a.tiles_x) * TX + (tid & 7) * 4, y = ((tile / a.tiles_x) % a.tiles_y) * TY + ((tid >> 3) & 7);
-    const int z = (tile / (a.tiles_x * a.tiles_y)) * TZ + (tid >> 6);
+    const int tid = threadIdx.x;
+    const Tile b = tile_of_block<1, 1, 1>(a.tiles_x, a.tiles_y);
+    const int x = b.x * TX + (tid & 7) * 4, y = b.y * TY + ((tid >> 3) & 7), z = b.z * TZ + (tid >> 6);
     if (x >= a.nx || y >= a.ny || z >= a.nz) return;
     const int n = a.nx - x < 4 ? a.nx - x : 4;
     const long long idx = ((long long)z * a.ny + y) * a.nx + x;
@@ -908,17 +865,16 @@ float t_of(float t_min, float step, long long k) { return t_min + (float)k * ste
 
 extern "C" int mr_tsdf_skip_grid_u8(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float min_weight,
                                     uint8_t* bricks, void* stream) {
-    if (bad_volume(tsdf, weight, nx, ny, nz) || min_weight != min_weight || !bricks) return MR_ERR_BAD_ARGUMENT;
+    if (bad_volume(tsdf, weight, nullptr, nx, ny, nz, NO_ORIGIN, 1.0f, min_weight) || !bricks) return MR_ERR_BAD_ARGUMENT;
     SkipArgs a;
     a.tsdf = tsdf; a.weight = weight; a.nx = nx; a.ny = ny; a.nz = nz; a.min_weight = min_weight; a.bricks = bricks;
-    a.tiles_x = (nx + TX - 1) / TX; a.tiles_y = (ny + TY - 1) / TY;
-    const long long tiles = (long long)a.tiles_x * a.tiles_y * ((nz + TZ - 1) / TZ);
-    if (tiles > 0x7fffffffLL) return MR_ERR_BAD_ARGUMENT;
+    const unsigned tiles = tile_grid(nx, ny, nz, a.tiles_x, a.tiles_y);
+    if (!tiles) return MR_ERR_BAD_ARGUMENT;
     a.bricks_x = (nx + BRICK - 1) / BRICK; a.bricks_y = (ny + BRICK - 1) / BRICK;
     const long long count = (long long)a.bricks_x * a.bricks_y * ((nz + BRICK - 1) / BRICK);
     const hipError_t cleared = hipMemsetAsync(bricks, 0, (size_t)count, (hipStream_t)stream);
     if (cleared != hipSuccess) return (int)cleared;
-    hipLaunchKernelGGL(tsdf_skip_grid_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tsdf_skip_grid_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 
@@ -926,8 +882,7 @@ extern "C" int mr_tsdf_render_f32(const float* tsdf, const float* weight, const 
                                   const float* origin, float voxel_size, float min_weight, const uint8_t* bricks,
                                   const mr_tsdf_ray_view* views, int32_t num_views, int32_t height, int32_t width, float t_min, float t_max,
                                   float step, void* stream) {
-    if (bad_volume(tsdf, weight, nx, ny, nz) || ((uintptr_t)colour & 3) || !origin || !views) return MR_ERR_BAD_ARGUMENT;
-    if (!(voxel_size > 0.0f) || min_weight != min_weight) return MR_ERR_BAD_ARGUMENT;
+    if (bad_volume(tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight) || !views) return MR_ERR_BAD_ARGUMENT;
     if (num_views < 1 || num_views > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return MR_ERR_BAD_ARGUMENT;
     if (!(step > 0.0f) || !(t_min >= 0.0f) || !(t_max >= t_min) || !isfinite(t_min) || !isfinite(t_max)) return MR_ERR_BAD_ARGUMENT;
     for (int i = 0; i < num_views; ++i) {

@@ -17,6 +17,7 @@ pointcloud_monorec_tmvo.json) with the data source on the device too:
 
     python -m monorec_amd.pointcloud --config configs/test/pointcloud_monorec_tmvo.json"""
 import ctypes
+import functools
 from array import array
 
 import numpy as np
@@ -25,9 +26,7 @@ import torch
 from . import _lib
 
 
-def _need_cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"monorec_amd.pointcloud: {what} must be a CUDA (HIP) tensor - there is no CPU fallback")
+_need_cuda = functools.partial(_lib.need_cuda, "pointcloud")
 
 
 def static_mask(cv_mask, mask_fill=32, threshold=0.1):

@@ -14,6 +14,7 @@ The encoders are the slow part (a 16-bit PNG costs tens of milliseconds, the mod
 ring on the caller's stream and returns; a pool of threads (Pillow's encoders release the GIL, like the decoders of
 input_pipeline.FrameCache's pool) waits for the slot's event and writes the files.  `add()` blocks only when every slot is taken."""
 import ctypes
+import functools
 import json
 import os
 import queue
@@ -112,9 +113,7 @@ def _inverse_pose(pose):
 
 
 # ------------------------------------------------------------------------------------------ the launch
-def _need_cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"monorec_amd.tsdf_export: {what} must be a CUDA (HIP) tensor - there is no CPU fallback")
+_need_cuda = functools.partial(_lib.need_cuda, "tsdf_export")
 
 
 def packed_sizes(batch, ch, cw):

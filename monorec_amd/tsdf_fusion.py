@@ -31,7 +31,9 @@ integrate launch on the same stream; nothing is copied to the host before the su
 
 Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; sparse or hashed volumes (the volume is dense, `max_bytes` bounds
 it; `save()` writes it as an .npz); a cap on the weight; fusing across ranks (`run` is single-process)."""
+import contextlib
 import ctypes
+import functools
 import math
 import os
 import re
@@ -48,9 +50,7 @@ TILE = _lib.MR_TSDF_TILE                      # (x, y, z) voxels of one workgrou
 BRICK = _lib.MR_TSDF_BRICK                    # edge of one brick of `TSDFVolume.skip_grid` in voxels
 
 
-def _need_cuda(t, what):
-    if not t.is_cuda:
-        raise RuntimeError(f"monorec_amd.tsdf_fusion: {what} must be a CUDA (HIP) tensor - there is no CPU fallback")
+_need_cuda = functools.partial(_lib.need_cuda, "tsdf_fusion")
 
 
 def _matrix(m, what):
@@ -59,6 +59,23 @@ def _matrix(m, what):
     if m.dim() != 2:
         raise ValueError(f"{what}: expected one matrix, got shape {tuple(m.shape)}")
     return m
+
+
+def _host_batches(cam_to_world, intrinsics):
+    """Poses (B, 4, 4), intrinsics (n, 3 x 3 / 4 x 4) from anywhere as fp32 on the host, and B; whether n is 1 or B the caller checks."""
+    poses = torch.as_tensor(cam_to_world).detach().to("cpu", torch.float32).reshape(-1, 4, 4)
+    ks = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32)
+    return poses, ks.reshape(-1, ks.shape[-2], ks.shape[-1]), poses.shape[0]
+
+
+def _set_intrinsics(view, k):
+    view.fx, view.fy, view.cx, view.cy = float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+
+
+def _write(file, writer, *arrays):
+    """writer(f, *arrays) into `file`: a binary file object, or a path."""
+    with (contextlib.nullcontext(file) if hasattr(file, "write") else open(file, "wb")) as f:
+        writer(f, *arrays)
 
 
 # ------------------------------------------------------------------------------------------ geometry on the host
@@ -185,11 +202,9 @@ class TSDFVolume:
             depth_cm = depth_cm.unsqueeze(0)
             colour = None if colour is None else colour.unsqueeze(0)
         b = depth_cm.shape[0]
-        poses = torch.as_tensor(cam_to_world).detach().to("cpu", torch.float32).reshape(-1, 4, 4)
-        ks = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32)
-        ks = ks.reshape(-1, ks.shape[-2], ks.shape[-1])
-        if poses.shape[0] != b or ks.shape[0] not in (1, b) or (colour is not None and colour.shape[0] != b):
-            raise ValueError(f"integrate: {b} depth maps, {poses.shape[0]} poses, {ks.shape[0]} intrinsics"
+        poses, ks, count = _host_batches(cam_to_world, intrinsics)
+        if count != b or ks.shape[0] not in (1, b) or (colour is not None and colour.shape[0] != b):
+            raise ValueError(f"integrate: {b} depth maps, {count} poses, {ks.shape[0]} intrinsics"
                              + ("" if colour is None else f", {colour.shape[0]} colour images"))
         self.integrate_views([(depth_cm[i], None if colour is None else colour[i], poses[i], ks[i if ks.shape[0] == b else 0])
                               for i in range(b)], max_depth_m)
@@ -221,11 +236,10 @@ class TSDFVolume:
                 colour = colour.contiguous()
             else:
                 colour = None
-            k = _matrix(k, "intrinsics")
             view = _lib.TsdfView()
+            _set_intrinsics(view, _matrix(k, "intrinsics"))
             m = torch.inverse(_matrix(pose, "cam_to_world").reshape(4, 4))          # world -> camera, fp32 on the host
             view.m[:] = [float(v) for v in m[:3, :4].reshape(-1)]
-            view.fx, view.fy, view.cx, view.cy = float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
             view.depth_cm = depth.data_ptr()
             view.colour = colour.data_ptr() if colour is not None else None
             frames.append(view)
@@ -246,40 +260,33 @@ class TSDFVolume:
         self.frames += prepared["count"]
 
     # -- surface
+    def _extract_launch(self, min_weight, records=None):
+        """One launch of the entry on the current stream - counting, or filling `records` - and the read of its cursor."""
+        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        out = (None, 0) if records is None else (records.data_ptr(), records.shape[0])
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mr_tsdf_extract_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), *out,
+                                                       cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
+        return int(cursor.item())
+
     def extract(self, min_weight=0):
         """(n, 6) fp32 on the device: x y z red green blue of every edge crossing between two voxels of weight > min_weight.  Two
         launches (count, fill) and one read of the count.  The order of the records is unspecified."""
-        lib = _lib.load()
-        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
-        common = (*self._volume_args(), self._origin, self.voxel_size, float(min_weight))
-        with torch.cuda.device(self.device):
-            _lib.check(lib.mr_tsdf_extract_f32(*common, None, 0, cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
-            count = int(cursor.item())
-            records = torch.empty(count, 6, dtype=torch.float32, device=self.device)
-            if count:
-                cursor.zero_()
-                _lib.check(lib.mr_tsdf_extract_f32(*common, records.data_ptr(), count, cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
-                if int(cursor.item()) != count:
-                    raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launch")
+        count = self.count(min_weight)
+        records = torch.empty(count, 6, dtype=torch.float32, device=self.device)
+        if count and self._extract_launch(min_weight, records) != count:
+            raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launch")
         return records
 
     def count(self, min_weight=0):
         """Number of records `extract(min_weight)` would return (the count launch alone)."""
-        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().mr_tsdf_extract_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), None, 0,
-                                                       cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
-        return int(cursor.item())
+        return self._extract_launch(min_weight)
 
     def save_ply(self, file, min_weight=0):
         """The surface points as a binary .ply (pointcloud.PLYSaver's header and records) to a path or a binary file object.  Returns
         the number of vertices."""
         records = self.extract(min_weight).cpu().numpy()
-        if hasattr(file, "write"):
-            write_ply(file, records.reshape(-1))
-        else:
-            with open(file, "wb") as f:
-                write_ply(f, records.reshape(-1))
+        _write(file, write_ply, records.reshape(-1))
         return records.shape[0]
 
     # -- the surface as a mesh
@@ -322,17 +329,12 @@ class TSDFVolume:
                 self._mesh_launches(min_weight, cursor, vertices, triangles, vertex_base)
             if cursor.tolist() != [n, m]:
                 raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launches")
-            del vertex_base
         return vertices, triangles
 
     def save_mesh_ply(self, file, min_weight=0):
         """The mesh as a binary .ply (`pointcloud.write_mesh_ply`) to a path or a binary file object.  Returns (vertices, triangles)."""
         vertices, triangles = (t.cpu().numpy() for t in self.mesh(min_weight))
-        if hasattr(file, "write"):
-            write_mesh_ply(file, vertices, triangles)
-        else:
-            with open(file, "wb") as f:
-                write_mesh_ply(f, vertices, triangles)
+        _write(file, write_mesh_ply, vertices, triangles)
         return vertices.shape[0], triangles.shape[0]
 
     # -- the volume seen from a camera
@@ -366,10 +368,8 @@ class TSDFVolume:
         dict(depth (B, h, w) fp32 metres, 0 where nothing was hit, normal (B, h, w, 3) fp32 unit vectors in world axes pointing out
         of the surface | None, colour (B, h, w, 3) uint8 | None) on the device.  `skip`: march with `skip_grid(min_weight)`, which
         changes no bit of the result."""
-        poses = torch.as_tensor(cam_to_world).detach().to("cpu", torch.float32).reshape(-1, 4, 4)
-        ks = torch.as_tensor(intrinsics).detach().to("cpu", torch.float32)
-        ks = ks.reshape(-1, ks.shape[-2], ks.shape[-1])
-        b, height, width = poses.shape[0], int(height), int(width)
+        poses, ks, b = _host_batches(cam_to_world, intrinsics)
+        height, width = int(height), int(width)
         if b < 1 or ks.shape[0] not in (1, b):
             raise ValueError(f"render: {b} poses, {ks.shape[0]} intrinsics (one, or one per pose)")
         if height < 1 or width < 1:
@@ -383,10 +383,9 @@ class TSDFVolume:
         image = torch.empty(b, height, width, 3, dtype=torch.uint8, device=self.device) if colour else None
         views = []
         for i in range(b):
-            k = ks[i if ks.shape[0] == b else 0]
             view = _lib.TsdfRayView()
             view.m[:] = [float(v) for v in poses[i][:3, :4].reshape(-1)]
-            view.fx, view.fy, view.cx, view.cy = float(k[0, 0]), float(k[1, 1]), float(k[0, 2]), float(k[1, 2])
+            _set_intrinsics(view, ks[i if ks.shape[0] == b else 0])
             view.depth = depth[i].data_ptr()
             view.normal = normal[i].data_ptr() if normals else None
             view.colour = image[i].data_ptr() if colour else None

@@ -10,7 +10,8 @@ import pytest
 import torch
 
 import tsdf_fusion_ref as ref
-from monorec_amd import synth, tsdf_export as tx, tsdf_fusion as tf
+import tsdf_mesh_ref as mref
+from monorec_amd import _lib, synth, tsdf_export as tx, tsdf_fusion as tf
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -258,6 +259,90 @@ def test_extract_equals_the_restatement(hip_lib, name, colour, tmp_path):
     assert torch.equal(again.extract().sort(0).values, volume.extract().sort(0).values)
     volume.reset()
     assert volume.count() == 0 and bool((volume.tsdf == 1).all()) and not bool(volume.weight.any())
+
+
+# -- the tiled sweep of the extraction: volumes loaded directly (tsdf_fusion_ref.seam_volume), no integration
+@functools.lru_cache(maxsize=None)
+def _seams(dims, colour):
+    """The seam volume and, per min_weight, its sorted records.  Shared, never modified."""
+    vol = ref.seam_volume(dims, colour)
+    return vol, {mw: ref.sort_records(ref.extract(vol, mw)) for mw in (0, 2)}
+
+
+def _load(vol):
+    """A device volume holding the arrays of a restatement's volume dict."""
+    volume = tf.TSDFVolume(origin=vol["origin"], dims=vol["dims"], voxel_size=float(vol["voxel"]), trunc=float(vol["trunc"]),
+                           colour=vol["colour"] is not None, device=DEV)
+    volume.tsdf.copy_(torch.from_numpy(vol["tsdf"].reshape(-1)))
+    volume.weight.copy_(torch.from_numpy(vol["weight"].reshape(-1)))
+    if vol["colour"] is not None:
+        volume.colour.copy_(torch.from_numpy(vol["colour"].reshape(-1, 4)))
+    return volume
+
+
+def _assert_every_seam_is_crossed(vol, min_weight):
+    """On the restatement alone: crossings along x, y and z; on the edges 31|32, 7|8, 3|4 between the first tile and the next; and
+    between the last-but-one and the last voxel of every axis.  An owner at index i owns the edge i | i + 1."""
+    nx, ny, nz = vol["dims"]
+    own_x, own_y, own_z = ref.crossing_owners(vol, min_weight)
+    assert own_x.any() and own_y.any() and own_z.any()
+    assert own_x[:, :, 31].any() and own_y[:, 7, :].any() and own_z[3].any()
+    assert own_x[:, :, nx - 2].any() and own_y[:, ny - 2, :].any() and own_z[nz - 2].any()
+    assert not vol["weight"].all() and (vol["weight"] == 1).any()             # unseen voxels, and voxels min_weight = 2 drops
+
+
+@pytest.mark.parametrize("colour", [True, False], ids=["colour", "plain"])
+@pytest.mark.parametrize("dims", ref.SEAM_DIMS, ids=lambda d: "x".join(map(str, d)))
+def test_extract_across_tile_seams_and_ragged_ends(hip_lib, dims, colour):
+    """33 x 9 x 5, 34 x 10 x 6, 65 x 17 x 9: one and two voxels beyond whole 32 x 8 x 4 tiles, so a tile's last voxel and its
+    neighbour, the owner of an edge and the edge's far end, fall into different workgroups, and the last tiles are ragged."""
+    vol, wants = _seams(dims, colour)
+    volume = _load(vol)
+    for min_weight in (0, 2):
+        _assert_every_seam_is_crossed(vol, min_weight)
+        expected = wants[min_weight]
+        records = volume.extract(min_weight)
+        assert volume.count(min_weight) == records.shape[0] == len(expected)
+        assert np.array_equal(ref.sort_records(records.cpu().numpy()), expected)
+        assert (expected[:, 3:].max() > 100) if colour else (not expected[:, 3:].any())
+    assert len(wants[2]) < len(wants[0])
+
+
+@pytest.mark.parametrize("dims,axis", [((40, 1, 9), 0), ((1, 9, 9), 1), ((9, 9, 1), 0)])
+def test_extract_of_a_volume_one_voxel_thick(hip_lib, dims, axis):
+    vol = ref.slab(dims, axis)
+    expected = ref.sort_records(ref.extract(vol))
+    assert len(expected) >= 9
+    assert np.array_equal(ref.sort_records(_load(vol).extract().cpu().numpy()), expected)
+
+
+def test_extract_with_a_capacity_below_the_count_writes_nothing_beyond_it(hip_lib):
+    vol, wants = _seams((65, 17, 9), True)
+    n = len(wants[0])
+    volume = _load(vol)
+    capacity = n // 3
+    records = torch.full((n, 6), -7.0, dtype=torch.float32, device=DEV)
+    cursor = torch.zeros(1, dtype=torch.int64, device=DEV)
+    _lib.check(_lib.load().mr_tsdf_extract_f32(*volume._volume_args(), volume._origin, volume.voxel_size, 0.0, records.data_ptr(), capacity,
+                                               cursor.data_ptr(), torch.cuda.current_stream().cuda_stream), "extract")
+    assert int(cursor.item()) == n and capacity > 50
+    assert bool((records[capacity:] == -7).all()) and not bool((records[:capacity, :3] == -7).any())
+    known = {r.tobytes() for r in wants[0]}
+    assert all(r.tobytes() in known for r in records[:capacity].cpu().numpy())
+
+
+def test_extract_equals_the_mesh_vertices_on_the_axis_edges(hip_lib):
+    """The header's promise on a seam volume: the points are the mesh's vertices on the edges e < 3, bit for bit."""
+    vol, wants = _seams((65, 17, 9), True)
+    volume = _load(vol)
+    for min_weight in (0, 2):
+        want = mref.mesh(vol, min_weight)
+        diagonal = want["vertices"][want["keys"][:, 3] >= 3]
+        assert np.array_equal(ref.sort_records(mref.axis_vertices(want)), wants[min_weight]) and len(diagonal) > 100
+        points = volume.extract(min_weight).cpu().numpy()
+        vertices = volume.mesh(min_weight)[0].cpu().numpy()
+        assert np.array_equal(ref.sort_records(points), wants[min_weight])
+        assert np.array_equal(ref.sort_records(np.concatenate([points, diagonal])), ref.sort_records(vertices))
 
 
 # ------------------------------------------------------------------------------------------ 5. a directory of the export

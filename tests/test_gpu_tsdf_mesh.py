@@ -114,16 +114,7 @@ def test_fused_volumes_equal_the_restatement(hip_lib, name):
 
 
 # ------------------------------------------------------------------------------------------ 3. degenerate shapes
-def _slab(dims, axis, zero=False):
-    """All seen; negative on the low half of `axis` (or 0 everywhere)."""
-    vol = ref.new_volume(dims, (-0.3, 0.2, 1.0), 0.06, 0.18)
-    index = np.arange(dims[axis]).reshape([-1 if k == 2 - axis else 1 for k in range(3)])
-    vol["tsdf"] = np.broadcast_to(np.where(index < dims[axis] // 2, -0.25, 0.5), vol["tsdf"].shape).astype(np.float32)
-    if zero:
-        vol["tsdf"] = np.zeros_like(vol["tsdf"])
-    vol["weight"] = np.ones_like(vol["tsdf"])
-    vol["colour"][..., :3] = 90
-    return vol
+_slab = ref.slab                                   # shared with test_gpu_tsdf_fusion.py
 
 
 @pytest.mark.parametrize("dims,axis", [((40, 1, 9), 0), ((1, 9, 9), 1), ((9, 9, 1), 0)])

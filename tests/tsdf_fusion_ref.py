@@ -112,6 +112,59 @@ def sort_records(records):
     return records[np.lexsort(tuple(records[:, k] for k in range(5, -1, -1)))]
 
 
+# ------------------------------------------------------------------------------------------ volumes loaded directly
+def crossing_owners(vol, min_weight=0.0):
+    """[x, y, z] boolean (nz, ny, nx) arrays: voxel v owns a crossing along that axis (`extract`'s rule, on v and v + e_axis)."""
+    seen, neg = vol["weight"] > F(min_weight), vol["tsdf"] < 0
+    owners = []
+    for dim in (2, 1, 0):
+        lo, hi = [slice(None)] * 3, [slice(None)] * 3
+        lo[dim], hi[dim] = slice(0, -1), slice(1, None)
+        lo, hi = tuple(lo), tuple(hi)
+        own = np.zeros(seen.shape, bool)
+        own[lo] = seen[lo] & seen[hi] & (neg[lo] != neg[hi])
+        owners.append(own)
+    return owners
+
+
+def slab(dims, axis, zero=False):
+    """All seen; negative on the low half of `axis` (or 0 everywhere)."""
+    vol = new_volume(dims, (-0.3, 0.2, 1.0), 0.06, 0.18)
+    index = np.arange(dims[axis]).reshape([-1 if k == 2 - axis else 1 for k in range(3)])
+    vol["tsdf"] = np.broadcast_to(np.where(index < dims[axis] // 2, -0.25, 0.5), vol["tsdf"].shape).astype(F)
+    if zero:
+        vol["tsdf"] = np.zeros_like(vol["tsdf"])
+    vol["weight"] = np.ones_like(vol["tsdf"])
+    vol["colour"][..., :3] = 90
+    return vol
+
+
+def seam_volume(dims, colour=True, seed=0):
+    """A closed surface across every kind of seam of the 32 x 8 x 4 tiles of a volume a little larger than whole tiles: the union of a
+    ball in the low x third of the volume and of balls of 0.7 voxels round single voxels - the last of the first tile (31, 7, 3), the
+    first past it (32, 8, 4) and the volume's last - so that edges 31|32, 7|8, 3|4 and last-but-one|last along x, y, z are crossed.
+    tsdf = clip(distance / 3 voxels, -1, 1); weights 3, about one in ten 1, a few 0 (unseen), all 3 next to the small balls; random
+    colours."""
+    nx, ny, nz = dims
+    vol = new_volume(dims, (-0.3, 0.2, 1.0), 0.06, 0.18, colour=colour)
+    rng = np.random.default_rng(seed)
+    z, y, x = np.meshgrid(np.arange(nz, dtype=np.float64), np.arange(ny, dtype=np.float64), np.arange(nx, dtype=np.float64), indexing="ij")
+    marks = [(31, 7, 3), (32, 8, 4), (nx - 1, ny - 1, nz - 1)]
+    balls = [(0.3 * (nx - 1), (ny - 1) / 2 + 0.1, (nz - 1) / 2 - 0.2, 0.45 * min(dims) + 0.3)] + [m + (0.7,) for m in marks]
+    dist = np.min([np.sqrt((x - cx) ** 2 + (y - cy) ** 2 + (z - cz) ** 2) - r for cx, cy, cz, r in balls], axis=0)
+    vol["tsdf"] = np.clip(dist / 3.0, -1.0, 1.0).astype(F)
+    draw = rng.random((nz, ny, nx))
+    vol["weight"] = np.where(draw < 0.03, 0.0, np.where(draw < 0.13, 1.0, 3.0)).astype(F)
+    for mx, my, mz in marks:
+        vol["weight"][max(mz - 1, 0):mz + 2, max(my - 1, 0):my + 2, max(mx - 1, 0):mx + 2] = 3.0
+    if colour:
+        vol["colour"][..., :3] = rng.integers(0, 256, size=(nz, ny, nx, 3), dtype=np.uint8)
+    return vol
+
+
+SEAM_DIMS = [(33, 9, 5), (34, 10, 6), (65, 17, 9)]
+
+
 # ------------------------------------------------------------------------------------------ the scene
 WALL_Z = 3.0
 SPHERE = (0.1, -0.05, 2.95, 0.45)              # centre and radius; it pokes through the wall
