@@ -43,6 +43,7 @@ extern "C" {
 #define MR_TSDF_TILE_X 32     /* voxels of one workgroup of mr_tsdf_integrate_f32 - the unit of its frustum culling */
 #define MR_TSDF_TILE_Y 8
 #define MR_TSDF_TILE_Z 4
+#define MR_TSDF_BLOCK 8       /* edge, in voxels, of one block of the block-sparse volume (mr_tsdf_sparse_*_f32) */
 #ifndef MR_TSDF_BRICK         /* (a build with -DMR_TSDF_BRICK=8 exists for tools/bench_tsdf_render.py --brick 8 alone) */
 #define MR_TSDF_BRICK 4       /* edge, in voxels, of one brick of mr_tsdf_skip_grid_u8: 4 or 8, 4 by measurement */
 #endif
@@ -868,6 +869,70 @@ typedef struct mr_tsdf_ray_view {
 int mr_tsdf_render_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
                        const float* origin, float voxel_size, float min_weight, const uint8_t* bricks, const mr_tsdf_ray_view* views,
                        int32_t num_views, int32_t height, int32_t width, float t_min, float t_max, float step, void* stream);
+
+/* ---- A block-sparse TSDF volume (three entries added within ABI 24: the change only adds symbols; SparseTSDFVolume in
+ * monorec_amd/tsdf_fusion.py): storage only for the blocks of MR_TSDF_BLOCK^3 = 8 x 8 x 8 voxels near a surface.  No hashing.
+ *
+ * The volume has nbx x nby x nbz BLOCKS, so 8 nbx x 8 nby x 8 nbz voxels; voxel (x, y, z) lies at p_a = origin_a + (float)i_a * voxel_size,
+ * exactly as in the dense volume.
+ *   table          int32[nbz * nby * nbx] in device memory, x fastest: -1 = the block has no storage, anything else is its slot.
+ *                  nbx * nby * nbz < 2^31.
+ *   pool           tsdf float[capacity * 512], weight float[capacity * 512], colour uint8[capacity * 512 * 4] or NULL.  Voxel
+ *                  (lx, ly, lz) of slot s is at s * 512 + (lz * 8 + ly) * 8 + lx, a 64-bit index: every row of 8 voxels starts on a
+ *                  32-byte boundary of a 16-byte aligned array, all accesses of the sweeps are 16 bytes wide, no ragged path exists.
+ *   block_of_slot  int32[capacity]: the table index of each slot in use.
+ *   cursor         one int64 in device memory, 0 on reset: the number of slot requests so far.  Slots 0 .. min(cursor, capacity) - 1
+ *                  are in use; cursor > capacity: some block found no room (and still has none).
+ * Reset: the table to -1 (a memset of 0xff), the cursor to 0.  The pool needs no clearing: a block is written in full when it gets a slot.
+ *
+ * mr_tsdf_sparse_integrate_f32: frames[0 .. num_frames) (HOST array, 1 <= num_frames <= MR_TSDF_MAX_FRAMES) as for mr_tsdf_integrate_f32.
+ * For every block, within the one launch:
+ *   1. start state: the pool's values if the block has a slot, otherwise tsdf 1, weight 0, colour 0 for every voxel;
+ *   2. the frames in order into each of the 512 voxels, mr_tsdf_integrate_f32's arithmetic operation for operation (the same code),
+ *      with the same skips, roundings and colour blend; a voxel is IN BAND when some frame updated it with diff / trunc < 1;
+ *   3. the block has a slot: the touched voxels are stored, as by the dense kernel;
+ *   4. no slot and no voxel in band: nothing is stored;
+ *   5. no slot and some voxel in band: s = one fetch-add of 1 on *cursor; if s < capacity, table[b] = s, block_of_slot[s] = b and all 512
+ *      voxels are stored (untouched ones as 1 / 0 / 0); otherwise nothing is stored.
+ * So: WHICH slot a block gets is unspecified (the order of the workgroups); everything else is deterministic.  From the launch that
+ * gives a block its slot on, the block's voxels equal those of a dense volume that was empty at the start of that launch and received
+ * the same frames since: free-space observations (dist = 1) of EARLIER LAUNCHES are lost for that block, those of earlier frames of
+ * the SAME launch are kept.  A block that never comes within trunc of an observed surface is never stored: it reads as unseen.
+ * A workgroup owns one block.  It culls frames with the dense kernel's five planes against the block's bounding sphere and leaves
+ * without touching memory, the table included, when no frame is live; the band decision is one workgroup-wide OR, the allocation one
+ * atomic per new block.  The launch covers only the block-aligned box of the frames' frusta up to depth
+ * min(max_depth_m, 327.67) + trunc (depths are int16 centimetres), computed here in double, pushed outwards like the planes and clipped
+ * to the table: no voxel outside it could have been updated, so neither the box nor the culling changes a result, and a table of
+ * millions of blocks costs nothing where no camera looks (no launch at all when the box misses the table).
+ * MR_ERR_BAD_ARGUMENT, nothing is launched: every case of mr_tsdf_integrate_f32; table, block_of_slot or cursor NULL; capacity < 1 or
+ * capacity * 512 >= 2^40; a block count < 1 or nbx * nby * nbz >= 2^31; tsdf / weight / colour off a 16-byte, cursor off an 8-byte,
+ * table / block_of_slot off a 4-byte boundary. */
+int mr_tsdf_sparse_integrate_f32(int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, float* tsdf, float* weight, uint8_t* colour,
+                                 int32_t* block_of_slot, int64_t capacity, int64_t* cursor, const float* origin, float voxel_size,
+                                 float trunc, float max_depth_m, const mr_tsdf_view* frames, int32_t num_frames, int32_t height,
+                                 int32_t width, void* stream);
+
+/* mr_tsdf_extract_f32's rule on the virtual dense volume of 8 nbx x 8 nby x 8 nbz voxels in which a block without a slot is unseen
+ * (weight 0): as a set, the records equal those of mr_tsdf_extract_f32 on the gathered dense volume bit for bit.  num_slots: the slots
+ * in use, min(cursor, capacity) of the integration, read by the caller; 0 launches nothing.  Cursor protocol (THIS cursor counts
+ * records), record format and the count-only mode with records NULL are mr_tsdf_extract_f32's.  One workgroup per slot: it stages its
+ * 8^3 voxels plus one beyond the high faces (9^3) from up to eight blocks through the table and leaves at the barrier when no seen
+ * negative voxel is staged.  A table entry at or above num_slots reads as no slot.
+ * MR_ERR_BAD_ARGUMENT: the table, pool and alignment cases above, origin NULL, voxel_size <= 0, NaN min_weight, num_slots < 0,
+ * num_slots * 512 >= 2^40 or num_slots > nbx * nby * nbz, records off a 4-byte boundary, capacity_records < 0 with records. */
+int mr_tsdf_sparse_extract_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf, const float* weight,
+                               const uint8_t* colour, const int32_t* block_of_slot, int64_t num_slots, const float* origin,
+                               float voxel_size, float min_weight, float* records, int64_t capacity_records, int64_t* cursor,
+                               void* stream);
+
+/* The box of dx x dy x dz voxels that starts at voxel (x0, y0, z0) of the sparse volume into dense arrays of the dense layout
+ * (idx = (z * dy + y) * dx + x; out_colour 4 bytes per voxel, may be NULL): the pool's values, 1 / 0 / 0 where a block has no slot.
+ * The box need not be block-aligned but must lie inside the volume.  MR_ERR_BAD_ARGUMENT: the table and pool cases above, out_tsdf or
+ * out_weight NULL, out_colour without a pool colour, outputs off a 4-byte boundary, a negative offset, a size < 1, a box that leaves
+ * the volume, dx * dy * dz >= 2^40. */
+int mr_tsdf_sparse_gather_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf, const float* weight,
+                              const uint8_t* colour, int32_t x0, int32_t y0, int32_t z0, int32_t dx, int32_t dy, int32_t dz,
+                              float* out_tsdf, float* out_weight, uint8_t* out_colour, void* stream);
 
 /* ---- input pipeline: KittiOdometryDataset.preprocess_image, kitti_odometry_dataset.py:120-134 ------
  *

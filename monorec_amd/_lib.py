@@ -106,6 +106,7 @@ class TsdfView(ctypes.Structure):
                 ("depth_cm", ctypes.c_void_p), ("colour", ctypes.c_void_p)]
 
 
+MR_TSDF_BLOCK = 8              # edge of one block of the block-sparse volume (mr_tsdf_sparse_*_f32) in voxels
 MR_TSDF_BRICK = 4              # edge of one brick of mr_tsdf_skip_grid_u8 in voxels
 
 
@@ -296,6 +297,16 @@ ABI = {
     "mr_tsdf_render_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                           _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.POINTER(TsdfRayView), ctypes.c_int32,
                                           ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
+    "mr_tsdf_sparse_integrate_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_float_p, ctypes.c_float,
+                                                    ctypes.c_float, ctypes.c_float, ctypes.POINTER(TsdfView), ctypes.c_int32, ctypes.c_int32,
+                                                    ctypes.c_int32, ctypes.c_void_p]),
+    "mr_tsdf_sparse_extract_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_float_p, ctypes.c_float, ctypes.c_float,
+                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_sparse_gather_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mr_resample_ksize_bilinear": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "mr_resample_coeffs_bilinear": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_void_p]),

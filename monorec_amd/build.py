@@ -23,6 +23,7 @@ SOURCES = [
     ("pointcloud.hip", ["-ffp-contract=off"]),
     ("tsdf_export.hip", ["-ffp-contract=off"]),        # depth / colour packing of save_frame_for_tsdf: the reference's roundings, one by one
     ("tsdf_fusion.hip", ["-ffp-contract=off"]),        # TSDF integration / surface extraction: the roundings of include/monorec_hip.h, one by one
+    ("tsdf_sparse.hip", ["-ffp-contract=off"]),        # the block-sparse volume: the same roundings through csrc/tsdf_common.h
     ("preprocess.hip", ["-ffp-contract=off"]),
     ("eltwise.hip", []),
     ("select.hip", ["-ffp-contract=off"]),          # median scaling: exact masked selection; stage-scaled metric sums

@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "../../include/monorec_hip.h"
+#include "tsdf_common.h"                     // what the block-sparse volume (tsdf_sparse.hip) runs too: the voxel update, the edge masks, the planes
 
 namespace {
 
@@ -62,11 +63,6 @@ __global__ __launch_bounds__(256) void tsdf_reset_kernel(float* __restrict__ tsd
     }
 }
 
-__device__ __forceinline__ unsigned blend_byte(unsigned old, unsigned pix, float w_old, float w_new) {
-    const float c = fminf(255.0f, floorf(((float)old * w_old + (float)pix) / w_new + 0.5f));
-    return (unsigned)c;
-}
-
 // The workgroup's tile from blockIdx.  <TX, TY, TZ>: its first voxel; <1, 1, 1>: its index in tiles per axis, for the kernels that
 // multiply at each use (they did before the decode was shared, and keep their instruction order that way).
 struct Tile { int x, y, z; };
@@ -83,17 +79,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
     const float ccx = a.ox + ((float)(b.x * TX) + 0.5f * (TX - 1)) * a.voxel;
     const float ccy = a.oy + ((float)(b.y * TY) + 0.5f * (TY - 1)) * a.voxel;
     const float ccz = a.oz + ((float)(b.z * TZ) + 0.5f * (TZ - 1)) * a.voxel;
-    unsigned live = 0;
-    for (int fi = 0; fi < a.num_frames; ++fi) {
-        bool out = false;
-#pragma unroll
-        for (int p = 0; p < 5; ++p) {
-            const float* q = a.plane[fi][p];
-            const float dist = ((q[0] * ccx + q[1] * ccy) + q[2] * ccz) + q[3];
-            out = out || (dist < -a.cull_radius);                      // NaN: not culled
-        }
-        if (!out) live |= 1u << fi;
-    }
+    const unsigned live = live_frames(a.plane, a.num_frames, ccx, ccy, ccz, a.cull_radius);
     if (live == 0) return;
 
     const int tid = threadIdx.x;
@@ -134,6 +120,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
     const float py = a.oy + (float)y * a.voxel, pz = a.oz + (float)z * a.voxel;
     const float wf = (float)a.w, hf = (float)a.h;
     unsigned touched = 0;
+    bool band = false;                           // (the block-sparse volume's question; nobody asks here)
     for (int fi = 0; fi < a.num_frames; ++fi) {
         if (!(live & (1u << fi))) continue;
         const mr_tsdf_view& f = a.f[fi];
@@ -141,30 +128,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
         for (int j = 0; j < 4; ++j) {
             if (j >= n) continue;
             const float px = a.ox + (float)(x + j) * a.voxel;
-            const float c0 = ((f.m[0] * px + f.m[1] * py) + f.m[2] * pz) + f.m[3];
-            const float c1 = ((f.m[4] * px + f.m[5] * py) + f.m[6] * pz) + f.m[7];
-            const float c2 = ((f.m[8] * px + f.m[9] * py) + f.m[10] * pz) + f.m[11];
-            if (!(c2 > 0.0f)) continue;
-            const float uf = roundf(f.fx * (c0 / c2) + f.cx);
-            const float vf = roundf(f.fy * (c1 / c2) + f.cy);
-            if (!(uf >= 0.0f && uf < wf && vf >= 0.0f && vf < hf)) continue;
-            const long long pix = (long long)(int)vf * a.w + (int)uf;
-            const float d = (float)f.depth_cm[pix] / 100.0f;
-            if (d <= 0.0f || d > a.max_depth) continue;
-            const float diff = d - c2;
-            if (diff <= -a.trunc) continue;
-            const float dist = fminf(1.0f, diff / a.trunc);
-            const float w_old = wgt[j], w_new = w_old + 1.0f;
-            t[j] = (t[j] * w_old + dist) / w_new;
-            if (cp) {
-                const uint8_t* s = f.colour + pix * 3;
-                const unsigned r = blend_byte(col[j] & 0xffu, s[0], w_old, w_new);
-                const unsigned g = blend_byte((col[j] >> 8) & 0xffu, s[1], w_old, w_new);
-                const unsigned b = blend_byte((col[j] >> 16) & 0xffu, s[2], w_old, w_new);
-                col[j] = r | (g << 8) | (b << 16);
-            }
-            wgt[j] = w_new;
-            touched |= 1u << j;
+            tsdf_update_voxel(f, px, py, pz, a.w, wf, hf, a.trunc, a.max_depth, cp != nullptr, t[j], wgt[j], col[j], touched, 1u << j, band);
         }
     }
     if (!touched) return;
@@ -201,7 +165,6 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
 // leaves at the barrier that ends the staging (__syncthreads_or) and has touched neither its output, nor vertex_base, nor the cursor.
 constexpr int VSX = TX + 1, VSY = TY + 1, VSZ = TZ + 1, VSN = VSX * VSY * VSZ;           // staged block of the vertex kernel
 constexpr int CSX = TX + 2, CSY = TY + 2, CSZ = TZ + 2, CSN = CSX * CSY * CSZ;           // staged codes of the triangle kernel
-constexpr unsigned SEEN = 1u, NEG = 2u;
 
 struct MeshArgs {
     const float* tsdf;
@@ -216,48 +179,6 @@ struct MeshArgs {
     long long capacity;
     unsigned long long* cursor;
 };
-
-// exclusive prefix of `mine` over the workgroup and its total: shuffles within the wave, wave totals through LDS
-__device__ __forceinline__ int workgroup_prefix(int mine, int* wave_tot, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += up;
-    }
-    if (lane == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    int before = incl - mine;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const int v = wave_tot[w]; if (w < wave) before += v; total += v; }
-    return before;
-}
-
-// red green blue of a record, between the packed colours cv and cn of the edge's two voxels
-__device__ __forceinline__ void write_colour(float* o, unsigned cv, unsigned cn, float s) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float fv = (float)((cv >> (8 * c)) & 0xffu), fn = (float)((cn >> (8 * c)) & 0xffu);
-        o[3 + c] = floorf(fv + s * (fn - fv) + 0.5f);
-    }
-}
-
-// the active-edge mask, over the first EDGES of the seven, of the voxel at `at` of a block of codes with row stride sx and slice stride sxy
-template <int EDGES>
-__device__ __forceinline__ unsigned edge_mask(const uint8_t* code, int at, int sx, int sxy) {
-    const unsigned c = code[at];
-    if (!(c & SEEN)) return 0u;
-    const int far[7] = {1, sx, sxy, 1 + sx, 1 + sxy, sx + sxy, 1 + sx + sxy};
-    unsigned mask = 0;
-#pragma unroll
-    for (int e = 0; e < EDGES; ++e) {
-        const unsigned n = code[at + far[e]];
-        if ((n & SEEN) && ((n ^ c) & NEG)) mask |= 1u << e;
-    }
-    return mask;
-}
 
 // EDGES = 7: the vertices of the mesh, and vertex_base.  EDGES = 3: the axis edges alone, the points of mr_tsdf_extract_f32; nothing
 // of it indexes with int32, so it serves volumes past 2^31 voxels.
@@ -471,39 +392,6 @@ unsigned tile_grid(int nx, int ny, int nz, int& tiles_x, int& tiles_y) {
     return tiles > 0x7fffffffLL ? 0u : (unsigned)tiles;
 }
 
-// The near and four side planes of one view in world space, in double.  A voxel can pass the kernel's cam_2 > 0 and image-bounds
-// tests only if its camera-space point c = A p + t has c_2 > 0 and -0.5 <= fx c_0 / c_2 + cx < w - 0.5 (likewise v): the intersection
-// of five half spaces n_c . c >= 0 through the camera centre.  They are widened by `slack` pixels beyond the half pixel of roundf, and
-// the kernel culls a tile only when its sphere is `margin` further out than that (see mr_tsdf_integrate_f32): more than the fp32
-// evaluation of c, of u and v and of the plane test itself can move a point.  Anything doubtful (non-positive focal lengths, A far
-// from a rotation, non-finite numbers) leaves the plane at zero, which never culls.
-void view_planes(const mr_tsdf_view& f, int h, int w, float out[5][4]) {
-    for (int p = 0; p < 5; ++p) for (int k = 0; k < 4; ++k) out[p][k] = 0.0f;
-    if (!(f.fx > 0.0f) || !(f.fy > 0.0f)) return;
-    double rows[3];
-    for (int r = 0; r < 3; ++r) {
-        rows[r] = sqrt((double)f.m[4 * r] * f.m[4 * r] + (double)f.m[4 * r + 1] * f.m[4 * r + 1] + (double)f.m[4 * r + 2] * f.m[4 * r + 2]);
-        if (!(rows[r] > 0.5 && rows[r] < 2.0)) return;
-    }
-    const double slack_u = 1.0 + 1e-6 * (fabs((double)f.cx) + w + f.fx), slack_v = 1.0 + 1e-6 * (fabs((double)f.cy) + h + f.fy);
-    const double nc[5][3] = {
-        {0.0, 0.0, 1.0},                                                          // c_2 >= 0
-        {(double)f.fx, 0.0, (double)f.cx + 0.5 + slack_u},                        // u >= -0.5 - slack
-        {-(double)f.fx, 0.0, (double)w - 0.5 + slack_u - (double)f.cx},           // u <= w - 0.5 + slack
-        {0.0, (double)f.fy, (double)f.cy + 0.5 + slack_v},
-        {0.0, -(double)f.fy, (double)h - 0.5 + slack_v - (double)f.cy},
-    };
-    for (int p = 0; p < 5; ++p) {
-        double nw[3], d = 0.0;
-        for (int k = 0; k < 3; ++k) nw[k] = nc[p][0] * f.m[k] + nc[p][1] * f.m[4 + k] + nc[p][2] * f.m[8 + k];
-        for (int r = 0; r < 3; ++r) d += nc[p][r] * f.m[4 * r + 3];
-        const double len = sqrt(nw[0] * nw[0] + nw[1] * nw[1] + nw[2] * nw[2]);
-        const double lc = sqrt(nc[p][0] * nc[p][0] + nc[p][1] * nc[p][1] + nc[p][2] * nc[p][2]);
-        if (!(len > 0.25 * lc) || !isfinite(len) || !isfinite(d)) continue;      // (A within [0.5, 2] per row, yet nearly singular along n_c)
-        out[p][0] = (float)(nw[0] / len); out[p][1] = (float)(nw[1] / len); out[p][2] = (float)(nw[2] / len); out[p][3] = (float)(d / len);
-    }
-}
-
 }  // namespace
 
 extern "C" int mr_tsdf_volume_reset_f32(float* tsdf, float* weight, uint8_t* colour, int32_t nx, int32_t ny, int32_t nz, void* stream) {
@@ -533,11 +421,9 @@ extern "C" int mr_tsdf_integrate_f32(float* tsdf, float* weight, uint8_t* colour
     a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
     a.voxel = voxel_size; a.trunc = trunc; a.max_depth = max_depth_m;
     a.num_frames = num_frames; a.h = height; a.w = width;
-    // sphere round the voxel CENTRES of a full tile, plus what fp32 can move: the tile centre, a voxel's camera-space point and the plane
-    // test are each a handful of roundings of numbers no larger than `reach` (the far corner of the volume plus a camera's translation),
-    // so 64 ulp of it (4e-6) is several times their sum; a thousandth of a voxel covers volumes at the origin
+    // sphere round the voxel CENTRES of a full tile, plus what fp32 can move (frames_reach in tsdf_common.h)
     const double v = (double)voxel_size;
-    double reach = 0.0, corner = 0.0;
+    double corner = 0.0;
     const int dims[3] = {nx, ny, nz};
     for (int k = 0; k < 3; ++k) {
         const double far_k = fmax(fabs((double)origin[k]), fabs((double)origin[k] + (dims[k] + TX) * v));
@@ -547,15 +433,14 @@ extern "C" int mr_tsdf_integrate_f32(float* tsdf, float* weight, uint8_t* colour
     for (int i = 0; i < num_frames; ++i) {
         a.f[i] = frames[i];
         view_planes(frames[i], height, width, a.plane[i]);
-        const float* m = frames[i].m;
-        reach = fmax(reach, 2.0 * corner + sqrt((double)m[3] * m[3] + (double)m[7] * m[7] + (double)m[11] * m[11]));
     }
+    const double reach = frames_reach(corner, frames, num_frames);
     for (int i = num_frames; i < MR_TSDF_MAX_FRAMES; ++i) {
         a.f[i] = frames[0];
         for (int p = 0; p < 5; ++p) for (int k = 0; k < 4; ++k) a.plane[i][p][k] = 0.0f;
     }
     const double radius = 0.5 * v * sqrt((double)((TX - 1) * (TX - 1) + (TY - 1) * (TY - 1) + (TZ - 1) * (TZ - 1)));
-    const double cull = radius + 1e-3 * v + 64.0 * 5.97e-8 * reach;
+    const double cull = radius + 1e-3 * v + FP32_SLACK * reach;
     a.cull_radius = isfinite(cull) ? nextafterf((float)cull, INFINITY) : INFINITY;       // infinite: `dist < -inf` never holds
     hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();

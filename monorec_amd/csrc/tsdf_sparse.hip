@@ -1,0 +1,403 @@
+// A block-sparse TSDF volume (monorec_amd/tsdf_fusion.py, SparseTSDFVolume): storage only for the blocks of MR_TSDF_BLOCK^3 = 8^3 voxels
+// that some keyframe puts within the truncation band of a surface.  No hashing: a direct-indexed table of one int32 per block (-1: no
+// storage, else a slot) and a pool of slots of 512 voxels, handed out by one fetch-add on a cursor.  The arithmetic is the dense volume's
+// (tsdf_common.h; compiled with -ffp-contract=off), the rules are in include/monorec_hip.h, tests/tsdf_sparse_ref.py restates them in
+// numpy and the GPU tests compare bit for bit.
+//
+//   tsdf_sparse_integrate_kernel   a workgroup of 128 threads owns one block, a thread four voxels along x: the block's 2 KB of tsdf and
+//                                  of weight are 128 contiguous 16-byte accesses.  Frames are culled per block with the dense kernel's
+//                                  five planes; a block no frame reaches leaves before it has touched memory, the table included.  A
+//                                  block without a slot is computed in registers from the empty state; whether it gets one is a
+//                                  workgroup-wide OR of "some voxel in band" and then one atomic on the cursor.
+//   tsdf_sparse_extract_kernel     a workgroup of 256 threads per slot: its 8^3 voxels plus one beyond the high faces (9^3: tsdf, a code
+//                                  byte and the colour, 6.5 KB) staged from up to eight blocks through the table, then the dense vertex
+//                                  kernel's masks, prefix sum and records over the three axis edges
+//   tsdf_sparse_gather_kernel      a box of voxels into dense arrays, 1 / 0 / 0 where a block has no slot
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/monorec_hip.h"
+#include "tsdf_common.h"
+
+namespace {
+
+constexpr int B = MR_TSDF_BLOCK, BV = B * B * B;
+static_assert(B == 8, "128 threads of four voxels along x; rows of 32 bytes; >> 3 and & 7 below");
+constexpr int S = B + 1, SN = S * S * S;         // staged block of the extract kernel
+constexpr long long MAX_VOXELS = 1ll << 40;      // of the pool, and of a gathered box: idx * 4 bytes stays far from overflow
+
+struct Pool {
+    float* tsdf;
+    float* weight;
+    unsigned* colour;                            // r g b 0 per voxel or null
+};
+
+struct SparseIntegrateArgs {
+    int* table;
+    Pool pool;
+    int* block_of_slot;
+    unsigned long long* cursor;
+    long long capacity;
+    int nbx, nby;
+    int x0, y0, z0, cx, cy;                      // the launch's box of blocks: its first block and its extent along x and y
+    float ox, oy, oz, voxel, trunc, max_depth;
+    int num_frames, h, w;
+    float cull_radius;
+    mr_tsdf_view f[MR_TSDF_MAX_FRAMES];
+    float plane[MR_TSDF_MAX_FRAMES][5][4];
+};
+
+__global__ __launch_bounds__(128) void tsdf_sparse_integrate_kernel(const SparseIntegrateArgs a) {
+    __shared__ unsigned long long s_drawn;
+    const int box = blockIdx.x;
+    const int bx = a.x0 + box % a.cx, by = a.y0 + (box / a.cx) % a.cy, bz = a.z0 + box / (a.cx * a.cy);
+    const long long vx = (long long)bx * B, vy = (long long)by * B, vz = (long long)bz * B;         // (a block count may reach 2^31 - 1)
+    const float ccx = a.ox + ((float)vx + 0.5f * (B - 1)) * a.voxel;
+    const float ccy = a.oy + ((float)vy + 0.5f * (B - 1)) * a.voxel;
+    const float ccz = a.oz + ((float)vz + 0.5f * (B - 1)) * a.voxel;
+    const unsigned live = live_frames(a.plane, a.num_frames, ccx, ccy, ccz, a.cull_radius);
+    if (live == 0) return;
+
+    const int tid = threadIdx.x;
+    const int bi = (bz * a.nby + by) * a.nbx + bx;                           // below 2^31 (checked by the entry)
+    const int slot = a.table[bi];                                            // uniform over the workgroup
+    float t[4] = {1.0f, 1.0f, 1.0f, 1.0f}, wgt[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    unsigned col[4] = {0u, 0u, 0u, 0u};
+    if (slot >= 0) {
+        const long long at = (long long)slot * BV + tid * 4;
+        const float4 tv = *reinterpret_cast<const float4*>(a.pool.tsdf + at);
+        const float4 wv = *reinterpret_cast<const float4*>(a.pool.weight + at);
+        t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
+        wgt[0] = wv.x; wgt[1] = wv.y; wgt[2] = wv.z; wgt[3] = wv.w;
+        if (a.pool.colour) {
+            const uint4 cv = *reinterpret_cast<const uint4*>(a.pool.colour + at);
+            col[0] = cv.x; col[1] = cv.y; col[2] = cv.z; col[3] = cv.w;
+        }
+    }
+
+    const long long x = vx + (tid & 1) * 4, y = vy + ((tid >> 1) & 7), z = vz + (tid >> 4);
+    const float py = a.oy + (float)y * a.voxel, pz = a.oz + (float)z * a.voxel;
+    const float wf = (float)a.w, hf = (float)a.h;
+    unsigned touched = 0;
+    bool band = false;
+    for (int fi = 0; fi < a.num_frames; ++fi) {
+        if (!(live & (1u << fi))) continue;
+        const mr_tsdf_view& f = a.f[fi];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float px = a.ox + (float)(x + j) * a.voxel;
+            tsdf_update_voxel(f, px, py, pz, a.w, wf, hf, a.trunc, a.max_depth, a.pool.colour != nullptr, t[j], wgt[j], col[j], touched, 1u << j, band);
+        }
+    }
+
+    long long at;
+    if (slot >= 0) {
+        if (!touched) return;
+        at = (long long)slot * BV + tid * 4;
+    } else {
+        if (!__syncthreads_or((int)band)) return;                            // free space, or never seen: no storage
+        if (tid == 0) {
+            const unsigned long long drawn = atomicAdd(a.cursor, 1ull);      // one per new block
+            if (drawn < (unsigned long long)a.capacity) {
+                a.table[bi] = (int)drawn;
+                a.block_of_slot[drawn] = bi;
+            }
+            s_drawn = drawn;
+        }
+        __syncthreads();
+        if (s_drawn >= (unsigned long long)a.capacity) return;               // the pool is full: the cursor tells
+        at = (long long)s_drawn * BV + tid * 4;                              // the whole block, untouched voxels as 1 / 0 / 0
+    }
+    *reinterpret_cast<float4*>(a.pool.tsdf + at) = make_float4(t[0], t[1], t[2], t[3]);
+    *reinterpret_cast<float4*>(a.pool.weight + at) = make_float4(wgt[0], wgt[1], wgt[2], wgt[3]);
+    if (a.pool.colour) *reinterpret_cast<uint4*>(a.pool.colour + at) = make_uint4(col[0], col[1], col[2], col[3]);
+}
+
+struct SparseExtractArgs {
+    const int* table;
+    Pool pool;
+    const int* block_of_slot;
+    int nbx, nby, nbz;
+    long long blocks;                            // nbx * nby * nbz
+    long long num_slots;
+    float ox, oy, oz, voxel, min_weight;
+    float* records;                              // null: count only
+    long long capacity;
+    unsigned long long* cursor;
+};
+
+__global__ __launch_bounds__(256) void tsdf_sparse_extract_kernel(const SparseExtractArgs a) {
+    __shared__ float s_t[SN];
+    __shared__ unsigned s_col[SN];
+    __shared__ uint8_t s_code[SN];
+    __shared__ int s_slot[8];
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x;
+    const int bi = a.block_of_slot[blockIdx.x];
+    if (bi < 0 || bi >= a.blocks) return;                                    // (a slot the caller counts but no launch filled)
+    const int bx = bi % a.nbx, by = (bi / a.nbx) % a.nby, bz = bi / (a.nbx * a.nby);
+    if (tid < 8) {                                                           // the slots of this block and of its seven + neighbours
+        const int nx = bx + (tid & 1), ny = by + ((tid >> 1) & 1), nz = bz + (tid >> 2);
+        int s = -1;
+        if (nx < a.nbx && ny < a.nby && nz < a.nbz) s = tid == 0 ? (int)blockIdx.x : a.table[((long long)nz * a.nby + ny) * a.nbx + nx];
+        s_slot[tid] = s < a.num_slots ? s : -1;
+    }
+    __syncthreads();
+    int any_neg = 0;
+    for (int i = tid; i < SN; i += 256) {
+        const int sx = i % S, sy = (i / S) % S, sz = i / (S * S);
+        const int s = s_slot[(sx >> 3) | ((sy >> 3) << 1) | ((sz >> 3) << 2)];
+        float t = 1.0f;
+        unsigned c = 0u, rgb = 0u;
+        if (s >= 0) {
+            const long long p = (long long)s * BV + (((sz & 7) * B + (sy & 7)) * B + (sx & 7));
+            if (a.pool.weight[p] > a.min_weight) {
+                t = a.pool.tsdf[p];
+                c = t < 0.0f ? (SEEN | NEG) : SEEN;
+                if (a.pool.colour) rgb = a.pool.colour[p];
+            }
+        }
+        s_t[i] = t;
+        s_col[i] = rgb;
+        s_code[i] = (uint8_t)c;
+        any_neg |= (int)(c & NEG);
+    }
+    if (!__syncthreads_or(any_neg)) return;
+
+    const int lx = tid & 7, ly = (tid >> 3) & 7, lz = tid >> 6;              // the thread's two voxels: z = lz and lz + 4
+    unsigned masks = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) masks |= edge_mask<3>(s_code, ((lz + 4 * j) * S + ly) * S + lx, S, S * S) << (8 * j);
+    const int mine = __popc(masks);
+    int total;
+    const int before = workgroup_prefix(mine, wave_tot, total);
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);   // one per workgroup
+    if (!a.records) return;
+    __syncthreads();
+    if (!masks) return;
+    long long rec = (long long)s_base + before;
+    const float px = a.ox + (float)((long long)bx * B + lx) * a.voxel, py = a.oy + (float)((long long)by * B + ly) * a.voxel;
+    const int s_far[3] = {1, S, S * S};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const unsigned mask = (masks >> (8 * j)) & 0xffu;
+        if (!mask) continue;
+        const int at = ((lz + 4 * j) * S + ly) * S + lx;
+        const float p[3] = {px, py, a.oz + (float)((long long)bz * B + lz + 4 * j) * a.voxel};
+        const float tv = s_t[at];
+        const unsigned cv = s_col[at];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            if (!(mask & (1u << e))) continue;
+            if (rec < a.capacity) {
+                const float s = tv / (tv - s_t[at + s_far[e]]);
+                const float step = s * a.voxel;
+                float* r = a.records + rec * 6;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) r[k] = k == e ? p[k] + step : p[k];
+                write_colour(r, cv, s_col[at + s_far[e]], s);
+            }
+            ++rec;
+        }
+    }
+}
+
+struct SparseGatherArgs {
+    const int* table;
+    Pool pool;
+    int nbx, nby;
+    int x0, y0, z0, dx, dy;
+    long long voxels;                            // dx * dy * dz
+    float* tsdf;
+    float* weight;
+    unsigned* colour;                            // null: not asked for
+};
+
+__global__ __launch_bounds__(256) void tsdf_sparse_gather_kernel(const SparseGatherArgs a) {
+    const long long stride = (long long)gridDim.x * 256;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.voxels; i += stride) {
+        const long long row = i / a.dx;
+        const int x = a.x0 + (int)(i - row * a.dx), y = a.y0 + (int)(row % a.dy), z = a.z0 + (int)(row / a.dy);
+        const int s = a.table[((long long)(z >> 3) * a.nby + (y >> 3)) * a.nbx + (x >> 3)];
+        float t = 1.0f, w = 0.0f;
+        unsigned c = 0u;
+        if (s >= 0) {
+            const long long p = (long long)s * BV + (((z & 7) * B + (y & 7)) * B + (x & 7));
+            t = a.pool.tsdf[p];
+            w = a.pool.weight[p];
+            if (a.colour) c = a.pool.colour[p];
+        }
+        a.tsdf[i] = t;
+        a.weight[i] = w;
+        if (a.colour) a.colour[i] = c;
+    }
+}
+
+// The checks the entries share: the table and the pool.  True: a bad argument.  `blocks` returns nbx * nby * nbz.
+bool bad_sparse(const void* table, int nbx, int nby, int nbz, const void* tsdf, const void* weight, const void* colour, long long& blocks) {
+    if (!table || !tsdf || !weight || nbx < 1 || nby < 1 || nbz < 1) return true;
+    if (((uintptr_t)table & 3) || (((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)colour) & 15)) return true;
+    const long long xy = (long long)nbx * nby;                               // < 2^62
+    if (xy >= (1ll << 31)) return true;
+    blocks = xy * nbz;                                                       // < 2^62
+    return blocks >= (1ll << 31);
+}
+
+// The box of blocks one frame can update, in double: a voxel is updated only if its camera-space point c = A p + t has 0 < c_2, projects
+// within `slack` pixels of the image (view_planes) and has c_2 < d + trunc <= depth, so c lies in the pyramid between the camera centre
+// and the four image-corner rays at `depth`, and p in the box of the five points A^-1 (c - t).  `push`: what the fp32 evaluation can move
+// c by; it reaches p through A^-1.  False: anything doubtful (view_planes' cases, A nearly singular, non-finite numbers) - the whole table.
+bool frame_box(const mr_tsdf_view& f, int h, int w, double depth, double push, double lo[3], double hi[3]) {
+    if (!(f.fx > 0.0f) || !(f.fy > 0.0f)) return false;
+    double A[3][3], t[3];
+    for (int r = 0; r < 3; ++r) {
+        for (int k = 0; k < 3; ++k) A[r][k] = (double)f.m[4 * r + k];
+        t[r] = (double)f.m[4 * r + 3];
+        const double len = sqrt(A[r][0] * A[r][0] + A[r][1] * A[r][1] + A[r][2] * A[r][2]);
+        if (!(len > 0.5 && len < 2.0)) return false;
+    }
+    const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
+                       A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
+    if (!(fabs(det) > 0.05)) return false;
+    double inv[3][3], norm = 0.0;
+    for (int r = 0; r < 3; ++r)
+        for (int k = 0; k < 3; ++k) {
+            const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+            inv[k][r] = (A[r1][k1] * A[r2][k2] - A[r1][k2] * A[r2][k1]) / det;                   // the cofactor, transposed
+        }
+    for (int r = 0; r < 3; ++r) norm = fmax(norm, fabs(inv[r][0]) + fabs(inv[r][1]) + fabs(inv[r][2]));
+    const double slack_u = view_slack(f.cx, w, f.fx), slack_v = view_slack(f.cy, h, f.fy);
+    const double su[2] = {(-0.5 - slack_u - (double)f.cx) / f.fx, ((double)w - 0.5 + slack_u - (double)f.cx) / f.fx};
+    const double sv[2] = {(-0.5 - slack_v - (double)f.cy) / f.fy, ((double)h - 0.5 + slack_v - (double)f.cy) / f.fy};
+    for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+    for (int corner = 0; corner < 5; ++corner) {
+        const double c[3] = {corner < 4 ? su[corner & 1] * depth : 0.0, corner < 4 ? sv[corner >> 1] * depth : 0.0, corner < 4 ? depth : 0.0};
+        for (int k = 0; k < 3; ++k) {
+            const double p = inv[k][0] * (c[0] - t[0]) + inv[k][1] * (c[1] - t[1]) + inv[k][2] * (c[2] - t[2]);
+            if (!isfinite(p)) return false;
+            lo[k] = fmin(lo[k], p - push * norm);
+            hi[k] = fmax(hi[k], p + push * norm);
+        }
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int mr_tsdf_sparse_integrate_f32(int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, float* tsdf, float* weight, uint8_t* colour,
+                                            int32_t* block_of_slot, int64_t capacity, int64_t* cursor, const float* origin, float voxel_size,
+                                            float trunc, float max_depth_m, const mr_tsdf_view* frames, int32_t num_frames, int32_t height,
+                                            int32_t width, void* stream) {
+    long long blocks;
+    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !block_of_slot || !cursor || !origin || !frames) return MR_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)block_of_slot & 3) || ((uintptr_t)cursor & 7)) return MR_ERR_BAD_ARGUMENT;
+    if (capacity < 1 || capacity >= MAX_VOXELS / BV) return MR_ERR_BAD_ARGUMENT;
+    if (!(voxel_size > 0.0f) || !(trunc > 0.0f) || max_depth_m != max_depth_m) return MR_ERR_BAD_ARGUMENT;
+    if (num_frames < 1 || num_frames > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return MR_ERR_BAD_ARGUMENT;
+    if ((long long)height * width * 3 >= (1ll << 40)) return MR_ERR_BAD_ARGUMENT;
+    for (int i = 0; i < num_frames; ++i)
+        if (!frames[i].depth_cm || (colour && !frames[i].colour)) return MR_ERR_BAD_ARGUMENT;
+    SparseIntegrateArgs a;
+    a.table = table;
+    a.pool = {tsdf, weight, reinterpret_cast<unsigned*>(colour)};
+    a.block_of_slot = block_of_slot;
+    a.cursor = reinterpret_cast<unsigned long long*>(cursor);
+    a.capacity = capacity;
+    a.nbx = nbx; a.nby = nby;
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
+    a.voxel = voxel_size; a.trunc = trunc; a.max_depth = max_depth_m;
+    a.num_frames = num_frames; a.h = height; a.w = width;
+    // the dense entry's margins, for the sphere round the voxel centres of a block
+    const double v = (double)voxel_size;
+    const int nb[3] = {nbx, nby, nbz};
+    double corner = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        const double far_k = fmax(fabs((double)origin[k]), fabs((double)origin[k] + ((double)nb[k] * B + B) * v));
+        corner += far_k * far_k;
+    }
+    corner = sqrt(corner);
+    for (int i = 0; i < MR_TSDF_MAX_FRAMES; ++i) {
+        a.f[i] = frames[i < num_frames ? i : 0];
+        if (i < num_frames) view_planes(frames[i], height, width, a.plane[i]);
+        else for (int p = 0; p < 5; ++p) for (int k = 0; k < 4; ++k) a.plane[i][p][k] = 0.0f;
+    }
+    const double margin = 1e-3 * v + FP32_SLACK * frames_reach(corner, frames, num_frames);
+    const double cull = 0.5 * v * sqrt(3.0 * (B - 1) * (B - 1)) + margin;
+    a.cull_radius = isfinite(cull) ? nextafterf((float)cull, INFINITY) : INFINITY;       // infinite: `dist < -inf` never holds
+    // The launch's box of blocks: no frame can update a voxel outside it, so leaving the rest of the table out changes no result.  Depths
+    // come from int16 centimetres (at most 327.67 m) and count up to max_depth_m; a voxel trunc behind one is still updated.
+    const double depth = (fmax(0.0, fmin((double)max_depth_m, 327.67)) + (double)trunc) * (1.0 + 1e-6) + margin;
+    int first[3] = {nbx, nby, nbz}, last[3] = {-1, -1, -1};
+    for (int i = 0; i < num_frames; ++i) {
+        double lo[3], hi[3];
+        const bool known = isfinite(depth) && frame_box(frames[i], height, width, depth, margin, lo, hi);
+        bool empty = false;
+        int f_first[3], f_last[3];
+        for (int k = 0; k < 3; ++k) {
+            f_first[k] = 0; f_last[k] = nb[k] - 1;
+            if (!known) continue;
+            // voxel indices one further out than the box, then their blocks, clipped to the table while still double
+            const double b_lo = floor((floor((lo[k] - (double)origin[k]) / v) - 1.0) / B), b_hi = floor((ceil((hi[k] - (double)origin[k]) / v) + 1.0) / B);
+            if (!isfinite(b_lo) || !isfinite(b_hi)) continue;
+            if (b_hi < 0.0 || b_lo > (double)(nb[k] - 1)) { empty = true; break; }
+            f_first[k] = (int)fmax(b_lo, 0.0); f_last[k] = (int)fmin(b_hi, (double)(nb[k] - 1));
+        }
+        if (empty) continue;
+        for (int k = 0; k < 3; ++k) { first[k] = f_first[k] < first[k] ? f_first[k] : first[k]; last[k] = f_last[k] > last[k] ? f_last[k] : last[k]; }
+    }
+    if (last[0] < first[0]) return 0;                                                    // no frame looks at the table: nothing to do
+    a.x0 = first[0]; a.y0 = first[1]; a.z0 = first[2];
+    a.cx = last[0] - first[0] + 1; a.cy = last[1] - first[1] + 1;
+    const long long grid = (long long)a.cx * a.cy * (last[2] - first[2] + 1);           // at most the table: below 2^31
+    hipLaunchKernelGGL(tsdf_sparse_integrate_kernel, dim3((unsigned)grid), dim3(128), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_sparse_extract_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf, const float* weight,
+                                          const uint8_t* colour, const int32_t* block_of_slot, int64_t num_slots, const float* origin,
+                                          float voxel_size, float min_weight, float* records, int64_t capacity_records, int64_t* cursor,
+                                          void* stream) {
+    long long blocks;
+    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !block_of_slot || !cursor || !origin) return MR_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)block_of_slot & 3) || ((uintptr_t)cursor & 7) || ((uintptr_t)records & 3) || (records && capacity_records < 0)) return MR_ERR_BAD_ARGUMENT;
+    if (num_slots < 0 || num_slots >= MAX_VOXELS / BV || num_slots > blocks) return MR_ERR_BAD_ARGUMENT;
+    if (!(voxel_size > 0.0f) || min_weight != min_weight) return MR_ERR_BAD_ARGUMENT;
+    if (num_slots == 0) return 0;
+    SparseExtractArgs a;
+    a.table = table;
+    a.pool = {const_cast<float*>(tsdf), const_cast<float*>(weight), reinterpret_cast<unsigned*>(const_cast<uint8_t*>(colour))};
+    a.block_of_slot = block_of_slot;
+    a.nbx = nbx; a.nby = nby; a.nbz = nbz; a.blocks = blocks; a.num_slots = num_slots;
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.voxel = voxel_size; a.min_weight = min_weight;
+    a.records = records;
+    a.capacity = records ? capacity_records : 0;
+    a.cursor = reinterpret_cast<unsigned long long*>(cursor);
+    hipLaunchKernelGGL(tsdf_sparse_extract_kernel, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_sparse_gather_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf, const float* weight,
+                                         const uint8_t* colour, int32_t x0, int32_t y0, int32_t z0, int32_t dx, int32_t dy, int32_t dz,
+                                         float* out_tsdf, float* out_weight, uint8_t* out_colour, void* stream) {
+    long long blocks;
+    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !out_tsdf || !out_weight || (out_colour && !colour)) return MR_ERR_BAD_ARGUMENT;
+    if (((uintptr_t)out_tsdf | (uintptr_t)out_weight | (uintptr_t)out_colour) & 3) return MR_ERR_BAD_ARGUMENT;
+    if (x0 < 0 || y0 < 0 || z0 < 0 || dx < 1 || dy < 1 || dz < 1) return MR_ERR_BAD_ARGUMENT;
+    if ((long long)x0 + dx > (long long)nbx * B || (long long)y0 + dy > (long long)nby * B || (long long)z0 + dz > (long long)nbz * B) return MR_ERR_BAD_ARGUMENT;
+    const long long xy = (long long)dx * dy;
+    if (xy >= MAX_VOXELS || dz > MAX_VOXELS / xy || xy * dz >= MAX_VOXELS) return MR_ERR_BAD_ARGUMENT;
+    SparseGatherArgs a;
+    a.table = table;
+    a.pool = {const_cast<float*>(tsdf), const_cast<float*>(weight), reinterpret_cast<unsigned*>(const_cast<uint8_t*>(colour))};
+    a.nbx = nbx; a.nby = nby;
+    a.x0 = x0; a.y0 = y0; a.z0 = z0; a.dx = dx; a.dy = dy;
+    a.voxels = xy * dz;
+    a.tsdf = out_tsdf; a.weight = out_weight; a.colour = reinterpret_cast<unsigned*>(out_colour);
+    long long grid = (a.voxels + 255) / 256;
+    if (grid > 65536) grid = 65536;                                                      // grid-stride beyond that
+    hipLaunchKernelGGL(tsdf_sparse_gather_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}

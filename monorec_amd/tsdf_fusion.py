@@ -23,14 +23,20 @@ trilinear tsdf) and returns depth, the unit surface normal (the interpolant's gr
 `skip_grid()` (`mr_tsdf_skip_grid_u8`) is a byte per brick of 4^3 voxels that lets the march pass empty space with one load per sample
 and changes no bit of the result; header and tests/tsdf_render_ref.py as above.  There is no CPU fallback: CPU tensors raise.
 
+`SparseTSDFVolume` is the same volume for scenes whose dense grid does not fit (200 m x 200 m x 40 m of road at 0.1 m are 19 GB): a
+direct-indexed table of blocks of 8^3 voxels and a pool that holds only the blocks some keyframe put within the truncation band of a
+surface (`mr_tsdf_sparse_integrate_f32`, the dense kernel's arithmetic through csrc/tsdf_common.h).  It has the integrate methods and
+`extract` / `count` / `save_ply` (`mr_tsdf_sparse_extract_f32`) of `TSDFVolume`; `to_dense()` (`mr_tsdf_sparse_gather_f32`) hands any
+region that fits to the dense class for `mesh()`, `render()` and `score()`.  The runner key `sparse_volume` selects it.
+
 `run(config)` takes the configs of `pointcloud.run` / `tsdf_export.run` and drives the same pipelined loop
 (`tsdf_export.KeyframeStream`): per keyframe one pack launch into a staging slot on the device, per `fuse_batch` keyframes one
 integrate launch on the same stream; nothing is copied to the host before the surface is written.  With `fused_metrics` in the config,
 `Fusion.score()` renders the fused volume into every exported keyframe again and scores it against the dataset's targets; with
 `render_dir`, `write()` also writes those views as 16-bit centimetre PNGs and JPEGs.
 
-Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; sparse or hashed volumes (the volume is dense, `max_bytes` bounds
-it; `save()` writes it as an .npz); a cap on the weight; fusing across ranks (`run` is single-process)."""
+Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; a native mesh or ray-cast of the sparse volume
+(they go through `to_dense()`), growth of its pool, eviction or hashing; a cap on the weight; fusing across ranks (`run` is single-process)."""
 import contextlib
 import ctypes
 import functools
@@ -47,6 +53,7 @@ from .pointcloud import write_mesh_ply, write_ply
 
 MAX_FRAMES = _lib.MR_TSDF_MAX_FRAMES          # keyframes per integrate launch
 TILE = _lib.MR_TSDF_TILE                      # (x, y, z) voxels of one workgroup of the integrate kernel: the unit of its frustum culling
+BLOCK = _lib.MR_TSDF_BLOCK                    # edge of one block of `SparseTSDFVolume` in voxels
 BRICK = _lib.MR_TSDF_BRICK                    # edge of one brick of `TSDFVolume.skip_grid` in voxels
 
 
@@ -124,19 +131,18 @@ def volume_bytes(dims, colour=True):
 
 
 # ------------------------------------------------------------------------------------------ the volume
-class TSDFVolume:
-    """A dense TSDF volume on the device.  Give `bounds` = ((x0, y0, z0), (x1, y1, z1)) - e.g. from `bounds_from_frusta` - or `origin`
-    and `dims` = (nx, ny, nz); `voxel_size` in metres; `trunc` (default 5 voxels) the truncation distance.  A volume above `max_bytes`
-    raises a ValueError that names the voxel size that would fit.  `storage` = (tsdf, weight, colour | None): use these device tensors
-    (flat, of nx * ny * nz elements / x 4 bytes) instead of allocating - they are reset too."""
+class _Volume:
+    """What `TSDFVolume` and `SparseTSDFVolume` share: the geometry of the constructor, the host half of the integration (checks, pose
+    inverse, `mr_tsdf_view` arrays) and the count-then-fill protocol of the surface points.  A subclass has `_integrate_launch` (one
+    launch of its integrate entry) and `_extract_launch` (one launch of its extract entry and the read of the cursor)."""
 
-    def __init__(self, bounds=None, voxel_size=0.1, trunc=None, colour=True, device="cuda:0", max_bytes=8 << 30, origin=None, dims=None,
-                 storage=None):
+    def _geometry(self, bounds, voxel_size, trunc, origin, dims):
+        """Sets dims, origin, voxel_size and trunc as the entries will see them (fp32); returns voxel_size as given."""
         voxel_size = float(voxel_size)
         if not voxel_size > 0:
             raise ValueError(f"voxel_size {voxel_size}: must be positive")
         if (bounds is None) == (origin is None or dims is None):
-            raise ValueError("TSDFVolume: give either bounds or origin and dims")
+            raise ValueError(f"{type(self).__name__}: give either bounds or origin and dims")
         if bounds is not None:
             origin, dims = bounds[0], dims_of_bounds(bounds, voxel_size)
         self.dims = tuple(int(d) for d in dims)
@@ -147,49 +153,13 @@ class TSDFVolume:
         self.trunc = float(np.float32(5 * voxel_size if trunc is None else trunc))
         if not self.trunc > 0:
             raise ValueError(f"trunc {trunc}: must be positive")
-        self.has_colour = bool(colour)
-        need = volume_bytes(self.dims, self.has_colour)
-        if need > int(max_bytes):
-            extent = [(d - 1) * voxel_size for d in self.dims]
-            box, fits = ((0.0, 0.0, 0.0), tuple(extent)), voxel_size
-            while volume_bytes(dims_of_bounds(box, float(f"{fits:.3g}")), self.has_colour) > int(max_bytes):
-                fits *= 1.01
-            raise ValueError(f"TSDFVolume: {self.dims[0]} x {self.dims[1]} x {self.dims[2]} voxels of {voxel_size:g} m need {need / 2 ** 30:.2f} GiB, "
-                             f"more than max_bytes = {int(max_bytes) / 2 ** 30:.2f} GiB; a voxel size of {float(f'{fits:.3g}'):g} m would fit")
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("monorec_amd.tsdf_fusion: the volume lives on a CUDA (HIP) device - there is no CPU fallback")
-        n = self.dims[0] * self.dims[1] * self.dims[2]
-        if storage is None:
-            self.tsdf = torch.empty(n, dtype=torch.float32, device=self.device)
-            self.weight = torch.empty(n, dtype=torch.float32, device=self.device)
-            self.colour = torch.empty(n, 4, dtype=torch.uint8, device=self.device) if self.has_colour else None
-        else:
-            self.tsdf, self.weight, self.colour = storage
-            for t, what in ((self.tsdf, "tsdf"), (self.weight, "weight")) + (((self.colour, "colour"),) if self.has_colour else ()):
-                _need_cuda(t, what)
-                if not t.is_contiguous() or t.numel() != (n * 4 if what == "colour" else n) or \
-                        t.dtype != (torch.uint8 if what == "colour" else torch.float32):
-                    raise ValueError(f"storage: {what} must be a contiguous tensor of the volume's size and type")
-            if not self.has_colour:
-                self.colour = None
-        self._origin = (ctypes.c_float * 3)(*self.origin)
-        self._keep = None
-        self._skip = {}                                        # min_weight -> skip_grid(min_weight), dropped by whatever writes the volume
-        self.frames = 0                                        # keyframes integrated so far
-        self.reset()
+        return voxel_size
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
-    def _volume_args(self):
-        return (self.tsdf.data_ptr(), self.weight.data_ptr(), self.colour.data_ptr() if self.colour is not None else None, *self.dims)
-
-    def reset(self):
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().mr_tsdf_volume_reset_f32(*self._volume_args(), self._stream()), "mr_tsdf_volume_reset_f32")
-        self.frames = 0
-        self.drop_skip_grids()
+    def drop_skip_grids(self):
+        pass
 
     # -- integrate
     def integrate(self, depth_cm, colour, cam_to_world, intrinsics, max_depth_m=None):
@@ -253,22 +223,12 @@ class TSDFVolume:
         limit = float("inf") if max_depth_m is None else float(max_depth_m)
         with torch.cuda.device(self.device):
             for array in prepared["arrays"]:
-                _lib.check(lib.mr_tsdf_integrate_f32(*self._volume_args(), self._origin, self.voxel_size, self.trunc, limit, array, len(array),
-                                                     prepared["size"][0], prepared["size"][1], self._stream()), "mr_tsdf_integrate_f32")
+                self._integrate_launch(lib, array, limit, prepared["size"])
         self._keep = prepared["keep"]                          # alive until the launches have run (same stream: the next call may drop them)
         self.drop_skip_grids()
         self.frames += prepared["count"]
 
-    # -- surface
-    def _extract_launch(self, min_weight, records=None):
-        """One launch of the entry on the current stream - counting, or filling `records` - and the read of its cursor."""
-        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
-        out = (None, 0) if records is None else (records.data_ptr(), records.shape[0])
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().mr_tsdf_extract_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), *out,
-                                                       cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
-        return int(cursor.item())
-
+    # -- surface points
     def extract(self, min_weight=0):
         """(n, 6) fp32 on the device: x y z red green blue of every edge crossing between two voxels of weight > min_weight.  Two
         launches (count, fill) and one read of the count.  The order of the records is unspecified."""
@@ -288,6 +248,71 @@ class TSDFVolume:
         records = self.extract(min_weight).cpu().numpy()
         _write(file, write_ply, records.reshape(-1))
         return records.shape[0]
+
+
+class TSDFVolume(_Volume):
+    """A dense TSDF volume on the device.  Give `bounds` = ((x0, y0, z0), (x1, y1, z1)) - e.g. from `bounds_from_frusta` - or `origin`
+    and `dims` = (nx, ny, nz); `voxel_size` in metres; `trunc` (default 5 voxels) the truncation distance.  A volume above `max_bytes`
+    raises a ValueError that names the voxel size that would fit.  `storage` = (tsdf, weight, colour | None): use these device tensors
+    (flat, of nx * ny * nz elements / x 4 bytes) instead of allocating - they are reset too."""
+
+    def __init__(self, bounds=None, voxel_size=0.1, trunc=None, colour=True, device="cuda:0", max_bytes=8 << 30, origin=None, dims=None,
+                 storage=None):
+        voxel_size = self._geometry(bounds, voxel_size, trunc, origin, dims)
+        self.has_colour = bool(colour)
+        need = volume_bytes(self.dims, self.has_colour)
+        if need > int(max_bytes):
+            extent = [(d - 1) * voxel_size for d in self.dims]
+            box, fits = ((0.0, 0.0, 0.0), tuple(extent)), voxel_size
+            while volume_bytes(dims_of_bounds(box, float(f"{fits:.3g}")), self.has_colour) > int(max_bytes):
+                fits *= 1.01
+            raise ValueError(f"TSDFVolume: {self.dims[0]} x {self.dims[1]} x {self.dims[2]} voxels of {voxel_size:g} m need {need / 2 ** 30:.2f} GiB, "
+                             f"more than max_bytes = {int(max_bytes) / 2 ** 30:.2f} GiB; a voxel size of {float(f'{fits:.3g}'):g} m would fit")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("monorec_amd.tsdf_fusion: the volume lives on a CUDA (HIP) device - there is no CPU fallback")
+        n = self.dims[0] * self.dims[1] * self.dims[2]
+        if storage is None:
+            self.tsdf = torch.empty(n, dtype=torch.float32, device=self.device)
+            self.weight = torch.empty(n, dtype=torch.float32, device=self.device)
+            self.colour = torch.empty(n, 4, dtype=torch.uint8, device=self.device) if self.has_colour else None
+        else:
+            self.tsdf, self.weight, self.colour = storage
+            for t, what in ((self.tsdf, "tsdf"), (self.weight, "weight")) + (((self.colour, "colour"),) if self.has_colour else ()):
+                _need_cuda(t, what)
+                if not t.is_contiguous() or t.numel() != (n * 4 if what == "colour" else n) or \
+                        t.dtype != (torch.uint8 if what == "colour" else torch.float32):
+                    raise ValueError(f"storage: {what} must be a contiguous tensor of the volume's size and type")
+            if not self.has_colour:
+                self.colour = None
+        self._origin = (ctypes.c_float * 3)(*self.origin)
+        self._keep = None
+        self._skip = {}                                        # min_weight -> skip_grid(min_weight), dropped by whatever writes the volume
+        self.frames = 0                                        # keyframes integrated so far
+        self.reset()
+
+    def _volume_args(self):
+        return (self.tsdf.data_ptr(), self.weight.data_ptr(), self.colour.data_ptr() if self.colour is not None else None, *self.dims)
+
+    def reset(self):
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mr_tsdf_volume_reset_f32(*self._volume_args(), self._stream()), "mr_tsdf_volume_reset_f32")
+        self.frames = 0
+        self.drop_skip_grids()
+
+    def _integrate_launch(self, lib, array, limit, size):
+        _lib.check(lib.mr_tsdf_integrate_f32(*self._volume_args(), self._origin, self.voxel_size, self.trunc, limit, array, len(array),
+                                             size[0], size[1], self._stream()), "mr_tsdf_integrate_f32")
+
+    # -- surface
+    def _extract_launch(self, min_weight, records=None):
+        """One launch of the entry on the current stream - counting, or filling `records` - and the read of its cursor."""
+        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        out = (None, 0) if records is None else (records.data_ptr(), records.shape[0])
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mr_tsdf_extract_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), *out,
+                                                       cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
+        return int(cursor.item())
 
     # -- the surface as a mesh
     def _mesh_launches(self, min_weight, cursor, vertices=None, triangles=None, vertex_base=None):
@@ -436,6 +461,205 @@ class TSDFVolume:
         return volume
 
 
+# ------------------------------------------------------------------------------------------ the block-sparse volume
+def sparse_bytes(blocks, capacity, colour=True):
+    """Device bytes of a sparse volume of `blocks` = (nbx, nby, nbz) blocks with a pool of `capacity` slots: 4 per table entry, and per
+    slot 512 voxels of 12 (8 without colour) bytes plus its 4 bytes of `block_of_slot`."""
+    return 4 * int(blocks[0]) * int(blocks[1]) * int(blocks[2]) + int(capacity) * (BLOCK ** 3 * (12 if colour else 8) + 4)
+
+
+class SparseTSDFVolume(_Volume):
+    """A block-sparse TSDF volume on the device: storage only for the blocks of `BLOCK`^3 = 8 x 8 x 8 voxels that some keyframe puts
+    within the truncation band of a surface - for scenes whose dense grid `TSDFVolume` refuses.  A direct-indexed `table` of one int32
+    per block (-1: no storage, else a slot; no hashing) and a pool of `capacity_blocks` slots (`tsdf`, `weight`, `colour` of 512 voxels
+    each, `block_of_slot`), handed out on the device by one fetch-add per new block on `cursor` (include/monorec_hip.h has the rules,
+    tests/tsdf_sparse_ref.py restates them).  The constructor is `TSDFVolume`'s; the dims are ROUNDED UP to whole blocks (`dims` holds
+    the voxels, a multiple of 8 per axis, `blocks` the blocks: the volume may reach up to 7 voxels beyond the bounds asked for on the
+    high side).  `max_bytes` is the budget for table plus pool; `capacity_blocks` defaults to what fits in it (at most every block) and
+    raises above it; a table that alone exceeds the budget raises a ValueError that names its size.
+
+    A block gets its slot in the first integrate launch that brings one of its voxels into the band; from then on it equals the same
+    block of a dense volume that was empty at the start of that launch.  Free space seen only by EARLIER launches is lost for it (those
+    voxels have a lower weight than in a dense volume, and a crossing into a block that was never in a band is gone), that of earlier
+    frames of the same launch is kept; which slot a block gets is unspecified, everything else is deterministic.  A pool that runs out
+    drops the blocks that found no room: `overflowed()` tells, nothing is written out of bounds.
+    `extract` / `count` / `save_ply` work on the sparse volume itself (`mr_tsdf_sparse_extract_f32`); `to_dense()` gathers any region that
+    fits into a `TSDFVolume` for `mesh()`, `render()` and the rest."""
+
+    def __init__(self, bounds=None, voxel_size=0.1, trunc=None, colour=True, device="cuda:0", max_bytes=8 << 30, origin=None, dims=None,
+                 capacity_blocks=None):
+        voxel_size = self._geometry(bounds, voxel_size, trunc, origin, dims)
+        self.blocks = tuple((d + BLOCK - 1) // BLOCK for d in self.dims)
+        self.dims = tuple(b * BLOCK for b in self.blocks)
+        self.has_colour = bool(colour)
+        count, budget = self.blocks[0] * self.blocks[1] * self.blocks[2], int(max_bytes)
+        what = f"SparseTSDFVolume: {self.blocks[0]} x {self.blocks[1]} x {self.blocks[2]} blocks of {BLOCK}^3 voxels of {voxel_size:g} m"
+        if count >= 2 ** 31:
+            raise ValueError(f"{what} are {count} blocks; the table holds fewer than 2^31 - use a coarser voxel or a smaller box")
+        if sparse_bytes(self.blocks, 0) > budget:
+            raise ValueError(f"{what}: the table alone needs {4 * count / 2 ** 20:.1f} MiB, more than max_bytes = {budget / 2 ** 20:.1f} MiB")
+        fits = (budget - sparse_bytes(self.blocks, 0)) // sparse_bytes((0, 0, 0), 1, self.has_colour)
+        self.capacity = min(fits, count) if capacity_blocks is None else int(capacity_blocks)
+        if self.capacity < 1 or self.capacity > fits:
+            raise ValueError(f"{what}: a pool of {self.capacity} blocks and the table need {sparse_bytes(self.blocks, self.capacity, self.has_colour) / 2 ** 20:.1f} MiB; "
+                             f"max_bytes = {budget / 2 ** 20:.1f} MiB has room for {fits} blocks (at least 1 is needed)")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("monorec_amd.tsdf_fusion: the volume lives on a CUDA (HIP) device - there is no CPU fallback")
+        n = self.capacity * BLOCK ** 3
+        self.table = torch.empty(count, dtype=torch.int32, device=self.device)
+        self.tsdf = torch.empty(n, dtype=torch.float32, device=self.device)
+        self.weight = torch.empty(n, dtype=torch.float32, device=self.device)
+        self.colour = torch.empty(n, 4, dtype=torch.uint8, device=self.device) if self.has_colour else None
+        self.block_of_slot = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
+        self.cursor = torch.empty(1, dtype=torch.int64, device=self.device)
+        self._origin = (ctypes.c_float * 3)(*self.origin)
+        self._keep = None
+        self.frames = 0                                        # keyframes integrated so far
+        self.reset()
+
+    @property
+    def bounds(self):
+        """((x0, y0, z0), (x1, y1, z1)) of the first and the last voxel (after the rounding to whole blocks)."""
+        return self.origin, tuple(o + (d - 1) * self.voxel_size for o, d in zip(self.origin, self.dims))
+
+    def _table_args(self):
+        return (self.table.data_ptr(), *self.blocks, self.tsdf.data_ptr(), self.weight.data_ptr(),
+                self.colour.data_ptr() if self.colour is not None else None)
+
+    def reset(self):
+        """The table to -1, the cursor to 0, on the current stream; the pool needs no clearing (a block is written in full when it gets
+        a slot)."""
+        self.table.fill_(-1)
+        self.cursor.zero_()
+        self.frames = 0
+
+    def _integrate_launch(self, lib, array, limit, size):
+        _lib.check(lib.mr_tsdf_sparse_integrate_f32(*self._table_args(), self.block_of_slot.data_ptr(), self.capacity, self.cursor.data_ptr(),
+                                                    self._origin, self.voxel_size, self.trunc, limit, array, len(array), size[0], size[1],
+                                                    self._stream()), "mr_tsdf_sparse_integrate_f32")
+
+    # -- state
+    def allocated_blocks(self):
+        """Blocks that have storage (one read of the cursor)."""
+        return min(int(self.cursor.item()), self.capacity)
+
+    def overflowed(self):
+        """True when some block found no room in the pool (one read of the cursor): those blocks are missing from the volume."""
+        return int(self.cursor.item()) > self.capacity
+
+    def bytes_in_use(self):
+        """The table (4 bytes per block) plus the pool bytes of the allocated blocks: exactly `allocated_blocks()` x 512 x 12 (x 8 without colour)."""
+        return sparse_bytes(self.blocks, 0) + self.allocated_blocks() * BLOCK ** 3 * (12 if self.has_colour else 8)
+
+    # -- surface
+    def _extract_launch(self, min_weight, records=None):
+        """One launch of the entry over the allocated slots on the current stream - counting, or filling `records` - and the read of
+        its cursor."""
+        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        out = (None, 0) if records is None else (records.data_ptr(), records.shape[0])
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mr_tsdf_sparse_extract_f32(*self._table_args(), self.block_of_slot.data_ptr(), self.allocated_blocks(), self._origin,
+                                                              self.voxel_size, float(min_weight), *out, cursor.data_ptr(), self._stream()),
+                       "mr_tsdf_sparse_extract_f32")
+        return int(cursor.item())
+
+    # -- dense views of it
+    def allocated_box(self):
+        """(offset, dims) in voxels of the bounding box of the allocated blocks, or None when there is none."""
+        n = self.allocated_blocks()
+        if not n:
+            return None
+        coords = self._block_coords(self.block_of_slot[:n].cpu().numpy())
+        lo, hi = coords.min(axis=0), coords.max(axis=0) + 1
+        return tuple(int(v) * BLOCK for v in lo), tuple(int(v) * BLOCK for v in hi - lo)
+
+    def _block_coords(self, index):
+        index = np.asarray(index, dtype=np.int64)
+        return np.stack([index % self.blocks[0], index // self.blocks[0] % self.blocks[1], index // (self.blocks[0] * self.blocks[1])], axis=1)
+
+    def to_dense(self, bounds=None, max_bytes=8 << 30, offset=None, dims=None):
+        """A `TSDFVolume` holding a copy of a region (`mr_tsdf_sparse_gather_f32`; blocks without storage read as tsdf 1, weight 0,
+        colour 0): of `bounds` = ((x0, y0, z0), (x1, y1, z1)) in metres, clipped to the volume, or of `offset` and `dims` in voxels (need
+        not be block-aligned), or - the default - of the bounding box of the allocated blocks.  Above `max_bytes` the usual ValueError.
+        The dense volume's origin is the fp32 position of the region's first voxel, so with an offset other than 0 its voxel positions
+        (origin + i * voxel_size) may differ from this volume's in the last bit; the whole volume (`to_dense(volume.bounds)`) has
+        the same positions."""
+        if bounds is not None:
+            lo, hi = (np.asarray(b, dtype=np.float64) for b in bounds)
+            first = np.clip(np.floor((lo - self.origin) / self.voxel_size + 1e-6), 0, np.asarray(self.dims) - 1).astype(np.int64)
+            last = np.clip(np.ceil((hi - self.origin) / self.voxel_size - 1e-6), first, np.asarray(self.dims) - 1).astype(np.int64)
+            offset, dims = tuple(int(v) for v in first), tuple(int(v) for v in last - first + 1)
+        elif offset is None or dims is None:
+            box = self.allocated_box()
+            if box is None:
+                raise ValueError("SparseTSDFVolume.to_dense: no block is allocated; give bounds")
+            offset, dims = box
+        offset, dims = tuple(int(v) for v in offset), tuple(int(v) for v in dims)
+        if len(offset) != 3 or len(dims) != 3 or min(offset) < 0 or min(dims) < 1 or any(o + d > n for o, d, n in zip(offset, dims, self.dims)):
+            raise ValueError(f"SparseTSDFVolume.to_dense: the box of {dims} voxels at {offset} leaves the volume of {self.dims}")
+        origin = tuple(float(np.float32(o) + np.float32(i) * np.float32(self.voxel_size)) for o, i in zip(self.origin, offset))
+        dense = TSDFVolume(origin=origin, dims=dims, voxel_size=self.voxel_size, trunc=self.trunc, colour=self.has_colour, device=self.device,
+                           max_bytes=max_bytes)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().mr_tsdf_sparse_gather_f32(*self._table_args(), *offset, *dims, *dense._volume_args()[:3], self._stream()),
+                       "mr_tsdf_sparse_gather_f32")
+        dense.frames = self.frames
+        return dense
+
+    # -- the volume itself
+    def blocks_host(self):
+        """Host copies of the allocated blocks in the order of their table index (not of their slots): coordinates (n, 3) int32
+        (bx, by, bz), tsdf and weight (n, 8, 8, 8) fp32 indexed [z][y][x], colour (n, 8, 8, 8, 4) uint8 or None."""
+        n = self.allocated_blocks()
+        index = self.block_of_slot[:n].cpu().numpy().astype(np.int64)
+        order = np.argsort(index, kind="stable")
+        tsdf = self.tsdf[:n * BLOCK ** 3].cpu().numpy().reshape(n, BLOCK, BLOCK, BLOCK)[order]
+        weight = self.weight[:n * BLOCK ** 3].cpu().numpy().reshape(n, BLOCK, BLOCK, BLOCK)[order]
+        colour = self.colour[:n * BLOCK ** 3].cpu().numpy().reshape(n, BLOCK, BLOCK, BLOCK, 4)[order] if self.colour is not None else None
+        return self._block_coords(index[order]).astype(np.int32), tsdf, weight, colour
+
+    def save(self, file):
+        """.npz: blocks (n, 3) int32 block coordinates, tsdf, weight (n, 8, 8, 8) fp32, colour (n, 8, 8, 8, 4) uint8 if any - in the order of
+        the table, whatever the slots were -, origin, dims (nx, ny, nz voxels), voxel_size, trunc, frames."""
+        blocks, tsdf, weight, colour = self.blocks_host()
+        arrays = dict(blocks=blocks, tsdf=tsdf, weight=weight, origin=np.asarray(self.origin, dtype=np.float32),
+                      dims=np.asarray(self.dims, dtype=np.int64), voxel_size=np.float32(self.voxel_size), trunc=np.float32(self.trunc),
+                      frames=np.int64(self.frames))
+        if colour is not None:
+            arrays["colour"] = colour
+        np.savez(file, **arrays)
+
+    def set_blocks(self, blocks, tsdf, weight, colour=None):
+        """Replace the volume's content by these blocks (`blocks_host()`'s arrays, in any order, no block twice): slot i holds block i."""
+        blocks = np.asarray(blocks, dtype=np.int64).reshape(-1, 3)
+        n = blocks.shape[0]
+        index = (blocks[:, 2] * self.blocks[1] + blocks[:, 1]) * self.blocks[0] + blocks[:, 0]
+        if n > self.capacity or (n and (blocks.min() < 0 or np.any(blocks >= np.asarray(self.blocks)))) or len(np.unique(index)) != n:
+            raise ValueError(f"SparseTSDFVolume: {n} blocks for a pool of {self.capacity}, a block outside {self.blocks}, or one given twice")
+        if (colour is None) != (self.colour is None):
+            raise ValueError("SparseTSDFVolume: the blocks and the volume must both have colour, or neither")
+        self.reset()
+        if n:
+            self.table[torch.from_numpy(index).to(self.device)] = torch.arange(n, dtype=torch.int32, device=self.device)
+            self.block_of_slot[:n].copy_(torch.from_numpy(index.astype(np.int32)))
+            self.tsdf[:n * BLOCK ** 3].copy_(torch.from_numpy(np.ascontiguousarray(tsdf, dtype=np.float32).reshape(-1)))
+            self.weight[:n * BLOCK ** 3].copy_(torch.from_numpy(np.ascontiguousarray(weight, dtype=np.float32).reshape(-1)))
+            if self.colour is not None:
+                self.colour[:n * BLOCK ** 3].copy_(torch.from_numpy(np.ascontiguousarray(colour, dtype=np.uint8).reshape(-1, 4)))
+        self.cursor.fill_(n)
+
+    @classmethod
+    def load(cls, file, device="cuda:0", max_bytes=8 << 30, capacity_blocks=None):
+        """The volume of a `save`d .npz; `capacity_blocks` defaults to what fits in `max_bytes`."""
+        with np.load(file) as z:
+            volume = cls(origin=z["origin"], dims=z["dims"], voxel_size=float(z["voxel_size"]), trunc=float(z["trunc"]),
+                         colour="colour" in z.files, device=device, max_bytes=max_bytes, capacity_blocks=capacity_blocks)
+            volume.set_blocks(z["blocks"], z["tsdf"], z["weight"], z["colour"] if "colour" in z.files else None)
+            volume.frames = int(z["frames"]) if "frames" in z.files else 0
+        return volume
+
+
 # ------------------------------------------------------------------------------------------ a directory of tsdf_export
 _FRAME = re.compile(r"^frame-(\d+)\.pose\.txt$")
 
@@ -526,13 +750,24 @@ def fusion_settings(config):
                 save_volume=config.get("save_volume", None), fused_metrics=list(fused_metrics), render_dir=config.get("render_dir", None))
 
 
+def sparse_setting(config):
+    """The runner key `sparse_volume` (default false), checked: fuse into a `SparseTSDFVolume` over the same bounds, with
+    `tsdf_max_bytes` as the budget of its table and pool."""
+    sparse = config.get("sparse_volume", False)
+    if not isinstance(sparse, bool):
+        raise ValueError(f"monorec_amd.tsdf_fusion: sparse_volume {sparse!r} must be true or false")
+    return sparse
+
+
 class Fusion:
     """The stages of `run`, for callers that want them apart (tools/bench_tsdf_fusion.py times them): the constructor builds model,
     dataset and volume, `fuse()` drives the keyframe loop, `write()` extracts and saves."""
 
     def __init__(self, config, model=None, dataset=None, device="cuda:0"):
-        self.config, self.settings = config, fusion_settings(config)
+        self.config, self.settings, self.sparse = config, fusion_settings(config), sparse_setting(config)
         settings = self.settings
+        if settings["bounds"] is not None:
+            self._check_dense_outputs(settings["bounds"])         # before the model is built
         self.stream = stream = tx.KeyframeStream(config, model, dataset, (0, 1), device, who="monorec_amd.tsdf_fusion")
         y0, y1, x0, x1 = tx.crop_box(stream.crop, stream.height, stream.width)
         self.offset = (y0, x0)
@@ -547,11 +782,35 @@ class Fusion:
             geometry = [stream.dataset.keyframe_geometry(i) for i in items]
             bounds = bounds_from_frusta([g[0] for g in geometry], [self.shifted(g[1]) for g in geometry], ch, cw, config["max_d"],
                                         settings["voxel_size"])
-        self.volume = TSDFVolume(bounds, settings["voxel_size"], trunc=settings["trunc"], colour=True, device=stream.device,
-                                 max_bytes=settings["max_bytes"])
+            self._check_dense_outputs(bounds)
+        self.volume = (SparseTSDFVolume if self.sparse else TSDFVolume)(bounds, settings["voxel_size"], trunc=settings["trunc"], colour=True,
+                                                                        device=stream.device, max_bytes=settings["max_bytes"])
+        self._dense = None                                     # the sparse volume gathered for mesh, renders and score, once asked for
         depth_bytes, colour_bytes = tx.packed_sizes(1, ch, cw)
         self._slots = [torch.empty(depth_bytes + colour_bytes, dtype=torch.uint8, device=stream.device) for _ in range(settings["fuse_batch"])]
         self.mesh_counts = None                                # (vertices, triangles) of the mesh file, once `write()` has written one
+
+    def _check_dense_outputs(self, bounds):
+        """With `sparse_volume`, the mesh, the renders and the score work on the whole volume gathered into a dense one, which must fit
+        `tsdf_max_bytes` too: a ValueError that names the keys before anything is fused."""
+        settings = self.settings
+        asked = [key for key in ("mesh_file_name", "render_dir", "fused_metrics") if settings[key]]
+        if not self.sparse or not asked:
+            return
+        dims = tuple((d + BLOCK - 1) // BLOCK * BLOCK for d in dims_of_bounds(bounds, settings["voxel_size"]))
+        if volume_bytes(dims) > settings["max_bytes"]:
+            raise ValueError(f"monorec_amd.tsdf_fusion: {', '.join(asked)} with sparse_volume need the volume gathered into a dense one of "
+                             f"{dims[0]} x {dims[1]} x {dims[2]} voxels, {volume_bytes(dims) / 2 ** 30:.2f} GiB, more than tsdf_max_bytes = "
+                             f"{settings['max_bytes'] / 2 ** 30:.2f} GiB; raise tsdf_max_bytes, or write the points alone (file_name)")
+
+    def dense(self):
+        """The volume `mesh()`, `render()` and `score()` work on: the volume itself, or the whole sparse one gathered (`to_dense`, once)."""
+        if not self.sparse:
+            return self.volume
+        if self._dense is None:
+            self._check_dense_outputs(self.volume.bounds)
+            self._dense = self.volume.to_dense(self.volume.bounds, max_bytes=self.settings["max_bytes"])
+        return self._dense
 
     def shifted(self, k):
         """The intrinsics of the cropped image, as `save_intrinsics_for_tsdf` shifts them, on a copy."""
@@ -582,6 +841,9 @@ class Fusion:
 
         stream.run(emit)
         flush()
+        if self.sparse and volume.overflowed():
+            raise RuntimeError(f"monorec_amd.tsdf_fusion: the pool of {volume.capacity} blocks ({sparse_bytes((0, 0, 0), volume.capacity) / 2 ** 20:.1f} MiB) "
+                               f"of the sparse volume ran out, blocks of the surface are missing; raise tsdf_max_bytes (or the voxel size)")
         return self
 
     def write(self):
@@ -589,7 +851,7 @@ class Fusion:
         os.makedirs(out_dir, exist_ok=True)
         count = self.volume.save_ply(os.path.join(out_dir, self.settings["file_name"]))
         if self.settings["mesh_file_name"] is not None:
-            self.mesh_counts = self.volume.save_mesh_ply(os.path.join(out_dir, self.settings["mesh_file_name"]))
+            self.mesh_counts = self.dense().save_mesh_ply(os.path.join(out_dir, self.settings["mesh_file_name"]))
         if self.settings["save_volume"] is not None:
             self.volume.save(self.settings["save_volume"])
         if self.settings["render_dir"] is not None:
@@ -608,7 +870,7 @@ class Fusion:
         `max_distance`: as the metric functions take them.  Returns dict(metrics {name: value} - each what the metric function of that
         name returns for all samples as one batch -, coverage: the share of target pixels the render hit, samples)."""
         from . import metrics
-        stream, volume = self.stream, self.volume
+        stream, volume = self.stream, self.dense()
         items = stream.export_items()
         height, width = stream.height, stream.width
         sums, hit, have = [], torch.zeros((), dtype=torch.int64, device=volume.device), torch.zeros((), dtype=torch.int64, device=volume.device)
@@ -633,7 +895,7 @@ class Fusion:
         intrinsics, `frame-%06d.fused.depth.png` (16 bit, centimetres, 0: nothing) and `frame-%06d.fused.color.jpg`, names that sort
         next to the export's.  After the fusion and synchronous: not a stage of the loop.  Returns the number of keyframes."""
         from PIL import Image
-        stream, volume = self.stream, self.volume
+        stream, volume = self.stream, self.dense()
         os.makedirs(str(directory), exist_ok=True)
         items = stream.export_items()
         y0, y1, x0, x1 = tx.crop_box(stream.crop, stream.height, stream.width)
@@ -661,7 +923,10 @@ def run(config, model=None, dataset=None, device="cuda:0"):
     `trunc_voxels` (5), `mesh_file_name` (None; a name: the surface is also written as a triangle mesh, `TSDFVolume.save_mesh_ply`, next to
     the points), `bounds` (else `bounds_from_frusta` over the window's exported keyframe poses and `max_d`; without both it
     raises), `tsdf_max_bytes`, `fuse_batch` (keyframes per integrate launch, default 4), `save_volume` (a path for `TSDFVolume.save`),
-    `render_dir` (a directory for `Fusion.write_renders`), `fused_metrics` (names for `Fusion.score()`; `main` prints its result).
+    `render_dir` (a directory for `Fusion.write_renders`), `fused_metrics` (names for `Fusion.score()`; `main` prints its result),
+    `sparse_volume` (false; true: fuse into a `SparseTSDFVolume` over the same bounds with `tsdf_max_bytes` as the budget of table and pool -
+    points and `save_volume` come from it, mesh, renders and score from the whole of it gathered into a dense volume, which must fit
+    `tsdf_max_bytes` as well; a pool that ran out raises after the loop).
 
     Per keyframe `pack_frames` (vote, crop, thresholds: the depths are exactly the ones the export writes to the PNG) fills a staging slot
     on the device; after `fuse_batch` keyframes, or at the end, one integrate launch follows on the same stream.  Every keyframe is
@@ -675,6 +940,9 @@ def main(argv=None):
     fusion = Fusion(config, device=device).fuse()
     count = fusion.write()
     print(f"{count} surface points written to {os.path.join(config.get('output_dir', 'saved'), config.get('file_name', 'tsdf.ply'))}")
+    if fusion.sparse:
+        print(f"{fusion.volume.allocated_blocks()} of {fusion.volume.table.numel()} blocks allocated, {fusion.volume.bytes_in_use() / 2 ** 20:.1f} MiB in use "
+              f"(dense: {volume_bytes(fusion.volume.dims) / 2 ** 20:.1f} MiB)")
     if fusion.mesh_counts is not None:
         print(f"{fusion.mesh_counts[0]} vertices and {fusion.mesh_counts[1]} triangles written to "
               f"{os.path.join(config.get('output_dir', 'saved'), config['mesh_file_name'])}")
