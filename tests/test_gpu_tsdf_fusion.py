@@ -142,6 +142,43 @@ def test_cameras_in_and_around_the_volume_at_any_angle(hip_lib, seed):
     _assert_equal(volume, want, seed)
 
 
+HARD_SEED = 6                                  # of ref.camera_cases: the first seed at which every case below, on both volumes, meets its sums
+
+
+@functools.lru_cache(maxsize=None)
+def _hard_reference(name, kind, depth, shift):
+    """(spec, frames, ks, the restatement's volume, [updated, behind, outside] summed over the frames as fractions of the volume)."""
+    spec = ref.shifted(VOLUMES[name], shift)
+    frames, ks = ref.camera_cases(VOLUMES[name], HARD_SEED, kind, depth, shift)
+    want, sums = ref.new_volume(**spec), np.zeros(3)
+    for (pose, depth_cm, image), k in zip(frames, ks):
+        stats = ref.integrate(want, ref.world_to_camera(pose), k, depth_cm, image, np.inf if depth is None else depth)
+        sums += [stats["updated"].mean(), stats["behind"].mean(), stats["outside"].mean()]
+    return spec, frames, ks, want, sums
+
+
+@pytest.mark.parametrize("depth", [None, 2.0], ids=["inf", "2m"])
+@pytest.mark.parametrize("shift", [ref.ORIGIN, ref.FAR], ids=["origin", "far"])
+@pytest.mark.parametrize("kind", ref.CAMERA_KINDS)
+@pytest.mark.parametrize("name", ["wide", "small"])
+def test_hard_cameras_poses_and_intrinsics_in_both_worlds(hip_lib, name, kind, shift, depth):
+    """The tile cull where its margins are asked for: ref.camera_cases' eight cameras in one launch - poses that are no rotations
+    (normalised per plane, or culling off), principal points outside the image, fy = 4 fx, one K per frame - round the origin and
+    1.5 km from it, where FP32_SLACK * reach carries the margin and not 1e-3 voxel; on the wide volume and on the one with the odd nx."""
+    spec, frames, ks, want, (updated, behind, outside) = _hard_reference(name, kind, depth, shift)
+    assert updated > (0.05 if depth is None else 0.03) and behind > 1 and outside > 1 and want["weight"].max() >= 2, (updated, behind, outside)
+    rows = np.linalg.norm(ref.world_to_camera(frames[0][0])[:, :3], axis=1)
+    assert np.all(rows < 0.5) == (kind == "wild") and (np.abs(rows - 1).max() > 0.2) == (kind in ("scaled", "sheared", "wild"))
+    depth_cm, image, poses = _on_device(frames)
+    k = torch.tensor(np.stack([ref.k_matrix(v) for v in ks]), dtype=torch.float32)
+    volume = tf.TSDFVolume(origin=spec["origin"], dims=spec["dims"], voxel_size=spec["voxel_size"], trunc=spec["trunc"], device=DEV)
+    volume.integrate(depth_cm, image, poses, k, depth)
+    if kind == "wild":
+        # culling is off for these matrices; the restatement has one path for every matrix, the one `rigid` takes
+        _assert_equal(volume, want, ("wild against the restatement's only path", name, shift, depth))
+    _assert_equal(volume, want, (name, kind, shift, depth))
+
+
 def test_voxel_indices_past_2_to_31(hip_lib):
     """The only cover of the 64-bit index path, and the one large test of this file: 2048 x 1024 x 1028 voxels without colour, 17.2 GB
     of device memory for about a second (plus 0.1 GB of temporaries: the untouched voxels are counted 64 slices at a time).  The

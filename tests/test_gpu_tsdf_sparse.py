@@ -34,12 +34,15 @@ def _volume(spec, colour=True, **kw):
                                device=DEV, **kw)
 
 
-def _fuse(volume, frames, batch):
+def _fuse(volume, frames, batch, ks=None, max_depth_m=None):
+    """`ks`: one (fx, fy, cx, cy) per frame; None: sref.K for all."""
     depth = torch.from_numpy(np.stack([f[1] for f in frames])).to(DEV)
     image = torch.from_numpy(np.stack([f[2] for f in frames])).to(DEV)
     poses = torch.from_numpy(np.stack([f[0] for f in frames]))
+    kmat = None if ks is None else torch.tensor(np.stack([ref.k_matrix(k) for k in ks]), dtype=torch.float32)
     for lo in range(0, len(frames), batch):
-        volume.integrate(depth[lo:lo + batch], image[lo:lo + batch] if volume.has_colour else None, poses[lo:lo + batch], KMAT)
+        volume.integrate(depth[lo:lo + batch], image[lo:lo + batch] if volume.has_colour else None, poses[lo:lo + batch],
+                         KMAT if ks is None else kmat[lo:lo + batch], max_depth_m)
     return volume
 
 
@@ -119,6 +122,30 @@ def test_late_allocation_loses_earlier_launches_and_keeps_earlier_frames(hip_lib
     _assert_grids_equal(got3, want3)
     keep = sref.per_voxel(want3["allocated"])
     assert np.array_equal(got3.grids()[1][keep], dense["weight"][keep]) and np.array_equal(got3.grids()[0][keep], dense["tsdf"][keep])
+
+
+def _assert_records_equal(volume, want, weights=(0, 1)):
+    for min_weight in weights:
+        expect = ref.sort_records(sref.extract(want, min_weight))
+        assert volume.count(min_weight) == len(expect), min_weight
+        assert np.array_equal(ref.sort_records(volume.extract(min_weight).cpu().numpy()), expect), min_weight
+
+
+@pytest.mark.parametrize("case", sref.CULL_CASES, ids=sref.cull_case_id)
+def test_culls_that_cut(hip_lib, case):
+    """Neither the planes per block nor the launch's box of blocks may change a result: ref.camera_cases' cameras - inside and round
+    the volume, turned any way, poses that are no rotations, principal points outside the image, fy = 4 fx, one K per frame - with a
+    depth limit that puts the faces of the box inside the table (test_tsdf_sparse.py proves that on the restatement), round the origin
+    and 1.5 km from it, in launches of 1, 3 and 8."""
+    kind, depth, shift, batch, colour = case
+    spec, frames, ks, limit = sref.cull_inputs(kind, depth, shift)
+    want = sref.fuse(spec, frames, batch, colour=colour, intrinsics=ks, max_depth_m=limit)
+    _assert_not_degenerate(want, points=False)
+    volume = _fuse(_volume(spec, colour), frames, batch, ks, depth)
+    assert volume.frames == 8
+    _assert_table_consistent(volume, want)
+    _assert_grids_equal(volume.to_dense(volume.bounds), want, what=case)
+    _assert_records_equal(volume, want)
 
 
 # ------------------------------------------------------------------------------------------ 2. extract
@@ -245,6 +272,38 @@ def test_gather_of_boxes_off_the_block_grid_and_of_unallocated_space(hip_lib):
         volume.to_dense(volume.bounds, max_bytes=1 << 20)
 
 
+def test_gather_beyond_one_grid_of_workgroups(hip_lib):
+    """Above 65536 workgroups of 256 voxels the gather kernel strides: a box of 263 x 256 x 256 = 17 235 968 voxels (an odd dx under
+    the 64-bit i / dx), and one of 256^3 = 16 777 216, the last size that does not.  Eight blocks, the table's first and last among
+    them; everything else reads as the empty state."""
+    dims = (264, 256, 256)
+    volume = tf.SparseTSDFVolume(origin=(-0.3, 0.2, 1.0), dims=dims, voxel_size=0.06, trunc=0.18, device=DEV, capacity_blocks=8)
+    nbx, nby, nbz = volume.blocks
+    assert (nbx, nby, nbz) == (33, 32, 32)
+    rng = np.random.default_rng(11)
+    index = np.concatenate([[0, nbx * nby * nbz - 1], rng.choice(np.arange(1, nbx * nby * nbz - 1), size=6, replace=False)])
+    coords = volume._block_coords(index)
+    assert (coords[:, 0] == 0).any() and (coords[:, 0] == 32).any() and len(np.unique(index)) == 8     # blocks that each box cuts or leaves out
+    tsdf = rng.uniform(-1, 1, size=(8, 8, 8, 8)).astype(np.float32)
+    weight = rng.integers(0, 5, size=(8, 8, 8, 8)).astype(np.float32)
+    colour = rng.integers(0, 256, size=(8, 8, 8, 8, 4)).astype(np.uint8)
+    colour[..., 3] = 0
+    volume.set_blocks(coords, tsdf, weight, colour)
+    want_t, want_w = np.ones(dims[::-1], np.float32), np.zeros(dims[::-1], np.float32)
+    want_c = np.zeros(dims[::-1] + (4,), np.uint8)
+    for (bx, by, bz), t, w, c in zip(coords, tsdf, weight, colour):
+        cut = (slice(bz * 8, bz * 8 + 8), slice(by * 8, by * 8 + 8), slice(bx * 8, bx * 8 + 8))
+        want_t[cut], want_w[cut], want_c[cut] = t, w, c
+    for offset, size in (((1, 0, 0), (263, 256, 256)), ((0, 0, 0), (256, 256, 256))):
+        assert (size[0] * size[1] * size[2] > 65536 * 256) == (offset[0] == 1)
+        dense = volume.to_dense(offset=offset, dims=size)
+        got_t, got_w, got_c = dense.grids()
+        cut = tuple(slice(o, o + d) for o, d in zip(offset[::-1], size[::-1]))
+        assert got_t.shape == size[::-1] and (want_w[cut] > 0).sum() > 1000
+        assert np.array_equal(got_w, want_w[cut]) and np.array_equal(got_t, want_t[cut]) and np.array_equal(got_c, want_c[cut])
+        del dense, got_t, got_w, got_c
+
+
 # ------------------------------------------------------------------------------------------ 4. a pool that runs out
 def test_a_full_pool_drops_blocks_and_writes_nothing_out_of_bounds(hip_lib):
     want = _restated("first", 3)
@@ -272,7 +331,36 @@ def test_a_full_pool_drops_blocks_and_writes_nothing_out_of_bounds(hip_lib):
         assert np.array_equal(t, want["tsdf"][cut]) and np.array_equal(w, want["weight"][cut]) and np.array_equal(c, want["colour"][cut])
     points = volume.extract().cpu().numpy()
     have = {r.tobytes() for r in sref.extract(want)}
+    # which eight blocks found room is unspecified: read them off the table; the points are those of the restatement cut down to them
+    stored = (table >= 0).reshape(want["allocated"].shape)
+    assert stored.sum() == 8 and not (stored & ~want["allocated"]).any()
+    assert np.array_equal(ref.sort_records(points), ref.sort_records(ref.extract(sref.sparsify(want, stored))))
     assert 0 < len(points) < len(have)
+
+
+def test_reset_and_reuse(hip_lib):
+    """`reset()` clears the table and the cursor alone.  The second content allocates fewer blocks than the first, so the first's
+    block_of_slot entries and pool data lie beyond the new count - and must stay out of every result."""
+    volume = _fuse(_volume(sref.SECOND), _frames(), 3)
+    first = _restated("second", 3)
+    _assert_table_consistent(volume, first)
+    volume.reset()
+    assert volume.allocated_blocks() == 0 and volume.count() == 0 and volume.frames == 0 and not volume.overflowed()
+    assert tuple(volume.extract().shape) == (0, 6) and bool((volume.table == -1).all())
+    # the rigid case with a 2 m limit: its first two frames alone band 20 blocks, fewer than the arc's 47
+    spec, frames, ks, limit = sref.cull_inputs("rigid", 2.0, "origin")
+    assert spec == sref.SECOND
+    for count, batch in ((2, 1), (8, 3)):                                     # ... and then all eight: 139 blocks, past the stale ones again
+        want = sref.fuse(spec, frames[:count], batch, intrinsics=ks[:count], max_depth_m=limit)
+        _assert_not_degenerate(want)
+        assert int(want["allocated"].sum()) == {2: 20, 8: 139}[count] and int(first["allocated"].sum()) == 47
+        _fuse(volume, frames[:count], batch, ks[:count], limit)
+        assert volume.frames == count
+        _assert_table_consistent(volume, want)
+        _assert_grids_equal(volume.to_dense(volume.bounds), want)
+        _assert_records_equal(volume, want)
+        volume.reset()
+    assert volume.allocated_blocks() == 0 and volume.count() == 0 and volume.frames == 0
 
 
 # ------------------------------------------------------------------------------------------ 5. a volume the dense class refuses

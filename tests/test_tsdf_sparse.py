@@ -243,3 +243,63 @@ def test_blocks_of_and_sparsify_round_trip():
     again = sref.sparsify(dense, sparse["allocated"])
     for key in ("tsdf", "weight", "colour"):
         assert np.array_equal(again[key], sparse[key])
+
+
+# ------------------------------------------------------------------------------------------ the inputs of the culling tests
+@functools.lru_cache(maxsize=None)
+def _cull_measures(kind, depth, shift):
+    """What the restatement and `bounds_from_frusta` say about one set of inputs of test_culls_that_cut, in launches of one frame (a
+    larger launch changes these voxels and more: a block allocated at its end keeps every frame's update).  The geometric box of a
+    frame is the box of its pyramid out to min(max_depth_m, 327.67) + trunc: no slack, no code under test.  In voxel indices:
+    interior  frames whose box has a face strictly inside the table
+    faces     (axis, side) where some frame has that face strictly inside the table AND changes a voxel of the face's own layer of
+              blocks - a launch box that is one block short there loses that voxel
+    outside   how far, in voxels, a changed voxel lies outside its frame's box, at most
+    changed   voxels some launch changed; allocated, blocks: the blocks with storage at the end, and all"""
+    spec, frames, ks, limit = sref.cull_inputs(kind, depth, shift)
+    changed = []
+    vol = sref.fuse(spec, frames, 1, colour=False, intrinsics=ks, max_depth_m=limit, changed=changed)
+    dims, origin, voxel = np.array(spec["dims"]), np.array(spec["origin"], dtype=np.float64), spec["voxel_size"]
+    interior, faces, outside = 0, set(), 0.0
+    for (pose, _, _), k, mask in zip(frames, ks, changed):
+        lo, hi = tf.bounds_from_frusta([pose], ref.k_matrix(k), ref.CASE_H, ref.CASE_W, min(limit, 327.67) + spec["trunc"], voxel)
+        box = ((np.array(lo) - origin) / voxel, (np.array(hi) - origin) / voxel)
+        index = np.nonzero(mask)[::-1]                                        # x, y, z of the changed voxels
+        inside = False
+        for axis in range(3):
+            if len(index[axis]):
+                outside = max(outside, box[0][axis] - index[axis].min(), index[axis].max() - box[1][axis])
+            for side in range(2):
+                face = box[side][axis]
+                if 0 < face < dims[axis] - 1:
+                    inside = True
+                    if np.any(index[axis] // sref.B == int(np.floor(face / sref.B))):
+                        faces.add((axis, side))
+        interior += inside
+    return dict(interior=interior, faces=faces, outside=float(outside), changed=int(np.any(changed, axis=0).sum()),
+                allocated=int(vol["allocated"].sum()), blocks=vol["allocated"].size)
+
+
+def test_the_cases_of_the_culling_test_are_sharp():
+    """Before a GPU sees them: the inputs of test_culls_that_cut put the faces of the launch box inside the table, with voxels the
+    restatement changes right behind them, on every side and under every depth limit."""
+    cases = sref.CULL_CASES
+    assert len(cases) == 40
+    for depth in sref.CULL_DEPTHS:                                            # every value of every axis meets every depth limit
+        mine = [c for c in cases if c[1] == depth]
+        assert {c[0] for c in mine} == set(ref.CAMERA_KINDS) and {c[2] for c in mine} == set(sref.SHIFTS)
+        assert {c[3] for c in mine} == {1, 3, 8} and {c[4] for c in mine} == {True, False}
+    for depth in sref.CULL_DEPTHS:
+        for shift in sref.SHIFTS:
+            group = set()
+            for kind in ref.CAMERA_KINDS:
+                m = _cull_measures(kind, depth, shift)
+                what = (kind, depth, shift, m)
+                assert m["outside"] <= sref.B, what                           # the helper itself: nothing changes beyond its frame's pyramid
+                assert m["changed"] >= 500 and 0 < m["allocated"] < m["blocks"], what
+                if depth is not None:
+                    assert m["interior"] >= 7, what
+                if kind != "wild":                                            # (wild's launch box is the whole table: its faces prove nothing)
+                    group |= m["faces"]
+            if depth is not None:
+                assert group == {(axis, side) for axis in range(3) for side in range(2)}, (depth, shift, group)

@@ -233,3 +233,69 @@ SMALL = dict(dims=(37, 21, 13), origin=(-1.1, -0.6, 2.45), voxel_size=0.06, trun
 WIDE = dict(dims=(128, 24, 12), origin=(-3.81, -0.7, 2.5), voxel_size=0.06, trunc=0.18)
 INTRINSICS_30 = (30.0, 30.0, 19.5, 11.5)
 INTRINSICS_60 = (60.0, 60.0, 19.5, 11.5)
+
+
+# ------------------------------------------------------------------------------------------ hard cameras
+CAMERA_KINDS = ("rigid", "scaled", "sheared", "wild", "offcentre", "aniso")
+ORIGIN, FAR = (0.0, 0.0, 0.0), (812.3, -41.7, 1203.9)      # the two worlds: round the origin, and where an fp32 ulp is a tenth of a millimetre
+CASE_H, CASE_W = 24, 40
+
+
+def shifted(spec, shift):
+    """`spec` moved by `shift` metres."""
+    return dict(spec, origin=tuple(float(o) + float(s) for o, s in zip(spec["origin"], shift)))
+
+
+def camera_cases(spec, seed, kind="rigid", max_depth_m=None, shift=ORIGIN):
+    """Eight cameras for culling to be wrong about, for the volume `shifted(spec, shift)`: (frames, ks), frames = [(cam_to_world (4, 4)
+    fp32, depth_cm (24, 40) int16, colour (24, 40, 3) uint8)] and ks = [(fx, fy, cx, cy)], one per frame.
+    Centres uniform in the volume's box grown by 0.3 m, turned any way (the Q of a normal matrix, det +1), fx from {12, 30, 90} and
+    fy = 1.1 fx, the principal point within a pixel of the middle, depth uniform in 20 .. 400 cm with one pixel in ten 0, random colours.
+    The outermost ring of every depth map holds min(max_depth_m, 4 m) - written before the zeros are drawn -, so that voxels out to
+    max_depth_m + trunc along the corner rays are updated.  `kind`:
+      rigid      as above
+      scaled     the rotation block of cam_to_world times 1.5 (even frames) or 0.7 (odd): world -> camera has rows of 0.67 or 1.43
+      sheared    its columns times 0.8, 1.0, 1.3
+      wild       times 3: the rows of world -> camera are 1 / 3 long, beyond what culling takes for a rotation
+      offcentre  on frames 0, 2, 4, 6 the principal point outside the image: cx from {-15, w + 10}, cy from {-9, h + 6}
+      aniso      fy = 4 fx"""
+    assert kind in CAMERA_KINDS, kind
+    rng = np.random.default_rng(seed)
+    h, w = CASE_H, CASE_W
+    lo = np.array(shifted(spec, shift)["origin"], dtype=np.float64)
+    hi = lo + (np.array(spec["dims"]) - 1) * spec["voxel_size"]
+    depth = rng.integers(20, 400, size=(8, h, w)).astype(np.int16)
+    ring = int(round(100 * min(np.inf if max_depth_m is None else float(max_depth_m), 4.0)))
+    depth[:, 0, :] = depth[:, -1, :] = ring
+    depth[:, :, 0] = depth[:, :, -1] = ring
+    depth[rng.random((8, h, w)) < 0.1] = 0
+    image = rng.integers(0, 256, size=(8, h, w, 3)).astype(np.uint8)
+    frames, ks = [], []
+    for i in range(8):
+        q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+        q = q * np.sign(np.diag(r))
+        if np.linalg.det(q) < 0:
+            q[:, 0] = -q[:, 0]
+        centre = lo - 0.3 + rng.random(3) * (hi - lo + 0.6)
+        focal = float(rng.choice([12.0, 30.0, 90.0]))
+        cx, cy = 19.5 + rng.normal(), 11.5 + rng.normal()
+        out_x, out_y = float(rng.choice([-15.0, w + 10.0])), float(rng.choice([-9.0, h + 6.0]))
+        if kind == "scaled":
+            q = q * (1.5 if i % 2 == 0 else 0.7)
+        elif kind == "sheared":
+            q = q * np.array([0.8, 1.0, 1.3])
+        elif kind == "wild":
+            q = q * 3.0
+        elif kind == "offcentre" and i % 2 == 0:
+            cx, cy = out_x, out_y
+        pose = np.eye(4)
+        pose[:3, :3], pose[:3, 3] = q, centre
+        frames.append((pose.astype(F), depth[i], image[i]))
+        ks.append((focal, focal * (4.0 if kind == "aniso" else 1.1), float(cx), float(cy)))
+    return frames, ks
+
+
+def k_matrix(k):
+    """(fx, fy, cx, cy) as the 3 x 3 matrix."""
+    fx, fy, cx, cy = k
+    return np.array([[fx, 0.0, cx], [0.0, fy, cy], [0.0, 0.0, 1.0]], dtype=np.float64)

@@ -32,14 +32,22 @@ def per_voxel(blocks):
     return blocks.repeat(B, axis=0).repeat(B, axis=1).repeat(B, axis=2)
 
 
+def intrinsics_of(intrinsics, count):
+    """One (fx, fy, cx, cy) for all of `count` frames, or one per frame, as a list of `count`."""
+    ks = np.asarray(intrinsics, dtype=np.float64)
+    assert ks.shape in ((4,), (count, 4)), ks.shape
+    return [tuple(ks)] * count if ks.ndim == 1 else [tuple(k) for k in ks]
+
+
 def integrate_launch(vol, frames, intrinsics=K, max_depth_m=np.inf):
     """One launch of `frames` = [(cam_to_world, depth_cm, colour)] into `vol`, in place: the frames go into a trial copy with
     `ref.integrate` one by one - for a block without storage that is the empty start state -, the blocks with a voxel in some frame's
-    band join the allocated set, and only allocated blocks keep the trial's values.  Returns the grid of newly allocated blocks."""
+    band join the allocated set, and only allocated blocks keep the trial's values.  `intrinsics`: one (fx, fy, cx, cy), or one per
+    frame.  Returns the grid of newly allocated blocks."""
     trial = ref.copy_volume(vol)
     band = np.zeros(vol["tsdf"].shape, bool)
-    for pose, depth, colour in frames:
-        band |= ref.integrate(trial, ref.world_to_camera(pose), intrinsics, depth, colour if vol["colour"] is not None else None, max_depth_m)["band"]
+    for (pose, depth, colour), k in zip(frames, intrinsics_of(intrinsics, len(frames))):
+        band |= ref.integrate(trial, ref.world_to_camera(pose), k, depth, colour if vol["colour"] is not None else None, max_depth_m)["band"]
     new = any_per_block(band) & ~vol["allocated"]
     vol["allocated"] = vol["allocated"] | new
     keep = per_voxel(vol["allocated"])
@@ -48,11 +56,16 @@ def integrate_launch(vol, frames, intrinsics=K, max_depth_m=np.inf):
     return new
 
 
-def fuse(spec, frames, batch, colour=True, intrinsics=K):
-    """A new volume of `spec` after `frames` in launches of `batch`."""
+def fuse(spec, frames, batch, colour=True, intrinsics=K, max_depth_m=np.inf, changed=None):
+    """A new volume of `spec` after `frames` in launches of `batch`.  `changed`: a list that receives, per launch, the mask of the
+    voxels whose weight the launch changed."""
     vol = new_volume(colour=colour, **spec)
+    ks = intrinsics_of(intrinsics, len(frames))
     for lo in range(0, len(frames), batch):
-        integrate_launch(vol, frames[lo:lo + batch], intrinsics)
+        before = vol["weight"]
+        integrate_launch(vol, frames[lo:lo + batch], ks[lo:lo + batch], max_depth_m)
+        if changed is not None:
+            changed.append(vol["weight"] != before)
     return vol
 
 
@@ -89,3 +102,40 @@ def sparsify(vol, allocated):
         out["colour"] = np.where(keep[..., None], vol["colour"], np.uint8(0)).astype(np.uint8)
     out["allocated"] = allocated.copy()
     return out
+
+
+# ------------------------------------------------------------------------------------------ culls that cut
+# The cases of test_culls_that_cut (GPU) and of the CPU test that proves them sharp: every kind of ref.camera_cases with every depth
+# limit in both worlds on SECOND, launches of 1, 3 and 8 and both colour settings dealt round so that every value of every axis meets
+# every depth limit, and four more launches of 1 (the launch box is then one frame's own).
+SHIFTS = {"origin": ref.ORIGIN, "far": ref.FAR}
+CULL_DEPTHS = (None, 2.0, 0.6)
+# (kind, max_depth_m, shift name) -> seed where seed 0 misses a precondition (its launches change 352 and 263 voxels, fewer than 500)
+CULL_SEEDS = {("offcentre", 0.6, "origin"): 1, ("offcentre", 0.6, "far"): 1, ("aniso", 0.6, "origin"): 3, ("aniso", 0.6, "far"): 3}
+
+
+def _cull_cases():
+    cases = []
+    for ki, kind in enumerate(ref.CAMERA_KINDS):
+        for di, depth in enumerate(CULL_DEPTHS):
+            for si, shift in enumerate(SHIFTS):
+                cases.append((kind, depth, shift, (1, 3, 8)[(ki + di + si) % 3], (ki + si) % 2 == 0))
+    cases += [("rigid", 0.6, "origin", 1, False), ("scaled", 0.6, "far", 1, True), ("offcentre", 2.0, "origin", 1, False),
+              ("aniso", 0.6, "far", 1, True)]
+    assert len(set(cases)) == len(cases) == 40
+    return cases
+
+
+CULL_CASES = _cull_cases()
+
+
+def cull_case_id(case):
+    kind, depth, shift, batch, colour = case
+    return f"{kind}-{'inf' if depth is None else depth}-{shift}-{batch}-{'colour' if colour else 'plain'}"
+
+
+def cull_inputs(kind, depth, shift):
+    """(spec, frames, ks, limit) of a case: SECOND moved to the case's world and ref.camera_cases' eight frames for it."""
+    seed = CULL_SEEDS.get((kind, depth, shift), 0)
+    frames, ks = ref.camera_cases(SECOND, seed, kind, depth, SHIFTS[shift])
+    return ref.shifted(SECOND, SHIFTS[shift]), frames, ks, np.inf if depth is None else depth
