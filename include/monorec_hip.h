@@ -934,6 +934,28 @@ int mr_tsdf_sparse_gather_f32(const int32_t* table, int32_t nbx, int32_t nby, in
                               const uint8_t* colour, int32_t x0, int32_t y0, int32_t z0, int32_t dx, int32_t dy, int32_t dz,
                               float* out_tsdf, float* out_weight, uint8_t* out_colour, void* stream);
 
+/* The sparse volume seen from a camera (added within ABI 24: the change only adds symbols).  The entry returns the result of
+ * mr_tsdf_render_f32 with bricks NULL on the virtual dense volume of 8 nbx x 8 nby x 8 nbz voxels in which a block without a slot reads
+ * tsdf 1, weight 0, colour 0 - what mr_tsdf_sparse_gather_f32 would write -: bit for bit, for depth, normal and colour, for every
+ * min_weight and any number of views per launch.  The views, the samples t_k = t_min + (float)k * step, the VALID / HIT / back-face state
+ * machine, the fp32 operation order and the 2^20-sample cap are mr_tsdf_render_f32's (the same code, csrc/tsdf_render.h).
+ * num_slots: the slots in use, as for mr_tsdf_sparse_extract_f32; a table entry below 0 or at or above num_slots is no slot.
+ * num_slots == 0 is no error: no voxel is negative, every output is written as 0.
+ * Corner fetch: for the cell base i, corner i + d lies in block (i + d) >> 3 at the local voxel (i + d) & 7, pool index
+ * slot * 512 + (lz * 8 + ly) * 8 + lx (64 bit).  When (i_a & 7) < 7 on all three axes - 343 of every 512 cells - the eight corners share
+ * one block and one table load serves them; otherwise up to eight table loads.  A corner in a block without a slot yields weight 0,
+ * tsdf 1, colour 0 without touching the pool.
+ * Empty space: with min_weight >= 0 a sample whose base cell lies in a block without a slot is not VALID (corner i itself has weight 0):
+ * it costs one table load and sets prev_valid = false.  With min_weight < 0 such corners count as seen with tsdf 1 and the sample is
+ * evaluated in full, with no shortcut.
+ * MR_ERR_BAD_ARGUMENT, nothing is launched: the table, pool and alignment cases of the other sparse entries; a block count above 2^27 on
+ * some axis; num_slots < 0, num_slots * 512 >= 2^40 or num_slots > nbx * nby * nbz; origin NULL, voxel_size <= 0 (or NaN), NaN
+ * min_weight; every view, size and range case of mr_tsdf_render_f32. */
+int mr_tsdf_sparse_render_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf, const float* weight,
+                              const uint8_t* colour, int64_t num_slots, const float* origin, float voxel_size, float min_weight,
+                              const mr_tsdf_ray_view* views, int32_t num_views, int32_t height, int32_t width, float t_min, float t_max,
+                              float step, void* stream);
+
 /* ---- input pipeline: KittiOdometryDataset.preprocess_image, kitti_odometry_dataset.py:120-134 ------
  *
  * img.crop(box) -> img.resize((W,H), Image.BILINEAR) -> float32 / 255 - .5 -> CHW (a 1-channel image is stacked 3x),

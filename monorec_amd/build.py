@@ -24,6 +24,7 @@ SOURCES = [
     ("tsdf_export.hip", ["-ffp-contract=off"]),        # depth / colour packing of save_frame_for_tsdf: the reference's roundings, one by one
     ("tsdf_fusion.hip", ["-ffp-contract=off"]),        # TSDF integration / surface extraction: the roundings of include/monorec_hip.h, one by one
     ("tsdf_sparse.hip", ["-ffp-contract=off"]),        # the block-sparse volume: the same roundings through csrc/tsdf_common.h
+    ("tsdf_sparse_render.hip", ["-ffp-contract=off"]), # its ray-cast: the dense render kernel's roundings through csrc/tsdf_render.h
     ("preprocess.hip", ["-ffp-contract=off"]),
     ("eltwise.hip", []),
     ("select.hip", ["-ffp-contract=off"]),          # median scaling: exact masked selection; stage-scaled metric sums

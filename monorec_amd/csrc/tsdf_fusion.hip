@@ -33,6 +33,7 @@
 
 #include "../../include/monorec_hip.h"
 #include "tsdf_common.h"                     // what the block-sparse volume (tsdf_sparse.hip) runs too: the voxel update, the edge masks, the planes
+#include "tsdf_render.h"                     // what its ray-cast (tsdf_sparse_render.hip) runs too: the ray, the cell, the clip, the pixel's outputs
 
 namespace {
 
@@ -525,7 +526,6 @@ namespace {
 
 constexpr int BRICK = MR_TSDF_BRICK;
 static_assert(BRICK % 4 == 0 && BRICK >= 4, "the four voxels of a thread of the skip-grid sweep share a brick");
-constexpr int MAX_SAMPLES = 1 << 20;
 
 struct SkipArgs {
     const float* tsdf;
@@ -576,15 +576,6 @@ __global__ __launch_bounds__(256) void tsdf_skip_grid_kernel(const SkipArgs a) {
                 a.bricks[((long long)(bz - dz) * a.bricks_y + (by - dy)) * a.bricks_x + (bx - dx)] = 1;
 }
 
-struct RayView {
-    float r[9];                                  // camera -> world rotation, row-major
-    float o[3];                                  // the camera centre in voxel units: (c - origin) * inv
-    float fx, fy, cx, cy;
-    float* depth;
-    float* normal;
-    uint8_t* colour;
-};
-
 struct RenderArgs {
     const float* tsdf;
     const float* weight;
@@ -598,36 +589,6 @@ struct RenderArgs {
     int h, w, tiles_x;
     RayView v[MR_TSDF_MAX_FRAMES];
 };
-
-__device__ __forceinline__ float lerp(float a, float b, float f) { return a + f * (b - a); }
-
-__device__ __forceinline__ float trilinear(const float c[8], float fx, float fy, float fz) {   // c[x + 2 y + 4 z]
-    const float y0 = lerp(lerp(c[0], c[1], fx), lerp(c[2], c[3], fx), fy);
-    const float y1 = lerp(lerp(c[4], c[5], fx), lerp(c[6], c[7], fx), fy);
-    return lerp(y0, y1, fz);
-}
-
-struct Cell {
-    float f[3];
-    int i[3];
-    bool inside;                                 // all 8 corners are voxels of the volume
-};
-
-__device__ __forceinline__ Cell cell_of(const RenderArgs& a, const float o[3], const float e[3], int k) {
-    const float t = a.t_min + (float)k * a.step;
-    Cell c;
-    c.inside = true;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const float g = o[q] + t * e[q];
-        const float fl = floorf(g);
-        c.f[q] = g - fl;
-        const bool in = fl >= 0.0f && fl <= a.lim[q];                      // NaN: outside
-        c.inside = c.inside && in;
-        c.i[q] = in ? (int)fl : 0;
-    }
-    return c;
-}
 
 // the 8 corner tsdf of an inside cell into T; false when a corner's weight is not above min_weight
 __device__ __forceinline__ bool corners_of(const RenderArgs& a, const Cell& c, float T[8], long long& base) {
@@ -652,36 +613,10 @@ __global__ __launch_bounds__(256) void tsdf_render_kernel(const RenderArgs a) {
     const int v = (blockIdx.x / a.tiles_x) * 16 + (wave >> 1) * 8 + (lane >> 3);
     if (u >= a.w || v >= a.h) return;
     const RayView& view = a.v[blockIdx.z];
-    const float rx = ((float)u - view.cx) / view.fx, ry = ((float)v - view.cy) / view.fy;
     float o[3], e[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        o[q] = view.o[q];
-        e[q] = ((view.r[3 * q] * rx + view.r[3 * q + 1] * ry) + view.r[3 * q + 2]) * a.inv;
-    }
-
-    // Clip to the box 0 <= g_a <= n_a in t, then in k.  Only an optimisation, so it only has to be conservative: no sample outside
-    // [k_lo, k_hi] may be valid.  The crossing times t_a = (bound - o_a) / e_a are a few ulp of max(|t_a|) off, and so is the t at which
-    // the fp32 g_a = o_a + t_k * e_a crosses the bound (|o_a| / |e_a| is one of the two |t_a|); the range is widened by 1e-5 of the
-    // larger |t_a| (more than 80 ulp) and by one step, and the k range by one more sample for the roundings of (t - t_min) / step and of
-    // (float)k * step (k < 2^20: 0.07 of a sample each).  fmaxf / fminf drop a NaN, which leaves the range as it was.
-    float t_lo = a.t_min, t_hi = a.t_min + (float)a.last * a.step;
-    bool empty = false;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const float top = a.lim[q] + 2.0f;                                  // n_a (or just below): beyond the last valid g_a
-        if (e[q] == 0.0f) {
-            empty = empty || !(o[q] >= 0.0f && o[q] <= top);                // g_a = o_a all along the ray
-            continue;
-        }
-        const float ta = (0.0f - o[q]) / e[q], tb = (top - o[q]) / e[q];
-        const float slack = 1e-5f * fmaxf(fabsf(ta), fabsf(tb)) + a.step;
-        t_lo = fmaxf(t_lo, fminf(ta, tb) - slack);
-        t_hi = fminf(t_hi, fmaxf(ta, tb) + slack);
-    }
-    int k_lo = (int)fminf(fmaxf(floorf((t_lo - a.t_min) / a.step) - 1.0f, 0.0f), (float)a.last + 1.0f);
-    int k_hi = (int)fminf(fmaxf(ceilf((t_hi - a.t_min) / a.step) + 1.0f, -1.0f), (float)a.last);
-    if (empty) k_hi = -1;
+    ray_of_pixel(a, view, u, v, o, e);
+    int k_lo, k_hi;
+    clip_to_box(a, o, e, k_lo, k_hi);
 
     // prev: 0 not valid, 1 valid with F_prev, 2 skipped (in a brick of byte 0: not valid, or valid and not negative - evaluated in full
     // before the next sample that is)
@@ -712,39 +647,12 @@ __global__ __launch_bounds__(256) void tsdf_render_kernel(const RenderArgs a) {
         F_prev = F;
     }
 
-    const long long pix = (long long)v * a.w + u;
-    float depth = 0.0f, n[3] = {0.0f, 0.0f, 0.0f};
-    unsigned rgb[3] = {0u, 0u, 0u};
-    if (hit_k >= 0) {
-        const float s = F_prev / (F_prev - F_hit);
-        depth = (a.t_min + (float)(hit_k - 1) * a.step) + s * a.step;
-        if (view.normal) {
-            const float gx = lerp(lerp(T[1] - T[0], T[3] - T[2], f[1]), lerp(T[5] - T[4], T[7] - T[6], f[1]), f[2]);
-            const float gy = lerp(lerp(T[2] - T[0], T[3] - T[1], f[0]), lerp(T[6] - T[4], T[7] - T[5], f[0]), f[2]);
-            const float gz = lerp(lerp(T[4] - T[0], T[5] - T[1], f[0]), lerp(T[6] - T[2], T[7] - T[3], f[0]), f[1]);
-            const float len = sqrtf((gx * gx + gy * gy) + gz * gz);
-            if (len > 0.0f) { n[0] = gx / len; n[1] = gy / len; n[2] = gz / len; }
-        }
-        if (view.colour && a.colour) {
-            const long long plane = (long long)a.nx * a.ny;
-            unsigned C[8];
+    write_pixel(a, view, u, v, hit_k, F_prev, F_hit, T, f, a.colour != nullptr, [&](unsigned C[8]) {
+        const long long plane = (long long)a.nx * a.ny;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) C[j] = a.colour[base + (j & 1) + ((j >> 1) & 1) * (long long)a.nx + (j >> 2) * plane];
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                float B[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) B[j] = (float)((C[j] >> (8 * ch)) & 0xffu);
-                rgb[ch] = (unsigned)fminf(255.0f, floorf(trilinear(B, f[0], f[1], f[2]) + 0.5f));
-            }
-        }
-    }
-    view.depth[pix] = depth;
-    if (view.normal) { float* o3 = view.normal + pix * 3; o3[0] = n[0]; o3[1] = n[1]; o3[2] = n[2]; }
-    if (view.colour) { uint8_t* c3 = view.colour + pix * 3; c3[0] = (uint8_t)rgb[0]; c3[1] = (uint8_t)rgb[1]; c3[2] = (uint8_t)rgb[2]; }
+        for (int j = 0; j < 8; ++j) C[j] = a.colour[base + (j & 1) + ((j >> 1) & 1) * (long long)a.nx + (j >> 2) * plane];
+    });
 }
-
-float t_of(float t_min, float step, long long k) { return t_min + (float)k * step; }
 
 }  // namespace
 
@@ -767,45 +675,17 @@ extern "C" int mr_tsdf_render_f32(const float* tsdf, const float* weight, const 
                                   const float* origin, float voxel_size, float min_weight, const uint8_t* bricks,
                                   const mr_tsdf_ray_view* views, int32_t num_views, int32_t height, int32_t width, float t_min, float t_max,
                                   float step, void* stream) {
-    if (bad_volume(tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight) || !views) return MR_ERR_BAD_ARGUMENT;
-    if (num_views < 1 || num_views > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return MR_ERR_BAD_ARGUMENT;
-    if (!(step > 0.0f) || !(t_min >= 0.0f) || !(t_max >= t_min) || !isfinite(t_min) || !isfinite(t_max)) return MR_ERR_BAD_ARGUMENT;
-    for (int i = 0; i < num_views; ++i) {
-        const mr_tsdf_ray_view& s = views[i];
-        if (!s.depth || (((uintptr_t)s.depth | (uintptr_t)s.normal) & 3)) return MR_ERR_BAD_ARGUMENT;
-        if (s.fx == 0.0f || s.fy == 0.0f || s.fx != s.fx || s.fy != s.fy) return MR_ERR_BAD_ARGUMENT;
-    }
-    // the last k with t_k <= t_max, t_k as the kernel rounds it (non-decreasing in k): an estimate in double, then stepped into place
-    const double estimate = floor(((double)t_max - (double)t_min) / (double)step);
-    if (!(estimate < (double)MAX_SAMPLES + 2.0)) return MR_ERR_BAD_ARGUMENT;
-    long long last = (long long)estimate;
-    while (last > 0 && t_of(t_min, step, last) > t_max) --last;
-    while (last + 1 <= MAX_SAMPLES && t_of(t_min, step, last + 1) <= t_max) ++last;
-    if (last + 1 > MAX_SAMPLES) return MR_ERR_BAD_ARGUMENT;
+    if (bad_volume(tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight)) return MR_ERR_BAD_ARGUMENT;
+    if (bad_ray_views(views, num_views, height, width, t_min, t_max, step)) return MR_ERR_BAD_ARGUMENT;
+    const long long last = last_sample(t_min, t_max, step);
+    if (last < 0) return MR_ERR_BAD_ARGUMENT;
     RenderArgs a;
     a.tsdf = tsdf; a.weight = weight; a.colour = reinterpret_cast<const unsigned*>(colour); a.bricks = bricks;
     a.nx = nx; a.ny = ny; a.nz = nz;
     a.bricks_x = (nx + BRICK - 1) / BRICK; a.bricks_y = (ny + BRICK - 1) / BRICK;
     const int dims[3] = {nx, ny, nz};
-    for (int q = 0; q < 3; ++q) {
-        float lim = (float)(dims[q] - 2);                                   // -1 for a single layer of voxels: no cell, no valid sample
-        if ((double)lim > (double)(dims[q] - 2)) lim = nextafterf(lim, 0.0f);
-        a.lim[q] = lim;
-    }
-    a.inv = 1.0f / voxel_size; a.min_weight = min_weight; a.t_min = t_min; a.step = step; a.last = (int)last;
-    a.h = height; a.w = width; a.tiles_x = (width + 15) / 16;
-    const long long tiles = (long long)a.tiles_x * ((height + 15) / 16);
-    if (tiles > 0x7fffffffLL) return MR_ERR_BAD_ARGUMENT;
-    for (int i = 0; i < MR_TSDF_MAX_FRAMES; ++i) {
-        const mr_tsdf_ray_view& s = views[i < num_views ? i : 0];
-        RayView& d = a.v[i];
-        for (int q = 0; q < 3; ++q) {
-            for (int j = 0; j < 3; ++j) d.r[3 * q + j] = s.m[4 * q + j];
-            d.o[q] = (s.m[4 * q + 3] - origin[q]) * a.inv;
-        }
-        d.fx = s.fx; d.fy = s.fy; d.cx = s.cx; d.cy = s.cy;
-        d.depth = s.depth; d.normal = s.normal; d.colour = s.colour;
-    }
-    hipLaunchKernelGGL(tsdf_render_kernel, dim3((unsigned)tiles, 1, (unsigned)num_views), dim3(256), 0, (hipStream_t)stream, a);
+    const unsigned tiles = prepare_march(a, dims, origin, voxel_size, min_weight, t_min, step, last, height, width, views, num_views);
+    if (!tiles) return MR_ERR_BAD_ARGUMENT;
+    hipLaunchKernelGGL(tsdf_render_kernel, dim3(tiles, 1, (unsigned)num_views), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }

@@ -26,8 +26,10 @@ and changes no bit of the result; header and tests/tsdf_render_ref.py as above. 
 `SparseTSDFVolume` is the same volume for scenes whose dense grid does not fit (200 m x 200 m x 40 m of road at 0.1 m are 19 GB): a
 direct-indexed table of blocks of 8^3 voxels and a pool that holds only the blocks some keyframe put within the truncation band of a
 surface (`mr_tsdf_sparse_integrate_f32`, the dense kernel's arithmetic through csrc/tsdf_common.h).  It has the integrate methods and
-`extract` / `count` / `save_ply` (`mr_tsdf_sparse_extract_f32`) of `TSDFVolume`; `to_dense()` (`mr_tsdf_sparse_gather_f32`) hands any
-region that fits to the dense class for `mesh()`, `render()` and `score()`.  The runner key `sparse_volume` selects it.
+`extract` / `count` / `save_ply` (`mr_tsdf_sparse_extract_f32`) and `render` / `render_result` (`mr_tsdf_sparse_render_f32`: the dense
+march through the table, bit for bit the render of the gathered volume) of `TSDFVolume`; `to_dense()` (`mr_tsdf_sparse_gather_f32`) hands
+any region that fits to the dense class for `mesh()`.  The runner key `sparse_volume` selects it, `sparse_render` renders and scores it
+without the dense copy.
 
 `run(config)` takes the configs of `pointcloud.run` / `tsdf_export.run` and drives the same pipelined loop
 (`tsdf_export.KeyframeStream`): per keyframe one pack launch into a staging slot on the device, per `fuse_batch` keyframes one
@@ -35,8 +37,8 @@ integrate launch on the same stream; nothing is copied to the host before the su
 `Fusion.score()` renders the fused volume into every exported keyframe again and scores it against the dataset's targets; with
 `render_dir`, `write()` also writes those views as 16-bit centimetre PNGs and JPEGs.
 
-Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; a native mesh or ray-cast of the sparse volume
-(they go through `to_dense()`), growth of its pool, eviction or hashing; a cap on the weight; fusing across ranks (`run` is single-process)."""
+Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; a native mesh of the sparse volume
+(it goes through `to_dense()`), growth of its pool, eviction or hashing; a cap on the weight; fusing across ranks (`run` is single-process)."""
 import contextlib
 import ctypes
 import functools
@@ -55,6 +57,7 @@ MAX_FRAMES = _lib.MR_TSDF_MAX_FRAMES          # keyframes per integrate launch
 TILE = _lib.MR_TSDF_TILE                      # (x, y, z) voxels of one workgroup of the integrate kernel: the unit of its frustum culling
 BLOCK = _lib.MR_TSDF_BLOCK                    # edge of one block of `SparseTSDFVolume` in voxels
 BRICK = _lib.MR_TSDF_BRICK                    # edge of one brick of `TSDFVolume.skip_grid` in voxels
+MAX_RENDER_SAMPLES = 1 << 20                  # samples per ray of one render launch
 
 
 _need_cuda = functools.partial(_lib.need_cuda, "tsdf_fusion")
@@ -133,8 +136,10 @@ def volume_bytes(dims, colour=True):
 # ------------------------------------------------------------------------------------------ the volume
 class _Volume:
     """What `TSDFVolume` and `SparseTSDFVolume` share: the geometry of the constructor, the host half of the integration (checks, pose
-    inverse, `mr_tsdf_view` arrays) and the count-then-fill protocol of the surface points.  A subclass has `_integrate_launch` (one
-    launch of its integrate entry) and `_extract_launch` (one launch of its extract entry and the read of the cursor)."""
+    inverse, `mr_tsdf_view` arrays), the count-then-fill protocol of the surface points and the host half of the ray-cast (poses,
+    intrinsics, `mr_tsdf_ray_view` arrays, outputs, the defaults of the range).  A subclass has `_integrate_launch` (one
+    launch of its integrate entry), `_extract_launch` (one launch of its extract entry and the read of the cursor), `_render_shared`
+    (what the launches of one `render` call share, made before the first) and `_render_launch` (one launch of its render entry)."""
 
     def _geometry(self, bounds, voxel_size, trunc, origin, dims):
         """Sets dims, origin, voxel_size and trunc as the entries will see them (fp32); returns voxel_size as given."""
@@ -248,6 +253,55 @@ class _Volume:
         records = self.extract(min_weight).cpu().numpy()
         _write(file, write_ply, records.reshape(-1))
         return records.shape[0]
+
+    # -- the volume seen from a camera
+    def render(self, cam_to_world, intrinsics, height, width, t_min=0.0, t_max=None, step=None, min_weight=0, normals=True, colour=True,
+               skip=True):
+        """Ray-cast the volume into one camera or a batch: cam_to_world (4, 4) / (B, 4, 4) anywhere, intrinsics one 3 x 3 / 4 x 4 matrix
+        or one per pose, images of height x width.  Every ray is sampled at camera-z depths t_min, t_min + step, ... <= t_max metres
+        (`step` defaults to the voxel size, `t_max` to t_min plus the volume's diagonal) and ends at the first crossing from
+        non-negative to negative tsdf between two samples whose 8 corners all have weight > min_weight (`mr_tsdf_render_f32`,
+        `mr_tsdf_sparse_render_f32`; the arithmetic is in include/monorec_hip.h).  Launches of at most 8 views on the current stream.
+        Returns dict(depth (B, h, w) fp32 metres, 0 where nothing was hit, normal (B, h, w, 3) fp32 unit vectors in world axes pointing
+        out of the surface | None, colour (B, h, w, 3) uint8 | None) on the device.  `skip`: `TSDFVolume` marches with
+        `skip_grid(min_weight)`, which changes no bit of the result; `SparseTSDFVolume` accepts and ignores it (a sample in a block
+        without storage costs one table entry as it is)."""
+        poses, ks, b = _host_batches(cam_to_world, intrinsics)
+        height, width = int(height), int(width)
+        if b < 1 or ks.shape[0] not in (1, b):
+            raise ValueError(f"render: {b} poses, {ks.shape[0]} intrinsics (one, or one per pose)")
+        if height < 1 or width < 1:
+            raise ValueError(f"render: an image of {height} x {width}")
+        t_min = float(t_min)
+        step = self.voxel_size if step is None else float(step)
+        if t_max is None:
+            t_max = t_min + self.voxel_size * math.sqrt(sum(d * d for d in self.dims))
+        march = (t_min, float(t_max), step)
+        shared = self._render_shared(march, min_weight, skip)
+        depth = torch.empty(b, height, width, dtype=torch.float32, device=self.device)
+        normal = torch.empty(b, height, width, 3, dtype=torch.float32, device=self.device) if normals else None
+        image = torch.empty(b, height, width, 3, dtype=torch.uint8, device=self.device) if colour else None
+        views = []
+        for i in range(b):
+            view = _lib.TsdfRayView()
+            view.m[:] = [float(v) for v in poses[i][:3, :4].reshape(-1)]
+            _set_intrinsics(view, ks[i if ks.shape[0] == b else 0])
+            view.depth = depth[i].data_ptr()
+            view.normal = normal[i].data_ptr() if normals else None
+            view.colour = image[i].data_ptr() if colour else None
+            views.append(view)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            for lo in range(0, b, MAX_FRAMES):
+                chunk = views[lo:lo + MAX_FRAMES]
+                self._render_launch(lib, (_lib.TsdfRayView * len(chunk))(*chunk), (height, width), march, float(min_weight), shared)
+        return dict(depth=depth, normal=normal, colour=image)
+
+    def render_result(self, cam_to_world, intrinsics, height, width, **kwargs):
+        """The rendered depth in the model's `result` convention: (B, 1, h, w) inverse depth, 0 where nothing was hit - what
+        `metrics.*_sparse_onlyvalid_metric` (`pred_all_valid=False`) scores.  Keywords as `render` (normals and colour are not rendered)."""
+        depth = self.render(cam_to_world, intrinsics, height, width, **dict(kwargs, normals=False, colour=False))["depth"]
+        return torch.where(depth > 0, 1.0 / depth, torch.zeros_like(depth)).unsqueeze(1)
 
 
 class TSDFVolume(_Volume):
@@ -383,53 +437,12 @@ class TSDFVolume(_Volume):
     def drop_skip_grids(self):
         self._skip = {}
 
-    def render(self, cam_to_world, intrinsics, height, width, t_min=0.0, t_max=None, step=None, min_weight=0, normals=True, colour=True,
-               skip=True):
-        """Ray-cast the volume into one camera or a batch: cam_to_world (4, 4) / (B, 4, 4) anywhere, intrinsics one 3 x 3 / 4 x 4 matrix
-        or one per pose, images of height x width.  Every ray is sampled at camera-z depths t_min, t_min + step, ... <= t_max metres
-        (`step` defaults to the voxel size, `t_max` to t_min plus the volume's diagonal) and ends at the first crossing from
-        non-negative to negative tsdf between two samples whose 8 corners all have weight > min_weight (`mr_tsdf_render_f32`; the
-        arithmetic is in include/monorec_hip.h).  Launches of at most 8 views on the current stream.  Returns
-        dict(depth (B, h, w) fp32 metres, 0 where nothing was hit, normal (B, h, w, 3) fp32 unit vectors in world axes pointing out
-        of the surface | None, colour (B, h, w, 3) uint8 | None) on the device.  `skip`: march with `skip_grid(min_weight)`, which
-        changes no bit of the result."""
-        poses, ks, b = _host_batches(cam_to_world, intrinsics)
-        height, width = int(height), int(width)
-        if b < 1 or ks.shape[0] not in (1, b):
-            raise ValueError(f"render: {b} poses, {ks.shape[0]} intrinsics (one, or one per pose)")
-        if height < 1 or width < 1:
-            raise ValueError(f"render: an image of {height} x {width}")
-        t_min = float(t_min)
-        step = self.voxel_size if step is None else float(step)
-        if t_max is None:
-            t_max = t_min + self.voxel_size * math.sqrt(sum(d * d for d in self.dims))
-        depth = torch.empty(b, height, width, dtype=torch.float32, device=self.device)
-        normal = torch.empty(b, height, width, 3, dtype=torch.float32, device=self.device) if normals else None
-        image = torch.empty(b, height, width, 3, dtype=torch.uint8, device=self.device) if colour else None
-        views = []
-        for i in range(b):
-            view = _lib.TsdfRayView()
-            view.m[:] = [float(v) for v in poses[i][:3, :4].reshape(-1)]
-            _set_intrinsics(view, ks[i if ks.shape[0] == b else 0])
-            view.depth = depth[i].data_ptr()
-            view.normal = normal[i].data_ptr() if normals else None
-            view.colour = image[i].data_ptr() if colour else None
-            views.append(view)
-        bricks = self.skip_grid(min_weight).data_ptr() if skip else None
-        lib = _lib.load()
-        with torch.cuda.device(self.device):
-            for lo in range(0, b, MAX_FRAMES):
-                chunk = views[lo:lo + MAX_FRAMES]
-                _lib.check(lib.mr_tsdf_render_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), bricks,
-                                                  (_lib.TsdfRayView * len(chunk))(*chunk), len(chunk), height, width, t_min, float(t_max), step,
-                                                  self._stream()), "mr_tsdf_render_f32")
-        return dict(depth=depth, normal=normal, colour=image)
+    def _render_shared(self, march, min_weight, skip):
+        return self.skip_grid(min_weight).data_ptr() if skip else None            # the bricks
 
-    def render_result(self, cam_to_world, intrinsics, height, width, **kwargs):
-        """The rendered depth in the model's `result` convention: (B, 1, h, w) inverse depth, 0 where nothing was hit - what
-        `metrics.*_sparse_onlyvalid_metric` (`pred_all_valid=False`) scores.  Keywords as `render` (normals and colour are not rendered)."""
-        depth = self.render(cam_to_world, intrinsics, height, width, **dict(kwargs, normals=False, colour=False))["depth"]
-        return torch.where(depth > 0, 1.0 / depth, torch.zeros_like(depth)).unsqueeze(1)
+    def _render_launch(self, lib, array, size, march, min_weight, bricks):
+        _lib.check(lib.mr_tsdf_render_f32(*self._volume_args(), self._origin, self.voxel_size, min_weight, bricks, array, len(array), *size,
+                                          *march, self._stream()), "mr_tsdf_render_f32")
 
     # -- the volume itself
     def grids(self):
@@ -483,8 +496,11 @@ class SparseTSDFVolume(_Volume):
     voxels have a lower weight than in a dense volume, and a crossing into a block that was never in a band is gone), that of earlier
     frames of the same launch is kept; which slot a block gets is unspecified, everything else is deterministic.  A pool that runs out
     drops the blocks that found no room: `overflowed()` tells, nothing is written out of bounds.
-    `extract` / `count` / `save_ply` work on the sparse volume itself (`mr_tsdf_sparse_extract_f32`); `to_dense()` gathers any region that
-    fits into a `TSDFVolume` for `mesh()`, `render()` and the rest."""
+    `extract` / `count` / `save_ply` (`mr_tsdf_sparse_extract_f32`) and `render` / `render_result` (`mr_tsdf_sparse_render_f32`) work on
+    the sparse volume itself.  `render` has `TSDFVolume.render`'s signature and returns, bit for bit, what `to_dense(bounds).render` would:
+    a block without storage is unseen (tsdf 1, weight 0, colour 0), which costs a ray one table entry per sample; `skip` is accepted and
+    ignored.  It reads the cursor once per call, and a range of more than 2^20 samples per ray raises a ValueError.
+    `to_dense()` gathers any region that fits into a `TSDFVolume`; only `mesh()` needs it."""
 
     def __init__(self, bounds=None, voxel_size=0.1, trunc=None, colour=True, device="cuda:0", max_bytes=8 << 30, origin=None, dims=None,
                  capacity_blocks=None):
@@ -563,6 +579,19 @@ class SparseTSDFVolume(_Volume):
                                                               self.voxel_size, float(min_weight), *out, cursor.data_ptr(), self._stream()),
                        "mr_tsdf_sparse_extract_f32")
         return int(cursor.item())
+
+    # -- the volume seen from a camera
+    def _render_shared(self, march, min_weight, skip):
+        """The range checked here, where the message can name its keywords, and the slots in use: one read of the cursor per call."""
+        t_min, t_max, step = march
+        if step > 0 and np.float32(t_min) + np.float32(MAX_RENDER_SAMPLES) * np.float32(step) <= np.float32(t_max):     # sample 2^20 exists
+            raise ValueError(f"SparseTSDFVolume.render: t_max = {t_max:g} and step = {step:g} from t_min = {t_min:g} are more than 2^20 samples "
+                             f"per ray; lower t_max or raise step")
+        return self.allocated_blocks()                                            # `skip`: accepted and ignored, the table is the skip grid
+
+    def _render_launch(self, lib, array, size, march, min_weight, num_slots):
+        _lib.check(lib.mr_tsdf_sparse_render_f32(*self._table_args(), num_slots, self._origin, self.voxel_size, min_weight, array, len(array), *size,
+                                                 *march, self._stream()), "mr_tsdf_sparse_render_f32")
 
     # -- dense views of it
     def allocated_box(self):
@@ -759,12 +788,24 @@ def sparse_setting(config):
     return sparse
 
 
+def sparse_render_setting(config):
+    """The runner key `sparse_render` (default false), checked: with `sparse_volume`, render and score the sparse volume itself
+    (`SparseTSDFVolume.render`) and not the whole of it gathered into a dense one."""
+    native = config.get("sparse_render", False)
+    if not isinstance(native, bool):
+        raise ValueError(f"monorec_amd.tsdf_fusion: sparse_render {native!r} must be true or false")
+    if native and not sparse_setting(config):
+        raise ValueError("monorec_amd.tsdf_fusion: sparse_render needs sparse_volume: true (a dense volume is rendered as it is)")
+    return native
+
+
 class Fusion:
     """The stages of `run`, for callers that want them apart (tools/bench_tsdf_fusion.py times them): the constructor builds model,
     dataset and volume, `fuse()` drives the keyframe loop, `write()` extracts and saves."""
 
     def __init__(self, config, model=None, dataset=None, device="cuda:0"):
         self.config, self.settings, self.sparse = config, fusion_settings(config), sparse_setting(config)
+        self.sparse_render = sparse_render_setting(config)
         settings = self.settings
         if settings["bounds"] is not None:
             self._check_dense_outputs(settings["bounds"])         # before the model is built
@@ -785,16 +826,16 @@ class Fusion:
             self._check_dense_outputs(bounds)
         self.volume = (SparseTSDFVolume if self.sparse else TSDFVolume)(bounds, settings["voxel_size"], trunc=settings["trunc"], colour=True,
                                                                         device=stream.device, max_bytes=settings["max_bytes"])
-        self._dense = None                                     # the sparse volume gathered for mesh, renders and score, once asked for
+        self._dense = None                                     # the sparse volume gathered for the mesh (renders and score), once asked for
         depth_bytes, colour_bytes = tx.packed_sizes(1, ch, cw)
         self._slots = [torch.empty(depth_bytes + colour_bytes, dtype=torch.uint8, device=stream.device) for _ in range(settings["fuse_batch"])]
         self.mesh_counts = None                                # (vertices, triangles) of the mesh file, once `write()` has written one
 
     def _check_dense_outputs(self, bounds):
-        """With `sparse_volume`, the mesh, the renders and the score work on the whole volume gathered into a dense one, which must fit
-        `tsdf_max_bytes` too: a ValueError that names the keys before anything is fused."""
+        """With `sparse_volume`, the mesh - and without `sparse_render` the renders and the score - work on the whole volume gathered into
+        a dense one, which must fit `tsdf_max_bytes` too: a ValueError that names the keys before anything is fused."""
         settings = self.settings
-        asked = [key for key in ("mesh_file_name", "render_dir", "fused_metrics") if settings[key]]
+        asked = [key for key in (("mesh_file_name",) if self.sparse_render else ("mesh_file_name", "render_dir", "fused_metrics")) if settings[key]]
         if not self.sparse or not asked:
             return
         dims = tuple((d + BLOCK - 1) // BLOCK * BLOCK for d in dims_of_bounds(bounds, settings["voxel_size"]))
@@ -804,13 +845,17 @@ class Fusion:
                              f"{settings['max_bytes'] / 2 ** 30:.2f} GiB; raise tsdf_max_bytes, or write the points alone (file_name)")
 
     def dense(self):
-        """The volume `mesh()`, `render()` and `score()` work on: the volume itself, or the whole sparse one gathered (`to_dense`, once)."""
+        """The volume `mesh()` works on: the volume itself, or the whole sparse one gathered (`to_dense`, once)."""
         if not self.sparse:
             return self.volume
         if self._dense is None:
             self._check_dense_outputs(self.volume.bounds)
             self._dense = self.volume.to_dense(self.volume.bounds, max_bytes=self.settings["max_bytes"])
         return self._dense
+
+    def rendered(self):
+        """The volume `score()` and `write_renders()` render: `dense()`, or with `sparse_render` the sparse volume itself."""
+        return self.volume if self.sparse_render else self.dense()
 
     def shifted(self, k):
         """The intrinsics of the cropped image, as `save_intrinsics_for_tsdf` shifts them, on a copy."""
@@ -870,7 +915,7 @@ class Fusion:
         `max_distance`: as the metric functions take them.  Returns dict(metrics {name: value} - each what the metric function of that
         name returns for all samples as one batch -, coverage: the share of target pixels the render hit, samples)."""
         from . import metrics
-        stream, volume = self.stream, self.dense()
+        stream, volume = self.stream, self.rendered()
         items = stream.export_items()
         height, width = stream.height, stream.width
         sums, hit, have = [], torch.zeros((), dtype=torch.int64, device=volume.device), torch.zeros((), dtype=torch.int64, device=volume.device)
@@ -895,7 +940,7 @@ class Fusion:
         intrinsics, `frame-%06d.fused.depth.png` (16 bit, centimetres, 0: nothing) and `frame-%06d.fused.color.jpg`, names that sort
         next to the export's.  After the fusion and synchronous: not a stage of the loop.  Returns the number of keyframes."""
         from PIL import Image
-        stream, volume = self.stream, self.dense()
+        stream, volume = self.stream, self.rendered()
         os.makedirs(str(directory), exist_ok=True)
         items = stream.export_items()
         y0, y1, x0, x1 = tx.crop_box(stream.crop, stream.height, stream.width)
@@ -926,7 +971,9 @@ def run(config, model=None, dataset=None, device="cuda:0"):
     `render_dir` (a directory for `Fusion.write_renders`), `fused_metrics` (names for `Fusion.score()`; `main` prints its result),
     `sparse_volume` (false; true: fuse into a `SparseTSDFVolume` over the same bounds with `tsdf_max_bytes` as the budget of table and pool -
     points and `save_volume` come from it, mesh, renders and score from the whole of it gathered into a dense volume, which must fit
-    `tsdf_max_bytes` as well; a pool that ran out raises after the loop).
+    `tsdf_max_bytes` as well; a pool that ran out raises after the loop), `sparse_render` (false; true, with `sparse_volume` only: renders and
+    score come from the sparse volume itself, `SparseTSDFVolume.render` - the same bits without the dense copy, so only `mesh_file_name` still
+    asks for room for one).
 
     Per keyframe `pack_frames` (vote, crop, thresholds: the depths are exactly the ones the export writes to the PNG) fills a staging slot
     on the device; after `fuse_batch` keyframes, or at the end, one integrate launch follows on the same stream.  Every keyframe is
