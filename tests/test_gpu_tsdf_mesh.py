@@ -72,7 +72,8 @@ def _mesh(volume, min_weight=0):
 @pytest.mark.parametrize("colour", [True, False], ids=["colour", "plain"])
 @pytest.mark.parametrize("name", ["closed", "hole"])
 def test_sphere_equals_the_restatement_and_is_welded(hip_lib, name, colour):
-    """41 x 19 x 21: two tiles along x, three along y, six along z - vertices and triangles of one surface come from many workgroups."""
+    """41 x 19 x 21: three tiles along y, six along z - vertices and triangles of one surface come from many workgroups.  The sphere spans
+    x = 14 .. 29 and does not touch the seam x = 31 | 32; section 7 is about the seams."""
     vol = _analytic(name, colour)
     want, canonical = _want("analytic", name, colour, 0)
     vertices, triangles = _mesh(_load(vol))
@@ -146,9 +147,8 @@ def test_no_sign_change_means_empty_tensors_and_no_fill_launch(hip_lib):
 
 
 # ------------------------------------------------------------------------------------------ 4. capacity
-def test_a_capacity_below_the_count_writes_nothing_beyond_it(hip_lib):
-    vol = _analytic("closed", True)
-    want, _ = _want("analytic", "closed", True, 0)
+def _fill_with_a_third_of_the_capacity(vol, want):
+    """The two entries called directly with sentinel-filled outputs and capacities of a third of the counts."""
     n, m = len(want["vertices"]), len(want["triangles"])
     volume = _load(vol)
     lib, stream = _lib.load(), torch.cuda.current_stream().cuda_stream
@@ -171,6 +171,18 @@ def test_a_capacity_below_the_count_writes_nothing_beyond_it(hip_lib):
     # the records below the capacity are vertices of the mesh
     records = {r.tobytes() for r in want["vertices"]}
     assert all(r.tobytes() in records for r in vertices[:cap_v].cpu().numpy())
+
+
+def test_a_capacity_below_the_count_writes_nothing_beyond_it(hip_lib):
+    _fill_with_a_third_of_the_capacity(_analytic("closed", True), _want("analytic", "closed", True, 0)[0])
+
+
+def test_a_capacity_below_the_count_on_a_noise_volume(hip_lib):
+    """The same where nearly every voxel owns vertices and every tile's triangles reach into the next: 65 x 17 x 9."""
+    vol = mref.noise_volume(ref.SEAM_DIMS[2], seed=1)
+    want = mref.mesh(vol)
+    assert (want["masks"] != 0).mean() > 0.5 and (want["masks"] == 0).sum() > 100
+    _fill_with_a_third_of_the_capacity(vol, want)
 
 
 # ------------------------------------------------------------------------------------------ 5. the file
@@ -213,3 +225,40 @@ def test_runner_writes_the_mesh_next_to_unchanged_points(hip_lib, tmp_path):
     want = mref.mesh(dict(dims=fusion.volume.dims, origin=tuple(np.float32(v) for v in fusion.volume.origin), voxel=np.float32(fusion.volume.voxel_size),
                           tsdf=tsdf, weight=weight, colour=colour))
     assert np.array_equal(mref.canonical(vertices, triangles), mref.canonical(want["vertices"], want["triangles"]))
+
+
+# ------------------------------------------------------------------------------------------ 7. vertices across tile seams
+def _equals_the_restatement(vol, min_weight=0):
+    """The device mesh of `vol` against the restatement through `mref.canonical`, exactly, and `extract` against its axis-edge vertices."""
+    want = mref.mesh(vol, min_weight)
+    volume = _load(vol)
+    vertices, triangles = _mesh(volume, min_weight)
+    assert vertices.shape == want["vertices"].shape and triangles.shape == want["triangles"].shape
+    assert np.array_equal(mref.canonical(vertices, triangles), mref.canonical(want["vertices"], want["triangles"]))
+    assert np.array_equal(ref.sort_records(volume.extract(min_weight).cpu().numpy()), ref.sort_records(mref.axis_vertices(want)))
+    return want
+
+
+@pytest.mark.parametrize("background", [1, -1], ids=["positive", "negative"])
+@pytest.mark.parametrize("axis,seam", [(axis, seam) for axis, tile in enumerate(mref.TILE) for seam in (tile, tile - 1)])
+def test_every_sign_pattern_of_a_cube_on_a_tile_seam(hip_lib, axis, seam, background):
+    """mref.pattern_volume: tests/test_tsdf_mesh.py shows that the twelve together put every (owner mask, edge type) pair on a vertex
+    whose owner lies in the next tile - 192 per axis, where the fixtures above reach 15 / 53 / 89."""
+    want = _equals_the_restatement(mref.pattern_volume(axis, seam, background))
+    assert len(want["triangles"]) > 20000
+
+
+@pytest.mark.parametrize("min_weight", [0, 1])
+@pytest.mark.parametrize("colour", [True, False], ids=["colour", "plain"])
+@pytest.mark.parametrize("dims", ref.SEAM_DIMS, ids=lambda d: "x".join(map(str, d)))
+def test_noise_volumes_equal_the_restatement(hip_lib, dims, colour, min_weight):
+    """Independent random signs, a tenth unseen, zeros of both signs, a tile and a bit along every axis."""
+    want = _equals_the_restatement(mref.noise_volume(dims, seed=1, colour=colour), min_weight)
+    assert len(want["triangles"]) > (900 if min_weight else 4000)
+
+
+@pytest.mark.parametrize("dims", ref.SEAM_DIMS, ids=lambda d: "x".join(map(str, d)))
+def test_seam_volumes_equal_the_restatement(hip_lib, dims):
+    """ref.seam_volume, built for `extract` to cross every tile seam and ragged end, as a mesh."""
+    for min_weight in (0, 1):
+        assert len(_equals_the_restatement(ref.seam_volume(dims), min_weight)["triangles"]) > 100

@@ -308,3 +308,58 @@ def test_score_equals_the_metric_functions_by_hand(hip_lib, tmp_path):
         assert png.shape == (56, 84) and np.array_equal(png, want) and png.any()
         with Image.open(tmp_path / "views" / f"frame-{n:06d}.fused.color.jpg") as img:
             assert img.size == (84, 56) and img.mode == "RGB"
+
+
+# ------------------------------------------------------------------------------------------ 6. where the clip to the box decides
+H, W = rref.CLIP_H, rref.CLIP_W
+
+
+@pytest.mark.parametrize("case", rref.CLIP_CASES, ids=[c["id"] for c in rref.CLIP_CASES])
+def test_clip_cases_equal_the_restatement(hip_lib, case):
+    """rref.CLIP_CASES: samples ON the faces of the box, rays parallel to them, origins on the box, thin volumes, far cameras, a t_max
+    that decides, poses that are no rotation (tests/test_tsdf_render.py proves on the CPU that an exact clip has nothing to spare in
+    them).  The restatement marches every sample, so equality bit for bit says the kernel's clip dropped none that mattered."""
+    vol, pose, k, (t_min, t_max, step) = rref.case_inputs(case)
+    want = rref.render(vol, pose, k, H, W, t_min, t_max, step)
+    volume = _load(vol)
+    for skip in (True, False):
+        views = volume.render(torch.from_numpy(pose), _k3(k), H, W, t_min=t_min, t_max=t_max, step=step, skip=skip)
+        _check(views, 0, want, f"{case['id']} skip={skip}")
+
+
+def test_a_pose_that_is_not_finite_in_a_batch(hip_lib):
+    """Three views in one launch, the middle pose with a NaN in its rotation and an inf in its translation: every sample of every ray of
+    it is outside (a NaN compares false), so it is all zero, as the restatement says; its neighbours are what they are alone."""
+    case = next(c for c in rref.CLIP_CASES if c["id"] == "1-enter-zlo")
+    vol, pose, k, (t_min, t_max, step) = rref.case_inputs(case)
+    other = next(c for c in rref.CLIP_CASES if c["id"] == "3-oblique-zlo")["pose"]
+    broken = pose.copy()
+    broken[0, 1], broken[1, 3] = np.nan, np.inf
+    volume = _load(vol)
+    for skip in (True, False):
+        march = dict(t_min=t_min, t_max=t_max, step=step, skip=skip)
+        views = volume.render(torch.from_numpy(np.stack([pose, broken, other])), _k3(k), H, W, **march)
+        for j, p in enumerate((pose, broken, other)):
+            want = rref.render(vol, p, k, H, W, t_min, t_max, step)
+            assert want["hit"].any() == (j != 1)
+            _check(views, j, want, f"view {j} skip={skip}")
+            if j != 1:
+                alone = volume.render(torch.from_numpy(p), _k3(k), H, W, **march)
+                for key in ("depth", "normal", "colour"):
+                    assert torch.equal(views[key][j], alone[key][0]), (key, j)
+        assert not bool(views["depth"][1].any()) and not bool(views["normal"][1].any()) and not bool(views["colour"][1].any())
+
+
+@pytest.mark.parametrize("case", [c for c in rref.CLIP_CASES if c["group"] == "noise"], ids=lambda c: c["id"])
+def test_bricks_of_a_volume_that_is_no_scene(hip_lib, case):
+    """One voxel in 200 negative, independent of its neighbours: the brick bytes equal the restatement's, and the march that skips and
+    the one that does not both equal the full march, for min_weight 0 and 1."""
+    vol, pose, k, (t_min, t_max, step) = rref.case_inputs(case)
+    volume = _load(vol)
+    for min_weight in (0, 1):
+        _same(volume.skip_grid(min_weight), rref.brick_flags(vol, min_weight), f"bricks min_weight {min_weight}")
+        want = rref.render(vol, pose, k, H, W, t_min, t_max, step, min_weight)
+        assert want["hit"].any()
+        for skip in (True, False):
+            views = volume.render(torch.from_numpy(pose), _k3(k), H, W, t_min=t_min, t_max=t_max, step=step, min_weight=min_weight, skip=skip)
+            _check(views, 0, want, f"{case['id']} min_weight {min_weight} skip={skip}")

@@ -319,3 +319,28 @@ def test_runner_renders_and_scores_the_sparse_volume_itself(tree, model, tmp_pat
                       model=model).fuse()
     assert tight.volume.capacity == allocated and tight.write() == count
     assert tight.score() == score_a and _files(str(tmp_path / "c" / "renders")) == files_a
+
+
+# ------------------------------------------------------------------------------------------ 7. where the clip to the box decides
+@pytest.mark.parametrize("case", rref.CLIP_CASES, ids=[c["id"] for c in rref.CLIP_CASES])
+def test_clip_cases_equal_the_restatement_and_the_dense_render(hip_lib, case):
+    """rref.CLIP_CASES (tests/test_gpu_tsdf_render.py has them on the dense volume) through the table: the case's volume rounded up to
+    whole blocks, with a pool that holds the blocks with a seen negative voxel and no other - the rest read as unseen.  The restatement
+    is of that volume.  The faces of the box are faces of blocks, and hits lie in cells that straddle blocks
+    (tests/test_tsdf_sparse_render.py counts them)."""
+    vol, pose, k, (t_min, t_max, step) = rref.case_inputs(case)
+    stands_for = sref.without_positive_blocks(vol)
+    coords, tsdf, weight, rgb = sref.blocks_of(stands_for)
+    volume = tf.SparseTSDFVolume(origin=stands_for["origin"], dims=stands_for["dims"], voxel_size=float(stands_for["voxel"]),
+                                 trunc=float(stands_for["trunc"]), device=DEV, capacity_blocks=len(coords))
+    volume.set_blocks(coords, tsdf, weight, rgb)
+    assert volume.dims == stands_for["dims"] and volume.allocated_blocks() == volume.capacity == len(coords) > 0
+    want = rref.render(stands_for, pose, k, rref.CLIP_H, rref.CLIP_W, t_min, t_max, step)
+    kmat = torch.tensor([[k[0], 0.0, k[2]], [0.0, k[1], k[3]], [0.0, 0.0, 1.0]])
+    march = dict(t_min=t_min, t_max=t_max, step=step)
+    views = volume.render(torch.from_numpy(pose), kmat, rref.CLIP_H, rref.CLIP_W, **march)
+    _check(views, 0, want, case["id"])
+    dense = volume.to_dense(volume.bounds)
+    assert dense.dims == volume.dims
+    for skip in (True, False):
+        assert _equal(views, dense.render(torch.from_numpy(pose), kmat, rref.CLIP_H, rref.CLIP_W, skip=skip, **march)), skip

@@ -171,3 +171,64 @@ def test_the_fused_volume_meshes_without_a_fin(fused, min_weight):
     assert len(got["triangles"]) > 0 and topo["repeated"] == [] and all(n <= 2 for _, _, n in topo["open"])
     assert np.array_equal(ref.sort_records(mref.axis_vertices(got)), ref.sort_records(ref.extract(fused, min_weight)))
     assert got["triangles"].max() < len(got["vertices"])
+
+
+# ------------------------------------------------------------------------------------------ vertices across tile seams
+def _older_fixtures():
+    """The volumes test_gpu_tsdf_mesh.py meshed before the pattern volumes: both spheres, both fused volumes at min_weight 0 and 2."""
+    sphere = mref.sphere_volume(**mref.SPHERE_VOLUME)
+    yield sphere, 0
+    yield mref.with_hole(sphere), 0
+    frames = ref.make_frames(ref.INTRINSICS_60)
+    for spec in (ref.SMALL, ref.WIDE):
+        vol = ref.new_volume(**spec)
+        for i in [0, 10, 1, 2, 3, 4, 5, 6, 7, 8, 9]:
+            pose, depth, image = frames[i]
+            ref.integrate(vol, ref.world_to_camera(pose), ref.INTRINSICS_60, depth, image)
+        yield vol, 0
+        yield vol, 2
+
+
+def _per_axis(pairs):
+    return [sum(1 for p in pairs if p[0] == axis) for axis in range(3)]
+
+
+def test_the_pattern_volumes_reach_every_mask_and_edge_type_across_every_seam():
+    """A triangle vertex whose owner lies in the next 32 x 8 x 4 tile is ranked with a mask from the second halo layer of the triangle
+    kernel's staged codes and offset by a vertex_base another workgroup wrote; a wrong rank there still gives indices in range.  Per
+    axis there are 192 (owner mask, edge type) pairs for such a vertex (mref.seam_pairs).  The spheres and fused volumes the GPU test
+    meshed before reach 15 / 53 / 89 of them across the x / y / z seams (the sphere spans x = 14 .. 29 and never touches x = 31 | 32);
+    the twelve pattern volumes - all 256 sign patterns of a cube whose base is the first voxel of the second tile, or the last of the
+    first, on a background of either sign - reach 192 / 192 / 192."""
+    older = set()
+    for vol, min_weight in _older_fixtures():
+        older |= mref.seam_pairs(vol, mref.mesh(vol, min_weight))
+    assert _per_axis(older) == [15, 53, 89]
+    for axis, tile in enumerate(mref.TILE):
+        reached = set()
+        for seam in (tile, tile - 1):
+            for background in (1, -1):
+                vol = mref.pattern_volume(axis, seam, background)
+                assert vol["dims"][axis] == seam + 3 and sorted(vol["dims"])[1:] == [49, 49] and np.prod(vol["dims"]) < 100000
+                assert (vol["weight"] > 0).all() and (np.abs(vol["tsdf"]) >= np.float32(0.05)).all()
+                got = mref.mesh(vol)
+                assert len(got["triangles"]) > 20000 and got["triangles"].max() < len(got["vertices"])
+                assert (got["cubes"] >= 0).all() and (got["cubes"] < np.array(vol["dims"]) - 1).all() and set(got["tets"]) == set(range(6))
+                reached |= {p for p in mref.seam_pairs(vol, got) if p[0] == axis}
+        assert len(reached) == mref.SEAM_PAIRS == 192, (axis, len(reached))
+        assert {(m, e) for _, m, e in reached} == {(m, e) for m in range(128) for e in range(7) if m >> e & 1 and not mref.EDGES[e][axis]}
+
+
+@pytest.mark.parametrize("dims", ref.SEAM_DIMS)
+def test_the_noise_volumes_mesh_with_indices_in_range(dims):
+    """Independent random signs, a tenth unseen, exact zeros of both signs: nearly every tetrahedron of every cube has a triangle."""
+    vol = mref.noise_volume(dims, seed=1)
+    assert ((vol["tsdf"] == 0) & np.signbit(vol["tsdf"])).sum() == 8 == ((vol["tsdf"] == 0) & ~np.signbit(vol["tsdf"])).sum()
+    assert 0.05 < (vol["weight"] == 0).mean() < 0.15 and set(np.unique(vol["weight"])) == {0.0, 1.0, 2.0, 3.0}
+    got = mref.mesh(vol)
+    assert len(got["triangles"]) > 1000 and got["triangles"].min() >= 0 and got["triangles"].max() < len(got["vertices"])
+    assert np.array_equal(ref.sort_records(mref.axis_vertices(got)), ref.sort_records(ref.extract(vol)))
+    # +0 and -0 are outside: next to a positive voxel along x they own no vertex on that edge, next to a seen negative one they do
+    zero, seen = (vol["tsdf"] == 0)[:, :, :-1], ((vol["weight"] > 0)[:, :, :-1] & (vol["weight"] > 0)[:, :, 1:])
+    owns = (got["masks"][:, :, :-1] & 1) != 0
+    assert zero.sum() > 8 and np.array_equal(owns[zero], (seen & (vol["tsdf"][:, :, 1:] < 0))[zero])

@@ -141,3 +141,28 @@ def test_the_views_of_the_gpu_cases_hit_the_scene_across_block_faces(name, block
         # every hit cell has its base in an allocated block (min_weight 0: corner i itself is seen)
         assert vol["allocated"][base[:, 2] >> 3, base[:, 1] >> 3, base[:, 0] >> 3].all()
     assert not _view(name, 10)["hit"].any()                                   # the pose that looks away
+
+
+def test_the_clip_cases_through_the_table():
+    """The volumes test_gpu_tsdf_sparse_render.py makes of rref.CLIP_CASES - whole blocks, storage only where a block holds a seen
+    negative voxel: `render_virtual` equals the dense restatement of what the table stands for, the face cases keep their hits
+    without the all-positive blocks, and hit cells straddle block faces."""
+    dropped = 0
+    for case in rref.CLIP_CASES:
+        vol, pose, k, march = rref.case_inputs(case)
+        stands_for = sref.without_positive_blocks(vol)
+        assert all(d % 8 == 0 and d - 8 < n <= d for d, n in zip(stands_for["dims"], vol["dims"])) and stands_for["allocated"].any()
+        dropped += int((~stands_for["allocated"]).sum())
+        want = rref.render(stands_for, pose, k, rref.CLIP_H, rref.CLIP_W, *march)
+        got = srref.render_virtual(stands_for, (0, 0, 0), stands_for["origin"], tuple(d // 8 for d in stands_for["dims"]), pose, k,
+                                   rref.CLIP_H, rref.CLIP_W, *march)
+        for key in ("depth", "normal"):
+            assert np.array_equal(got[key].view(np.uint32), want[key].view(np.uint32)), (case["id"], key)
+        assert np.array_equal(got["colour"], want["colour"]) and np.array_equal(got["hit"], want["hit"]), case["id"]
+        if case["group"] in (1, 2):
+            whole = rref.render(vol, pose, k, rref.CLIP_H, rref.CLIP_W, *march)
+            base = got["base"][got["hit"]]
+            assert np.array_equal(want["depth"].view(np.uint32), whole["depth"].view(np.uint32)), case["id"]
+            assert int(((base % 8) == 7).any(axis=1).sum()) >= 100, case["id"]
+            assert (~stands_for["allocated"]).any() == (case["group"] == 2), case["id"]
+    assert dropped > 200

@@ -56,8 +56,9 @@ def edge_type(step):
 
 
 def mesh(vol, min_weight=0.0):
-    """dict(keys (n, 4) int64: x y z edge of every vertex, vertices (n, 6) fp32, triangles (m, 3) int64 into them).  The order of
-    both is this function's own."""
+    """dict(keys (n, 4) int64: x y z edge of every vertex, vertices (n, 6) fp32, triangles (m, 3) int64 into them; per triangle cubes
+    (m, 3) int64: x y z of the base voxel of its cube, and tets (m,) int64: its tetrahedron, an index into PERMS; masks (nz, ny, nx)
+    uint8: bit e set where the voxel owns a vertex on its edge EDGES[e]).  The order of vertices and triangles is this function's own."""
     nx, ny, nz = vol["dims"]
     tsdf, weight = vol["tsdf"], vol["weight"]
     seen = weight > F(min_weight)
@@ -66,6 +67,7 @@ def mesh(vol, min_weight=0.0):
     pos = [np.broadcast_to(p, tsdf.shape) for p in (px, py, pz)]
     index = np.full((7, nz, ny, nx), -1, np.int64)             # vertex number of (edge, z, y, x)
     keys, records, count = [], [], 0
+    masks = np.zeros((nz, ny, nx), np.uint8)
     zz, yy, xx = np.meshgrid(np.arange(nz), np.arange(ny), np.arange(nx), indexing="ij")
     for e, step in enumerate(EDGES):
         extent = (nx - step[0], ny - step[1], nz - step[2])
@@ -86,16 +88,17 @@ def mesh(vol, min_weight=0.0):
                     rec[..., 3 + c] = np.floor(cv + s * (cn - cv) + F(0.5))
         n = int(active.sum())
         lo(index[e])[active] = count + np.arange(n)
+        lo(masks)[active] |= np.uint8(1 << e)
         keys.append(np.stack([lo(xx)[active], lo(yy)[active], lo(zz)[active], np.full(n, e)], axis=1))
         records.append(rec[active])
         count += n
     keys = np.concatenate(keys) if keys else np.zeros((0, 4), np.int64)
     records = np.concatenate(records).astype(F) if records else np.zeros((0, 6), F)
 
-    triangles = []
+    triangles, bases, tets = [], [], []
     cubes = (nx - 1, ny - 1, nz - 1)
     if min(cubes) >= 1:
-        for perm, odd in zip(PERMS, ODD):
+        for number_of_tet, (perm, odd) in enumerate(zip(PERMS, ODD)):
             corner = [(0, 0, 0)]
             for axis in perm:
                 corner.append(tuple(p + q for p, q in zip(corner[-1], _unit(axis))))
@@ -117,14 +120,79 @@ def mesh(vol, min_weight=0.0):
                         step = tuple(q - p for p, q in zip(corner[near], corner[far]))
                         ids.append(_shifted(index[edge_type(step)], corner[near], cubes)[pick])
                     triangles.append(np.stack(ids, axis=1))
+                    bases.append(np.stack([_shifted(a, (0, 0, 0), cubes)[pick] for a in (xx, yy, zz)], axis=1))
+                    tets.append(np.full(int(pick.sum()), number_of_tet, np.int64))
     triangles = np.concatenate(triangles) if triangles else np.zeros((0, 3), np.int64)
-    assert records.dtype == F and (triangles >= 0).all()
-    return dict(keys=keys, vertices=records, triangles=triangles)
+    bases = np.concatenate(bases) if bases else np.zeros((0, 3), np.int64)
+    tets = np.concatenate(tets) if tets else np.zeros(0, np.int64)
+    assert records.dtype == F and (triangles >= 0).all() and len(bases) == len(tets) == len(triangles)
+    return dict(keys=keys, vertices=records, triangles=triangles, cubes=bases, tets=tets, masks=masks)
 
 
 def axis_vertices(result):
     """The records on the three axis edges: what `extract` returns."""
     return result["vertices"][result["keys"][:, 3] < 3]
+
+
+# ------------------------------------------------------------------------------------------ vertices across tile seams
+TILE = (32, 8, 4)                              # the workgroup tile of the mesh kernels
+SEAM_PAIRS = 192                               # per axis: the 3 edge types without a step along it x the 64 masks that contain one type
+
+
+def seam_pairs(vol, result, tile=TILE):
+    """The set of (axis, owner mask, edge type) over the triangle vertices of `result` = mesh(vol, ...) whose owner voxel lies in the
+    next tile along `axis` than the base voxel of the triangle's cube: the triangle kernel ranks such a vertex with a mask from the
+    second halo layer of its staged codes and adds a vertex_base another workgroup wrote.  The owner is then a corner of the cube one
+    step along `axis` from its base, so the edge has no step along `axis`: 3 types x 64 masks = SEAM_PAIRS per axis."""
+    keys, masks = result["keys"], result["masks"]
+    pairs = set()
+    for corner in range(3):
+        owner = keys[result["triangles"][:, corner]]
+        mask = masks[owner[:, 2], owner[:, 1], owner[:, 0]]
+        for axis in range(3):
+            across = owner[:, axis] // tile[axis] == result["cubes"][:, axis] // tile[axis] + 1
+            pairs |= {(axis, int(m), int(e)) for m, e in np.unique(np.stack([mask[across], owner[across, 3]], axis=1), axis=0)}
+    assert all(m >> e & 1 and not EDGES[e][axis] for axis, m, e in pairs)
+    return pairs
+
+
+def pattern_volume(axis, seam, background, seed=0):
+    """Every sign pattern of a cube whose base is voxel `seam` of `axis`: all voxels seen, magnitudes 0.05 .. 1, the sign `background`
+    (+1 or -1) except on a 16 x 16 grid of sites 3 voxels apart along the other two axes, where corner dx + 2 dy + 4 dz of the cube is
+    negative iff that bit of the site's number is set.  seam + 3 voxels along `axis`, 49 along the others, random colours."""
+    dims = tuple(seam + 3 if a == axis else 49 for a in range(3))
+    vol = ref.new_volume(dims, (-0.3, 0.2, 1.0), 0.06, 0.18)
+    rng = np.random.default_rng(seed)
+    shape = vol["tsdf"].shape
+    sign = np.full(shape, float(background))
+    others = [a for a in range(3) if a != axis]
+    for site in range(256):
+        base = [0, 0, 0]
+        base[axis], base[others[0]], base[others[1]] = seam, 3 * (site % 16), 3 * (site // 16)
+        for corner in range(8):
+            x, y, z = base[0] + (corner & 1), base[1] + (corner >> 1 & 1), base[2] + (corner >> 2)
+            sign[z, y, x] = -1.0 if site >> corner & 1 else 1.0
+    vol["tsdf"] = (sign * (0.05 + 0.95 * rng.random(shape))).astype(F)
+    vol["weight"] = np.ones(shape, F)
+    vol["colour"][..., :3] = rng.integers(0, 256, size=shape + (3,), dtype=np.uint8)
+    return vol
+
+
+def noise_volume(dims, seed, unseen=0.1, colour=True):
+    """Independent random signs, magnitudes 0.02 .. 1, weights 1 .. 3 with a share `unseen` at 0, random colours; eight voxels hold
+    exactly 0.0 and eight -0.0 (both count as outside).  No NaN, no denormal."""
+    vol = ref.new_volume(dims, (-0.3, 0.2, 1.0), 0.06, 0.18, colour=colour)
+    rng = np.random.default_rng(seed)
+    shape = vol["tsdf"].shape
+    tsdf = (np.where(rng.random(shape) < 0.5, -1.0, 1.0) * (0.02 + 0.98 * rng.random(shape))).astype(F).reshape(-1)
+    zeros = rng.choice(tsdf.size, 16, replace=False)
+    tsdf[zeros[:8]], tsdf[zeros[8:]] = F(0.0), F(-0.0)
+    vol["tsdf"] = tsdf.reshape(shape)
+    vol["weight"] = np.where(rng.random(shape) < unseen, 0.0, rng.integers(1, 4, shape)).astype(F)
+    if colour:
+        vol["colour"][..., :3] = rng.integers(0, 256, size=shape + (3,), dtype=np.uint8)
+    assert np.isfinite(vol["tsdf"]).all() and (np.abs(vol["tsdf"][vol["tsdf"] != 0]) >= 0.02).all()
+    return vol
 
 
 # ------------------------------------------------------------------------------------------ comparing meshes

@@ -139,3 +139,21 @@ def cull_inputs(kind, depth, shift):
     seed = CULL_SEEDS.get((kind, depth, shift), 0)
     frames, ks = ref.camera_cases(SECOND, seed, kind, depth, SHIFTS[shift])
     return ref.shifted(SECOND, SHIFTS[shift]), frames, ks, np.inf if depth is None else depth
+
+
+# ------------------------------------------------------------------------------------------ dense restatement volumes as sparse ones
+def pad_to_blocks(vol):
+    """A copy of a dense restatement volume with its dims rounded up to whole blocks, the new voxels empty (tsdf 1, weight 0, colour 0):
+    what `SparseTSDFVolume` makes of those dims."""
+    nx, ny, nz = (-(-d // B) * B for d in vol["dims"])
+    out = ref.new_volume((nx, ny, nz), vol["origin"], vol["voxel"], vol["trunc"], colour=vol["colour"] is not None)
+    z, y, x = vol["tsdf"].shape
+    for key in ("tsdf", "weight") + (("colour",) if vol["colour"] is not None else ()):
+        out[key][:z, :y, :x] = vol[key]
+    return out
+
+
+def without_positive_blocks(vol):
+    """`pad_to_blocks(vol)` as a sparse volume in which only the blocks that hold a seen negative voxel have storage."""
+    full = pad_to_blocks(vol)
+    return sparsify(full, any_per_block((full["tsdf"] < 0) & (full["weight"] > 0)))
