@@ -79,6 +79,8 @@ class PLYSaver(torch.nn.Module):
 
     def __init__(self, height, width, min_d=3, max_d=400, batch_size=1, roi=None, dropout=0, capacity=1 << 22):
         super().__init__()
+        if int(capacity) < 1:                       # 0 would never grow (`_ensure` doubles it)
+            raise ValueError(f"PLYSaver: capacity must be at least 1 record, not {capacity}")
         self.height, self.width = height, width
         self.min_d, self.max_d = min_d, max_d
         self.roi = roi
@@ -117,7 +119,8 @@ class PLYSaver(torch.nn.Module):
         """`depth` is the predicted inverse depth (B,1,H,W) like in the reference.  Extras: `static_masks` (list of the
         buffered static_mask() outputs) fuses the vote + `depth *= mask` of create_pointcloud.py:90-92; `uniform`
         replaces the `torch.rand_like(depth)` of ply_utils.py:45 (given: deterministic; None with dropout > 0: drawn
-        here on the device)."""
+        here on the device).  Like the reference (:44) it thins only with dropout > 0: with dropout 0 a `uniform` is
+        not handed to the kernel, whose `uniform > dropout` would drop the entries that are exactly 0."""
         for t, n in ((depth, "depth"), (image, "image"), (intrinsics, "intrinsics"), (extrinsics, "extrinsics")):
             _need_cuda(t, n)
         lib = _lib.load()
@@ -127,14 +130,20 @@ class PLYSaver(torch.nn.Module):
         image = image.contiguous().float()
         kinv = torch.inverse(intrinsics.float().cpu())[:, :3, :3].contiguous().to(depth.device)     # ply_utils.py:47, host LAPACK
         pose = extrinsics.float().contiguous()
-        if self.dropout > 0 and uniform is None:
+        if not self.dropout > 0:
+            uniform = None
+        elif uniform is None:
             uniform = torch.rand_like(depth)
-        masks = list(static_masks) if static_masks else []
-        ptrs = (ctypes.c_void_p * max(len(masks), 1))(*[m.contiguous().data_ptr() for m in masks])
+        if uniform is not None:
+            uniform = uniform.contiguous().float()
+        # the contiguous fp32 copies are held in `masks` (and in _keep): the pointer of a temporary copy would be handed out
+        # again by the allocator for the next mask's copy
+        masks = [m.contiguous().float() for m in static_masks] if static_masks else []
+        ptrs = (ctypes.c_void_p * max(len(masks), 1))(*[m.data_ptr() for m in masks])
         roi = (ctypes.c_int32 * 4)(*self.roi) if self.roi is not None else None
         _lib.check(lib.mr_pointcloud_append_f32(
             depth.data_ptr(), ptrs, len(masks), float(len(masks) - min_hits), image.data_ptr(), kinv.data_ptr(),
-            pose.data_ptr(), uniform.contiguous().data_ptr() if uniform is not None else None, float(self.dropout),
+            pose.data_ptr(), uniform.data_ptr() if uniform is not None else None, float(self.dropout),
             float(self.min_d), float(self.max_d), roi, b, h, w, self._records.data_ptr(), self._records.shape[0],
             self._cursor.data_ptr(), torch.cuda.current_stream().cuda_stream), "mr_pointcloud_append_f32")
         self._keep = (depth, image, kinv, pose, uniform, masks)          # alive until the launch has run
