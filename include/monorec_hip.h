@@ -956,6 +956,39 @@ int mr_tsdf_sparse_render_f32(const int32_t* table, int32_t nbx, int32_t nby, in
                               const mr_tsdf_ray_view* views, int32_t num_views, int32_t height, int32_t width, float t_min, float t_max,
                               float step, void* stream);
 
+/* The sparse volume as a welded triangle mesh (two entries added within ABI 24: the change only adds symbols).  As canonical meshes -
+ * vertices as a set, triangles as a set of triples of vertices - the result equals that of mr_tsdf_mesh_vertices_f32 and
+ * mr_tsdf_mesh_triangles_f32 on the virtual dense volume of 8 nbx x 8 nby x 8 nbz voxels in which a block without a slot is UNSEEN
+ * whatever min_weight is: bit for bit, records, masks, tetrahedra, parity and winding by the same code (csrc/tsdf_common.h,
+ * csrc/tsdf_mesh.h).  With min_weight >= 0 that volume is the gathered one (mr_tsdf_sparse_gather_f32 writes weight 0 there).  The one
+ * difference: with min_weight < 0 the gathered volume's empty blocks count as seen with tsdf 1 and the dense entries put a surface
+ * between them and every negative voxel next to them; here they stay unseen and that surface is absent, as for
+ * mr_tsdf_sparse_extract_f32.
+ * Slots: num_slots as for mr_tsdf_sparse_extract_f32; 0 launches nothing.  A table entry below 0 or at or above num_slots is no slot, a
+ * neighbour beyond the table is unseen.  One workgroup per slot, which owns the vertices of its block's voxels and the triangles of the
+ * cubes whose base voxel lies in its block; a cube with a corner in a block without a slot emits nothing, so iterating over the slots
+ * is complete.  A workgroup that stages no seen negative voxel (its block and what it reaches of the seven + neighbours) touches neither
+ * its output, nor vertex_base, nor the cursor.
+ * vertex_base: int32[num_slots * 512], caller-owned, indexed like the pool - voxel (lx, ly, lz) of slot s at s * 512 + (lz * 8 + ly) * 8
+ * + lx, a 64-bit index; only the values are int32.  Its size follows the pool, not the dense box.  The vertex entry writes the index of
+ * the first vertex of every voxel that owns one and leaves the rest untouched; index(v, e) = vertex_base[v] + popcount(mask(v) &
+ * ((1 << e) - 1)) as in the dense mesh.  The triangle entry recomputes the masks from the same table, pool, num_slots and min_weight and
+ * reads vertex_base in the owner's own slot - across a block face that of a + neighbour.
+ * Positions are origin_a + (float)(8 b_a + l_a) * voxel_size, as mr_tsdf_sparse_extract_f32 computes them: the vertices on axis edges are
+ * its records.  Cursor protocol, capacity rule (counted, not written, at or beyond the capacity) and the count-only mode (vertices /
+ * triangles NULL: capacity and vertex_base are ignored, vertex_base may be NULL) are the dense mesh entries'.  Indices are int32: a
+ * caller whose vertex count reaches 2^31 must not fill.
+ * MR_ERR_BAD_ARGUMENT, nothing is launched: the table, pool and alignment cases of mr_tsdf_sparse_extract_f32 (the triangle entry has
+ * neither colour nor origin nor voxel_size); num_slots < 0, num_slots * 512 >= 2^40 or num_slots > nbx * nby * nbz; NaN min_weight;
+ * vertex_base / vertices / triangles off a 4-byte boundary; an output without vertex_base; a negative capacity with an output. */
+int mr_tsdf_sparse_mesh_vertices_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf, const float* weight,
+                                     const uint8_t* colour, const int32_t* block_of_slot, int64_t num_slots, const float* origin,
+                                     float voxel_size, float min_weight, float* vertices, int64_t capacity_vertices,
+                                     int32_t* vertex_base, int64_t* cursor, void* stream);
+int mr_tsdf_sparse_mesh_triangles_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf, const float* weight,
+                                      const int32_t* block_of_slot, int64_t num_slots, float min_weight, const int32_t* vertex_base,
+                                      int32_t* triangles, int64_t capacity_triangles, int64_t* cursor, void* stream);
+
 /* ---- input pipeline: KittiOdometryDataset.preprocess_image, kitti_odometry_dataset.py:120-134 ------
  *
  * img.crop(box) -> img.resize((W,H), Image.BILINEAR) -> float32 / 255 - .5 -> CHW (a 1-channel image is stacked 3x),

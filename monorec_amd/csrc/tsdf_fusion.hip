@@ -33,6 +33,7 @@
 
 #include "../../include/monorec_hip.h"
 #include "tsdf_common.h"                     // what the block-sparse volume (tsdf_sparse.hip) runs too: the voxel update, the edge masks, the planes
+#include "tsdf_mesh.h"                       // what its mesh runs too: the tetrahedron tables and the cases of a cube
 #include "tsdf_render.h"                     // what its ray-cast (tsdf_sparse_render.hip) runs too: the ray, the cell, the clip, the pixel's outputs
 
 namespace {
@@ -257,32 +258,6 @@ __global__ __launch_bounds__(256) void tsdf_mesh_vertices_kernel(const MeshArgs 
     }
 }
 
-// Triangles of an even tetrahedron per case (bit i: corner c_i inside): bits 0-3 the count, then a nibble per vertex naming the
-// tetrahedron's edge 0 E01, 1 E12, 2 E23, 3 E02, 4 E13, 5 E03 - the table of include/monorec_hip.h.  An odd tetrahedron swaps the
-// last two vertices of every triangle.
-constexpr unsigned TET_CASES[16] = {0x00000000u, 0x00005301u, 0x00001401u, 0x04515312u, 0x00002131u, 0x05202102u, 0x03202402u, 0x00002451u,
-                                     0x00004251u, 0x04202302u, 0x01202502u, 0x00001231u, 0x03515412u, 0x00004101u, 0x00003501u, 0x00000000u};
-// the six permutations (a, b, c), the even ones first, two bits per axis
-constexpr unsigned TET_PERMS[6] = {0u | 1u << 2 | 2u << 4, 1u | 2u << 2 | 0u << 4, 2u | 0u << 2 | 1u << 4,
-                                    0u | 2u << 2 | 1u << 4, 2u | 1u << 2 | 0u << 4, 1u | 0u << 2 | 2u << 4};
-
-// the cases of the six tetrahedra of the cube at `at` of the staged codes, four bits each; 0 where a corner is unseen
-__device__ __forceinline__ unsigned cube_cases(const uint8_t* code, int at) {
-    const int unit[3] = {1, CSX, CSX * CSY};
-    const unsigned c0 = code[at], c3 = code[at + 1 + CSX + CSX * CSY];
-    if (!(c0 & c3 & SEEN)) return 0u;
-    unsigned cases = 0;
-#pragma unroll
-    for (int t = 0; t < 6; ++t) {
-        const unsigned perm = TET_PERMS[t];
-        const int a1 = at + unit[perm & 3u];
-        const unsigned c1 = code[a1], c2 = code[a1 + unit[(perm >> 2) & 3u]];
-        if (!(c1 & c2 & SEEN)) continue;
-        cases |= (((c0 & NEG) >> 1) | (c1 & NEG) | ((c2 & NEG) << 1) | ((c3 & NEG) << 2)) << (4 * t);
-    }
-    return cases;
-}
-
 __global__ __launch_bounds__(256) void tsdf_mesh_triangles_kernel(const MeshArgs a) {
     __shared__ uint8_t s_code[CSN];
     __shared__ uint8_t s_mask[VSN];
@@ -311,7 +286,7 @@ __global__ __launch_bounds__(256) void tsdf_mesh_triangles_kernel(const MeshArgs
     int mine = 0;
 #pragma unroll
     for (int j = 0; j < TZ; ++j) {
-        cases[j] = cube_cases(s_code, (j * CSY + ly) * CSX + lx);
+        cases[j] = cube_cases(s_code, (j * CSY + ly) * CSX + lx, CSX, CSX * CSY);
 #pragma unroll
         for (int t = 0; t < 6; ++t) mine += (int)(TET_CASES[(cases[j] >> (4 * t)) & 15u] & 15u);
     }

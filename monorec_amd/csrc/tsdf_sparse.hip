@@ -11,7 +11,11 @@
 //                                  workgroup-wide OR of "some voxel in band" and then one atomic on the cursor.
 //   tsdf_sparse_extract_kernel     a workgroup of 256 threads per slot: its 8^3 voxels plus one beyond the high faces (9^3: tsdf, a code
 //                                  byte and the colour, 6.5 KB) staged from up to eight blocks through the table, then the dense vertex
-//                                  kernel's masks, prefix sum and records over the three axis edges
+//                                  kernel's masks, prefix sum and records: <3> over the three axis edges (the points), <7> over all
+//                                  seven a voxel owns (the mesh's vertices), which also writes vertex_base per POOL voxel
+//   tsdf_sparse_mesh_triangles_kernel   a workgroup per slot again: the code byte of its block plus TWO voxels beyond the high faces
+//                                  (10^3, still only the seven + neighbours) and the 9^3 owner masks that follow from them (1.7 KB), then
+//                                  the dense triangle kernel's cases, count and fill; an owner's vertex_base is read in the owner's slot
 //   tsdf_sparse_gather_kernel      a box of voxels into dense arrays, 1 / 0 / 0 where a block has no slot
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -19,12 +23,14 @@
 
 #include "../../include/monorec_hip.h"
 #include "tsdf_common.h"
+#include "tsdf_mesh.h"
 
 namespace {
 
 constexpr int B = MR_TSDF_BLOCK, BV = B * B * B;
 static_assert(B == 8, "128 threads of four voxels along x; rows of 32 bytes; >> 3 and & 7 below");
-constexpr int S = B + 1, SN = S * S * S;         // staged block of the extract kernel
+constexpr int S = B + 1, SN = S * S * S;         // staged block of the vertex kernel, and the owner masks of the triangle kernel
+constexpr int C = B + 2, CN = C * C * C;         // staged codes of the triangle kernel
 constexpr long long MAX_VOXELS = 1ll << 40;      // of the pool, and of a gathered box: idx * 4 bytes stays far from overflow
 
 struct Pool {
@@ -123,11 +129,24 @@ struct SparseExtractArgs {
     long long num_slots;
     float ox, oy, oz, voxel, min_weight;
     float* records;                              // null: count only
+    int* vertex_base;                            // per pool voxel: written by the 7-edge vertex kernel, read by the triangle kernel
+    int* triangles;                              // null: count only
     long long capacity;
     unsigned long long* cursor;
 };
 
+// the slots of the workgroup's block (its own: blockIdx.x) and of its seven + neighbours, -1 where there is none; tid < 8
+__device__ __forceinline__ void stage_slots(const SparseExtractArgs& a, int* s_slot, int tid, int bx, int by, int bz) {
+    const int nx = bx + (tid & 1), ny = by + ((tid >> 1) & 1), nz = bz + (tid >> 2);
+    int s = -1;
+    if (nx < a.nbx && ny < a.nby && nz < a.nbz) s = tid == 0 ? (int)blockIdx.x : a.table[((long long)nz * a.nby + ny) * a.nbx + nx];
+    s_slot[tid] = s < a.num_slots ? s : -1;
+}
+
+// EDGES = 3: the axis edges alone, the points of mr_tsdf_sparse_extract_f32.  EDGES = 7: the vertices of the mesh, and vertex_base.
+template <int EDGES>
 __global__ __launch_bounds__(256) void tsdf_sparse_extract_kernel(const SparseExtractArgs a) {
+    static_assert(EDGES == 3 || EDGES == 7, "the axis edges, or all a voxel owns");
     __shared__ float s_t[SN];
     __shared__ unsigned s_col[SN];
     __shared__ uint8_t s_code[SN];
@@ -138,12 +157,7 @@ __global__ __launch_bounds__(256) void tsdf_sparse_extract_kernel(const SparseEx
     const int bi = a.block_of_slot[blockIdx.x];
     if (bi < 0 || bi >= a.blocks) return;                                    // (a slot the caller counts but no launch filled)
     const int bx = bi % a.nbx, by = (bi / a.nbx) % a.nby, bz = bi / (a.nbx * a.nby);
-    if (tid < 8) {                                                           // the slots of this block and of its seven + neighbours
-        const int nx = bx + (tid & 1), ny = by + ((tid >> 1) & 1), nz = bz + (tid >> 2);
-        int s = -1;
-        if (nx < a.nbx && ny < a.nby && nz < a.nbz) s = tid == 0 ? (int)blockIdx.x : a.table[((long long)nz * a.nby + ny) * a.nbx + nx];
-        s_slot[tid] = s < a.num_slots ? s : -1;
-    }
+    if (tid < 8) stage_slots(a, s_slot, tid, bx, by, bz);
     __syncthreads();
     int any_neg = 0;
     for (int i = tid; i < SN; i += 256) {
@@ -169,7 +183,7 @@ __global__ __launch_bounds__(256) void tsdf_sparse_extract_kernel(const SparseEx
     const int lx = tid & 7, ly = (tid >> 3) & 7, lz = tid >> 6;              // the thread's two voxels: z = lz and lz + 4
     unsigned masks = 0;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) masks |= edge_mask<3>(s_code, ((lz + 4 * j) * S + ly) * S + lx, S, S * S) << (8 * j);
+    for (int j = 0; j < 2; ++j) masks |= edge_mask<EDGES>(s_code, ((lz + 4 * j) * S + ly) * S + lx, S, S * S) << (8 * j);
     const int mine = __popc(masks);
     int total;
     const int before = workgroup_prefix(mine, wave_tot, total);
@@ -180,27 +194,126 @@ __global__ __launch_bounds__(256) void tsdf_sparse_extract_kernel(const SparseEx
     if (!masks) return;
     long long rec = (long long)s_base + before;
     const float px = a.ox + (float)((long long)bx * B + lx) * a.voxel, py = a.oy + (float)((long long)by * B + ly) * a.voxel;
-    const int s_far[3] = {1, S, S * S};
+    const int s_far[7] = {1, S, S * S, 1 + S, 1 + S * S, S + S * S, 1 + S + S * S};
+    constexpr unsigned along[7] = {1u, 2u, 4u, 3u, 5u, 6u, 7u};              // bit k: the edge advances along axis k
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const unsigned mask = (masks >> (8 * j)) & 0xffu;
         if (!mask) continue;
         const int at = ((lz + 4 * j) * S + ly) * S + lx;
+        if constexpr (EDGES == 7) a.vertex_base[(long long)blockIdx.x * BV + (((lz + 4 * j) * B + ly) * B + lx)] = (int)rec;
         const float p[3] = {px, py, a.oz + (float)((long long)bz * B + lz + 4 * j) * a.voxel};
         const float tv = s_t[at];
         const unsigned cv = s_col[at];
 #pragma unroll
-        for (int e = 0; e < 3; ++e) {
+        for (int e = 0; e < EDGES; ++e) {
             if (!(mask & (1u << e))) continue;
             if (rec < a.capacity) {
                 const float s = tv / (tv - s_t[at + s_far[e]]);
                 const float step = s * a.voxel;
                 float* r = a.records + rec * 6;
 #pragma unroll
-                for (int k = 0; k < 3; ++k) r[k] = k == e ? p[k] + step : p[k];
+                for (int k = 0; k < 3; ++k) r[k] = (along[e] >> k) & 1u ? p[k] + step : p[k];
                 write_colour(r, cv, s_col[at + s_far[e]], s);
             }
             ++rec;
+        }
+    }
+}
+
+// The triangles of the cubes whose base voxel lies in the workgroup's block, two cubes per thread (z = lz and lz + 4): the dense triangle
+// kernel's cases, count and fill.  An owner across a block face has its vertex_base in the slot of that + neighbour; it has one, because
+// a cube emits only where all its corners are seen, and a voxel of a block without a slot is not.
+__global__ __launch_bounds__(256) void tsdf_sparse_mesh_triangles_kernel(const SparseExtractArgs a) {
+    __shared__ uint8_t s_code[CN];
+    __shared__ uint8_t s_mask[SN];
+    __shared__ int s_slot[8];
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x;
+    const int bi = a.block_of_slot[blockIdx.x];
+    if (bi < 0 || bi >= a.blocks) return;                                    // (a slot the caller counts but no launch filled)
+    const int bx = bi % a.nbx, by = (bi / a.nbx) % a.nby, bz = bi / (a.nbx * a.nby);
+    if (tid < 8) stage_slots(a, s_slot, tid, bx, by, bz);
+    __syncthreads();
+    int any_neg = 0;
+    for (int i = tid; i < CN; i += 256) {
+        const int sx = i % C, sy = (i / C) % C, sz = i / (C * C);            // 8 and 9 lie in the + neighbour
+        const int s = s_slot[(sx >> 3) | ((sy >> 3) << 1) | ((sz >> 3) << 2)];
+        unsigned c = 0u;
+        if (s >= 0) {
+            const long long p = (long long)s * BV + (((sz & 7) * B + (sy & 7)) * B + (sx & 7));
+            if (a.pool.weight[p] > a.min_weight) c = a.pool.tsdf[p] < 0.0f ? (SEEN | NEG) : SEEN;
+        }
+        s_code[i] = (uint8_t)c;
+        if (sx < S && sy < S && sz < S) any_neg |= (int)(c & NEG);           // the corners of the block's cubes
+    }
+    if (!__syncthreads_or(any_neg)) return;
+
+    const int lx = tid & 7, ly = (tid >> 3) & 7, lz = tid >> 6;
+    unsigned cases[2];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        cases[j] = cube_cases(s_code, ((lz + 4 * j) * C + ly) * C + lx, C, C * C);
+#pragma unroll
+        for (int t = 0; t < 6; ++t) mine += (int)(TET_CASES[(cases[j] >> (4 * t)) & 15u] & 15u);
+    }
+    int total;
+    const int before = workgroup_prefix(mine, wave_tot, total);
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);   // one per workgroup
+    if (!a.triangles) return;
+    for (int i = tid; i < SN; i += 256) {
+        const int sx = i % S, sy = (i / S) % S, sz = i / (S * S);
+        s_mask[i] = (uint8_t)edge_mask<7>(s_code, (sz * C + sy) * C + sx, C, C * C);
+    }
+    __syncthreads();
+    if (!mine) return;
+    long long tri = (long long)s_base + before;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (!cases[j]) continue;
+#pragma unroll 1
+        for (int t = 0; t < 6; ++t) {
+            unsigned word = TET_CASES[(cases[j] >> (4 * t)) & 15u];
+            const int count = (int)(word & 15u);
+            if (!count) continue;
+            const unsigned perm = TET_PERMS[t];
+            const int pa = perm & 3u, pb = (perm >> 2) & 3u, pc = (perm >> 4) & 3u;
+            // the owners c0, c1, c2 of the tetrahedron's six edges, as voxels 0 .. 8 of the staged block, and the edges' types
+            const int x0 = lx, y0 = ly, z0 = lz + 4 * j;
+            const int x1 = x0 + (pa == 0), y1 = y0 + (pa == 1), z1 = z0 + (pa == 2);
+            const int x2 = x1 + (pb == 0), y2 = y1 + (pb == 1), z2 = z1 + (pb == 2);
+            const auto m_at = [](int x, int y, int z) { return (z * S + y) * S + x; };
+            const auto g_at = [&](int x, int y, int z) {                      // the voxel's place in the pool: its own slot's
+                const int s = s_slot[(x >> 3) | ((y >> 3) << 1) | ((z >> 3) << 2)];
+                return (long long)s * BV + (((z & 7) * B + (y & 7)) * B + (x & 7));
+            };
+            const int m_own[3] = {m_at(x0, y0, z0), m_at(x1, y1, z1), m_at(x2, y2, z2)};
+            const long long g_own[3] = {g_at(x0, y0, z0), g_at(x1, y1, z1), g_at(x2, y2, z2)};
+            const int owner[6] = {0, 1, 2, 0, 1, 0};
+            const int type[6] = {pa, pb, pc, 2 + pa + pb, 2 + pb + pc, 6};
+            word >>= 4;
+            for (int n = 0; n < count; ++n, ++tri, word >>= 12) {
+                if (tri >= a.capacity) continue;
+                int v[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const int edge = (int)((word >> (4 * k)) & 15u);
+                    int own = 0, ty = 0;
+#pragma unroll
+                    for (int q = 0; q < 6; ++q) if (edge == q) { own = owner[q]; ty = type[q]; }
+                    int mo = m_own[0];
+                    long long go = g_own[0];
+                    if (own == 1) { mo = m_own[1]; go = g_own[1]; }
+                    if (own == 2) { mo = m_own[2]; go = g_own[2]; }
+                    v[k] = a.vertex_base[go] + __popc((unsigned)s_mask[mo] & ((1u << ty) - 1u));
+                }
+                int* r = a.triangles + tri * 3;
+                const bool odd = t >= 3;
+                r[0] = v[0]; r[1] = odd ? v[2] : v[1]; r[2] = odd ? v[1] : v[2];
+            }
         }
     }
 }
@@ -285,6 +398,28 @@ bool frame_box(const mr_tsdf_view& f, int h, int w, double depth, double push, d
     return true;
 }
 
+// What the three surface entries share: the checks of table, pool, slots, output and cursor, and the kernels' arguments with no output
+// set.  The triangle entry has no colour and no positions (NO_ORIGIN, a voxel of 1).  True: a bad argument.
+constexpr float NO_ORIGIN[3] = {0.0f, 0.0f, 0.0f};
+bool surface_args(SparseExtractArgs& a, const int32_t* table, int nbx, int nby, int nbz, const float* tsdf, const float* weight,
+                  const uint8_t* colour, const int32_t* block_of_slot, long long num_slots, const float* origin, float voxel_size,
+                  float min_weight, const void* out, long long capacity, int64_t* cursor) {
+    long long blocks;
+    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !block_of_slot || !cursor || !origin) return true;
+    if (((uintptr_t)block_of_slot & 3) || ((uintptr_t)cursor & 7) || ((uintptr_t)out & 3) || (out && capacity < 0)) return true;
+    if (num_slots < 0 || num_slots >= MAX_VOXELS / BV || num_slots > blocks) return true;
+    if (!(voxel_size > 0.0f) || min_weight != min_weight) return true;
+    a.table = table;
+    a.pool = {const_cast<float*>(tsdf), const_cast<float*>(weight), reinterpret_cast<unsigned*>(const_cast<uint8_t*>(colour))};
+    a.block_of_slot = block_of_slot;
+    a.nbx = nbx; a.nby = nby; a.nbz = nbz; a.blocks = blocks; a.num_slots = num_slots;
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.voxel = voxel_size; a.min_weight = min_weight;
+    a.records = nullptr; a.vertex_base = nullptr; a.triangles = nullptr;
+    a.capacity = out ? capacity : 0;
+    a.cursor = reinterpret_cast<unsigned long long*>(cursor);
+    return false;
+}
+
 }  // namespace
 
 extern "C" int mr_tsdf_sparse_integrate_f32(int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, float* tsdf, float* weight, uint8_t* colour,
@@ -360,22 +495,43 @@ extern "C" int mr_tsdf_sparse_extract_f32(const int32_t* table, int32_t nbx, int
                                           const uint8_t* colour, const int32_t* block_of_slot, int64_t num_slots, const float* origin,
                                           float voxel_size, float min_weight, float* records, int64_t capacity_records, int64_t* cursor,
                                           void* stream) {
-    long long blocks;
-    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !block_of_slot || !cursor || !origin) return MR_ERR_BAD_ARGUMENT;
-    if (((uintptr_t)block_of_slot & 3) || ((uintptr_t)cursor & 7) || ((uintptr_t)records & 3) || (records && capacity_records < 0)) return MR_ERR_BAD_ARGUMENT;
-    if (num_slots < 0 || num_slots >= MAX_VOXELS / BV || num_slots > blocks) return MR_ERR_BAD_ARGUMENT;
-    if (!(voxel_size > 0.0f) || min_weight != min_weight) return MR_ERR_BAD_ARGUMENT;
-    if (num_slots == 0) return 0;
     SparseExtractArgs a;
-    a.table = table;
-    a.pool = {const_cast<float*>(tsdf), const_cast<float*>(weight), reinterpret_cast<unsigned*>(const_cast<uint8_t*>(colour))};
-    a.block_of_slot = block_of_slot;
-    a.nbx = nbx; a.nby = nby; a.nbz = nbz; a.blocks = blocks; a.num_slots = num_slots;
-    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2]; a.voxel = voxel_size; a.min_weight = min_weight;
+    if (surface_args(a, table, nbx, nby, nbz, tsdf, weight, colour, block_of_slot, num_slots, origin, voxel_size, min_weight, records,
+                     capacity_records, cursor))
+        return MR_ERR_BAD_ARGUMENT;
+    if (num_slots == 0) return 0;
     a.records = records;
-    a.capacity = records ? capacity_records : 0;
-    a.cursor = reinterpret_cast<unsigned long long*>(cursor);
-    hipLaunchKernelGGL(tsdf_sparse_extract_kernel, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(tsdf_sparse_extract_kernel<3>, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_sparse_mesh_vertices_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf, const float* weight,
+                                                const uint8_t* colour, const int32_t* block_of_slot, int64_t num_slots, const float* origin,
+                                                float voxel_size, float min_weight, float* vertices, int64_t capacity_vertices,
+                                                int32_t* vertex_base, int64_t* cursor, void* stream) {
+    SparseExtractArgs a;
+    if (surface_args(a, table, nbx, nby, nbz, tsdf, weight, colour, block_of_slot, num_slots, origin, voxel_size, min_weight, vertices,
+                     capacity_vertices, cursor) ||
+        ((uintptr_t)vertex_base & 3) || (vertices && !vertex_base))
+        return MR_ERR_BAD_ARGUMENT;
+    if (num_slots == 0) return 0;
+    a.records = vertices; a.vertex_base = vertex_base;
+    hipLaunchKernelGGL(tsdf_sparse_extract_kernel<7>, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_sparse_mesh_triangles_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf,
+                                                 const float* weight, const int32_t* block_of_slot, int64_t num_slots, float min_weight,
+                                                 const int32_t* vertex_base, int32_t* triangles, int64_t capacity_triangles, int64_t* cursor,
+                                                 void* stream) {
+    SparseExtractArgs a;
+    if (surface_args(a, table, nbx, nby, nbz, tsdf, weight, nullptr, block_of_slot, num_slots, NO_ORIGIN, 1.0f, min_weight, triangles,
+                     capacity_triangles, cursor) ||
+        ((uintptr_t)vertex_base & 3) || (triangles && !vertex_base))
+        return MR_ERR_BAD_ARGUMENT;
+    if (num_slots == 0) return 0;
+    a.triangles = triangles; a.vertex_base = const_cast<int*>(vertex_base);
+    hipLaunchKernelGGL(tsdf_sparse_mesh_triangles_kernel, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

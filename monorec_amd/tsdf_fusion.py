@@ -27,9 +27,11 @@ and changes no bit of the result; header and tests/tsdf_render_ref.py as above. 
 direct-indexed table of blocks of 8^3 voxels and a pool that holds only the blocks some keyframe put within the truncation band of a
 surface (`mr_tsdf_sparse_integrate_f32`, the dense kernel's arithmetic through csrc/tsdf_common.h).  It has the integrate methods and
 `extract` / `count` / `save_ply` (`mr_tsdf_sparse_extract_f32`) and `render` / `render_result` (`mr_tsdf_sparse_render_f32`: the dense
-march through the table, bit for bit the render of the gathered volume) of `TSDFVolume`; `to_dense()` (`mr_tsdf_sparse_gather_f32`) hands
-any region that fits to the dense class for `mesh()`.  The runner key `sparse_volume` selects it, `sparse_render` renders and scores it
-without the dense copy.
+march through the table, bit for bit the render of the gathered volume) and `mesh` / `mesh_counts` / `save_mesh_ply`
+(`mr_tsdf_sparse_mesh_vertices_f32`, `mr_tsdf_sparse_mesh_triangles_f32`: the dense mesh of the gathered volume as a canonical mesh, from
+the blocks themselves, with 4 bytes of workspace per pool voxel) of `TSDFVolume`; `to_dense()` (`mr_tsdf_sparse_gather_f32`) hands any
+region that fits to the dense class, which nothing needs any more.  The runner key `sparse_volume` selects it, `sparse_render` renders
+and scores it and `sparse_mesh` meshes it without the dense copy.
 
 `run(config)` takes the configs of `pointcloud.run` / `tsdf_export.run` and drives the same pipelined loop
 (`tsdf_export.KeyframeStream`): per keyframe one pack launch into a staging slot on the device, per `fuse_batch` keyframes one
@@ -37,8 +39,8 @@ integrate launch on the same stream; nothing is copied to the host before the su
 `Fusion.score()` renders the fused volume into every exported keyframe again and scores it against the dataset's targets; with
 `render_dir`, `write()` also writes those views as 16-bit centimetre PNGs and JPEGs.
 
-Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; a native mesh of the sparse volume
-(it goes through `to_dense()`), growth of its pool, eviction or hashing; a cap on the weight; fusing across ranks (`run` is single-process)."""
+Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; a mesh of a region of the
+sparse volume (it meshes the whole of it), growth of its pool, eviction or hashing; a cap on the weight; fusing across ranks (`run` is single-process)."""
 import contextlib
 import ctypes
 import functools
@@ -254,6 +256,43 @@ class _Volume:
         _write(file, write_ply, records.reshape(-1))
         return records.shape[0]
 
+    # -- the surface as a mesh
+    def mesh_counts(self, min_weight=0):
+        """(vertices, triangles) `mesh(min_weight)` would return: the two count launches and one read."""
+        cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            self._mesh_launches(min_weight, cursor)
+        n, m = cursor.tolist()
+        return int(n), int(m)
+
+    def mesh(self, min_weight=0):
+        """The zero-crossing surface between voxels of weight > min_weight as a welded triangle mesh on the device: vertices (n, 6) fp32
+        x y z red green blue - those on the grid's axis edges are `extract(min_weight)`'s records - and triangles (m, 3) int32 indices
+        into them, wound so that (b - a) x (c - a) points from inside (tsdf < 0) to outside.  Marching tetrahedra: closed wherever the
+        voxels are seen, about twice the triangles of marching cubes.  A count launch per array, one read of both counts, a fill launch per
+        array; 4 bytes per voxel of workspace for the time of the call - per voxel of the grid for `TSDFVolume`, per voxel of the allocated
+        blocks for `SparseTSDFVolume`, which meshes its blocks as they are (`mr_tsdf_sparse_mesh_vertices_f32`,
+        `mr_tsdf_sparse_mesh_triangles_f32`).  The order of both arrays is unspecified."""
+        n, m = self.mesh_counts(min_weight)
+        if n >= 2 ** 31:
+            raise ValueError(f"monorec_amd.tsdf_fusion: a mesh of {n} vertices does not fit int32 indices; raise min_weight or mesh a part")
+        vertices = torch.empty(n, 6, dtype=torch.float32, device=self.device)
+        triangles = torch.empty(m, 3, dtype=torch.int32, device=self.device)
+        if n:
+            cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
+            vertex_base = torch.empty(self._mesh_voxels(), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                self._mesh_launches(min_weight, cursor, vertices, triangles, vertex_base)
+            if cursor.tolist() != [n, m]:
+                raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launches")
+        return vertices, triangles
+
+    def save_mesh_ply(self, file, min_weight=0):
+        """The mesh as a binary .ply (`pointcloud.write_mesh_ply`) to a path or a binary file object.  Returns (vertices, triangles)."""
+        vertices, triangles = (t.cpu().numpy() for t in self.mesh(min_weight))
+        _write(file, write_mesh_ply, vertices, triangles)
+        return vertices.shape[0], triangles.shape[0]
+
     # -- the volume seen from a camera
     def render(self, cam_to_world, intrinsics, height, width, t_min=0.0, t_max=None, step=None, min_weight=0, normals=True, colour=True,
                skip=True):
@@ -382,39 +421,9 @@ class TSDFVolume(_Volume):
             _lib.check(lib.mr_tsdf_mesh_triangles_f32(self.tsdf.data_ptr(), self.weight.data_ptr(), *self.dims, float(min_weight), base, out[0], out[1],
                                                       cursor.data_ptr() + 8, self._stream()), "mr_tsdf_mesh_triangles_f32")
 
-    def mesh_counts(self, min_weight=0):
-        """(vertices, triangles) `mesh(min_weight)` would return: the two count launches and one read."""
-        cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
-        with torch.cuda.device(self.device):
-            self._mesh_launches(min_weight, cursor)
-        n, m = cursor.tolist()
-        return int(n), int(m)
-
-    def mesh(self, min_weight=0):
-        """The zero-crossing surface between voxels of weight > min_weight as a welded triangle mesh on the device: vertices (n, 6) fp32
-        x y z red green blue - those on the grid's axis edges are `extract(min_weight)`'s records - and triangles (m, 3) int32 indices
-        into them, wound so that (b - a) x (c - a) points from inside (tsdf < 0) to outside.  Marching tetrahedra: closed wherever the
-        voxels are seen, about twice the triangles of marching cubes.  A count launch per array, one read of both counts, a fill launch per
-        array; 4 bytes per voxel of workspace for the time of the call.  The order of both arrays is unspecified."""
-        n, m = self.mesh_counts(min_weight)
-        if n >= 2 ** 31:
-            raise ValueError(f"monorec_amd.tsdf_fusion: a mesh of {n} vertices does not fit int32 indices; raise min_weight or mesh a part")
-        vertices = torch.empty(n, 6, dtype=torch.float32, device=self.device)
-        triangles = torch.empty(m, 3, dtype=torch.int32, device=self.device)
-        if n:
-            cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
-            vertex_base = torch.empty(self.tsdf.numel(), dtype=torch.int32, device=self.device)
-            with torch.cuda.device(self.device):
-                self._mesh_launches(min_weight, cursor, vertices, triangles, vertex_base)
-            if cursor.tolist() != [n, m]:
-                raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launches")
-        return vertices, triangles
-
-    def save_mesh_ply(self, file, min_weight=0):
-        """The mesh as a binary .ply (`pointcloud.write_mesh_ply`) to a path or a binary file object.  Returns (vertices, triangles)."""
-        vertices, triangles = (t.cpu().numpy() for t in self.mesh(min_weight))
-        _write(file, write_mesh_ply, vertices, triangles)
-        return vertices.shape[0], triangles.shape[0]
+    def _mesh_voxels(self):
+        """Elements of `mesh()`'s vertex_base: one per voxel of the grid."""
+        return self.tsdf.numel()
 
     # -- the volume seen from a camera
     def skip_grid(self, min_weight=0):
@@ -500,7 +509,12 @@ class SparseTSDFVolume(_Volume):
     the sparse volume itself.  `render` has `TSDFVolume.render`'s signature and returns, bit for bit, what `to_dense(bounds).render` would:
     a block without storage is unseen (tsdf 1, weight 0, colour 0), which costs a ray one table entry per sample; `skip` is accepted and
     ignored.  It reads the cursor once per call, and a range of more than 2^20 samples per ray raises a ValueError.
-    `to_dense()` gathers any region that fits into a `TSDFVolume`; only `mesh()` needs it."""
+    `mesh` / `mesh_counts` / `save_mesh_ply` (`mr_tsdf_sparse_mesh_vertices_f32`, `mr_tsdf_sparse_mesh_triangles_f32`) have `TSDFVolume`'s
+    signatures and return, as a canonical mesh (the order of both arrays is unspecified), what `to_dense(bounds).mesh` would for
+    min_weight >= 0: a workgroup per allocated block, vertices welded across block faces through the table, and a workspace of 4 bytes per
+    voxel of the ALLOCATED blocks, not of the grid.  A block without storage is unseen whatever min_weight is (with min_weight < 0 the
+    gathered volume's empty blocks would count as seen).
+    `to_dense()` gathers any region that fits into a `TSDFVolume`; nothing here needs it any more."""
 
     def __init__(self, bounds=None, voxel_size=0.1, trunc=None, colour=True, device="cuda:0", max_bytes=8 << 30, origin=None, dims=None,
                  capacity_blocks=None):
@@ -579,6 +593,28 @@ class SparseTSDFVolume(_Volume):
                                                               self.voxel_size, float(min_weight), *out, cursor.data_ptr(), self._stream()),
                        "mr_tsdf_sparse_extract_f32")
         return int(cursor.item())
+
+    # -- the surface as a mesh
+    def _mesh_voxels(self):
+        """Elements of `mesh()`'s vertex_base: one per pool voxel of the allocated blocks (one read of the cursor)."""
+        return self.allocated_blocks() * BLOCK ** 3
+
+    def _mesh_launches(self, min_weight, cursor, vertices=None, triangles=None, vertex_base=None):
+        """The two sparse mesh entries over the allocated slots on the current stream, the vertex one first: counting (no outputs) or
+        filling, then over the slots `vertex_base` was sized for."""
+        lib, nothing = _lib.load(), (None, 0)
+        slots = self.allocated_blocks() if vertex_base is None else vertex_base.numel() // BLOCK ** 3
+        base = vertex_base.data_ptr() if vertex_base is not None else None
+        out = nothing if vertices is None else (vertices.data_ptr(), vertices.shape[0])
+        if vertices is None or vertices.shape[0]:
+            _lib.check(lib.mr_tsdf_sparse_mesh_vertices_f32(*self._table_args(), self.block_of_slot.data_ptr(), slots, self._origin, self.voxel_size,
+                                                            float(min_weight), out[0], out[1], base, cursor.data_ptr(), self._stream()),
+                       "mr_tsdf_sparse_mesh_vertices_f32")
+        out = nothing if triangles is None else (triangles.data_ptr(), triangles.shape[0])
+        if triangles is None or triangles.shape[0]:
+            _lib.check(lib.mr_tsdf_sparse_mesh_triangles_f32(*self._table_args()[:6], self.block_of_slot.data_ptr(), slots, float(min_weight), base,
+                                                             out[0], out[1], cursor.data_ptr() + 8, self._stream()),
+                       "mr_tsdf_sparse_mesh_triangles_f32")
 
     # -- the volume seen from a camera
     def _render_shared(self, march, min_weight, skip):
@@ -788,6 +824,17 @@ def sparse_setting(config):
     return sparse
 
 
+def sparse_mesh_setting(config):
+    """The runner key `sparse_mesh` (default false), checked: with `sparse_volume`, mesh the sparse volume itself
+    (`SparseTSDFVolume.save_mesh_ply`) and not the whole of it gathered into a dense one."""
+    native = config.get("sparse_mesh", False)
+    if not isinstance(native, bool):
+        raise ValueError(f"monorec_amd.tsdf_fusion: sparse_mesh {native!r} must be true or false")
+    if native and not sparse_setting(config):
+        raise ValueError("monorec_amd.tsdf_fusion: sparse_mesh needs sparse_volume: true (a dense volume is meshed as it is)")
+    return native
+
+
 def sparse_render_setting(config):
     """The runner key `sparse_render` (default false), checked: with `sparse_volume`, render and score the sparse volume itself
     (`SparseTSDFVolume.render`) and not the whole of it gathered into a dense one."""
@@ -805,7 +852,7 @@ class Fusion:
 
     def __init__(self, config, model=None, dataset=None, device="cuda:0"):
         self.config, self.settings, self.sparse = config, fusion_settings(config), sparse_setting(config)
-        self.sparse_render = sparse_render_setting(config)
+        self.sparse_render, self.sparse_mesh = sparse_render_setting(config), sparse_mesh_setting(config)
         settings = self.settings
         if settings["bounds"] is not None:
             self._check_dense_outputs(settings["bounds"])         # before the model is built
@@ -832,10 +879,11 @@ class Fusion:
         self.mesh_counts = None                                # (vertices, triangles) of the mesh file, once `write()` has written one
 
     def _check_dense_outputs(self, bounds):
-        """With `sparse_volume`, the mesh - and without `sparse_render` the renders and the score - work on the whole volume gathered into
-        a dense one, which must fit `tsdf_max_bytes` too: a ValueError that names the keys before anything is fused."""
+        """With `sparse_volume`, the mesh without `sparse_mesh` - and the renders and the score without `sparse_render` - work on the whole
+        volume gathered into a dense one, which must fit `tsdf_max_bytes` too: a ValueError that names the keys before anything is fused."""
         settings = self.settings
-        asked = [key for key in (("mesh_file_name",) if self.sparse_render else ("mesh_file_name", "render_dir", "fused_metrics")) if settings[key]]
+        dense = (() if self.sparse_mesh else ("mesh_file_name",)) + (() if self.sparse_render else ("render_dir", "fused_metrics"))
+        asked = [key for key in dense if settings[key]]
         if not self.sparse or not asked:
             return
         dims = tuple((d + BLOCK - 1) // BLOCK * BLOCK for d in dims_of_bounds(bounds, settings["voxel_size"]))
@@ -844,8 +892,12 @@ class Fusion:
                              f"{dims[0]} x {dims[1]} x {dims[2]} voxels, {volume_bytes(dims) / 2 ** 30:.2f} GiB, more than tsdf_max_bytes = "
                              f"{settings['max_bytes'] / 2 ** 30:.2f} GiB; raise tsdf_max_bytes, or write the points alone (file_name)")
 
+    def meshed(self):
+        """The volume `write()` meshes: `dense()`, or with `sparse_mesh` the sparse volume itself."""
+        return self.volume if self.sparse_mesh else self.dense()
+
     def dense(self):
-        """The volume `mesh()` works on: the volume itself, or the whole sparse one gathered (`to_dense`, once)."""
+        """The volume `mesh()` works on without `sparse_mesh`: the volume itself, or the whole sparse one gathered (`to_dense`, once)."""
         if not self.sparse:
             return self.volume
         if self._dense is None:
@@ -896,7 +948,7 @@ class Fusion:
         os.makedirs(out_dir, exist_ok=True)
         count = self.volume.save_ply(os.path.join(out_dir, self.settings["file_name"]))
         if self.settings["mesh_file_name"] is not None:
-            self.mesh_counts = self.dense().save_mesh_ply(os.path.join(out_dir, self.settings["mesh_file_name"]))
+            self.mesh_counts = self.meshed().save_mesh_ply(os.path.join(out_dir, self.settings["mesh_file_name"]))
         if self.settings["save_volume"] is not None:
             self.volume.save(self.settings["save_volume"])
         if self.settings["render_dir"] is not None:
@@ -972,8 +1024,9 @@ def run(config, model=None, dataset=None, device="cuda:0"):
     `sparse_volume` (false; true: fuse into a `SparseTSDFVolume` over the same bounds with `tsdf_max_bytes` as the budget of table and pool -
     points and `save_volume` come from it, mesh, renders and score from the whole of it gathered into a dense volume, which must fit
     `tsdf_max_bytes` as well; a pool that ran out raises after the loop), `sparse_render` (false; true, with `sparse_volume` only: renders and
-    score come from the sparse volume itself, `SparseTSDFVolume.render` - the same bits without the dense copy, so only `mesh_file_name` still
-    asks for room for one).
+    score come from the sparse volume itself, `SparseTSDFVolume.render` - the same bits without the dense copy), `sparse_mesh` (false; true,
+    with `sparse_volume` only: `mesh_file_name` is written from the sparse volume itself, `SparseTSDFVolume.save_mesh_ply` - the same mesh
+    without the dense copy; with both keys nothing asks for room for one).
 
     Per keyframe `pack_frames` (vote, crop, thresholds: the depths are exactly the ones the export writes to the PNG) fills a staging slot
     on the device; after `fuse_batch` keyframes, or at the end, one integrate launch follows on the same stream.  Every keyframe is
