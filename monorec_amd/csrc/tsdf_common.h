@@ -1,7 +1,8 @@
-// What tsdf_fusion.hip (the dense volume) and tsdf_sparse.hip (the block-sparse one) share, so that both run the same arithmetic and not
-// two copies of it: the update of one voxel by one frame, the colour blend, the edge masks and record colours of the surface points, the
-// workgroup prefix sum, and the host's preparation of a frame's culling planes.  include/monorec_hip.h has the rules; both sources are
-// compiled with -ffp-contract=off.
+// What tsdf_fusion.hip (the dense volume), tsdf_sparse.hip (the block-sparse one) and, for its last section, tsdf_sparse_render.hip share,
+// so that they run the same code and not copies of it (include/monorec_hip.h has the rules; compiled with -ffp-contract=off): the update
+// of one voxel by one frame, FrameArgs and the host's frame_args and planes, live_frames, edge masks, record colours, the workgroup
+// prefix sum, the checks of the surface entries, and the blocks' B, BV, pool_index and bad_sparse.  The frame loop round
+// the voxel update stays in the two kernels: as a shared inline function it cost the dense one five VGPRs.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -50,17 +51,28 @@ __device__ __forceinline__ void tsdf_update_voxel(const mr_tsdf_view& f, float p
     band = band || ratio < 1.0f;
 }
 
-// Which of `num_frames` frames can reach a workgroup's voxels: their bounding sphere (centre, cull_radius) against the five planes of each
-// frame.  Uniform over the workgroup.
-__device__ __forceinline__ unsigned live_frames(const float (*plane)[5][4], int num_frames, float ccx, float ccy, float ccz, float cull_radius) {
+// What both integrate kernels read of a launch's frames; the host's frame_args (below) fills it.
+struct FrameArgs {
+    float ox, oy, oz, voxel, trunc, max_depth;
+    int num_frames, h, w;
+    float cull_radius;                           // bounding sphere of a workgroup's voxels plus the margin for the fp32 evaluation
+    mr_tsdf_view f[MR_TSDF_MAX_FRAMES];
+    float plane[MR_TSDF_MAX_FRAMES][5][4];       // (n, d) in world space, |n| = 1 or 0 (0: never culls); inside is n . p + d >= 0
+};
+
+// Which frames can reach a workgroup's voxels: their bounding sphere (centre, cull_radius) against the five planes of each frame.
+// Uniform over the workgroup.
+__device__ __forceinline__ unsigned live_frames(const FrameArgs& a, float ccx, float ccy, float ccz) {
     unsigned live = 0;
+    const int num_frames = a.num_frames;
+    const float cull_radius = a.cull_radius;
     for (int fi = 0; fi < num_frames; ++fi) {
         bool out = false;
 #pragma unroll
         for (int p = 0; p < 5; ++p) {
-            const float* q = plane[fi][p];
+            const float* q = a.plane[fi][p];
             const float dist = ((q[0] * ccx + q[1] * ccy) + q[2] * ccz) + q[3];
-            out = out || (dist < -cull_radius);                        // NaN: not culled
+            out = out || (dist < -cull_radius);                      // NaN: not culled
         }
         if (!out) live |= 1u << fi;
     }
@@ -159,6 +171,67 @@ inline double frames_reach(double corner, const mr_tsdf_view* frames, int num_fr
         reach = fmax(reach, 2.0 * corner + sqrt((double)m[3] * m[3] + (double)m[7] * m[7] + (double)m[11] * m[11]));
     }
     return reach;
+}
+
+// The frame half of an integrate launch, for both entries: the checks of the frames, the image and the limits, then `a` - the frames,
+// their planes (those of the unused frames never cull) and the cull radius round a workgroup's sphere of `radius` metres.  The volume
+// has voxels[k] voxels along axis k and its workgroups reach `pad` further; origin and voxel_size are checked by the caller.  Returns the
+// margin 1e-3 * voxel + FP32_SLACK * reach that widens the cull radius (not negative; it may be infinite or NaN), or -1: a bad argument.
+inline double frame_args(FrameArgs& a, const float* origin, float voxel_size, float trunc, float max_depth_m,
+                       const mr_tsdf_view* frames, int num_frames, int height, int width, bool has_colour, const double voxels[3], int pad,
+                       double radius) {
+    if (!frames || num_frames < 1 || num_frames > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return -1.0;
+    if (!(trunc > 0.0f) || max_depth_m != max_depth_m) return -1.0;
+    if ((long long)height * width * 3 >= (1ll << 40)) return -1.0;
+    for (int i = 0; i < num_frames; ++i)
+        if (!frames[i].depth_cm || (has_colour && !frames[i].colour)) return -1.0;
+    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
+    a.voxel = voxel_size; a.trunc = trunc; a.max_depth = max_depth_m;
+    a.num_frames = num_frames; a.h = height; a.w = width;
+    const double v = (double)voxel_size;
+    double corner = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        const double far_k = fmax(fabs((double)origin[k]), fabs((double)origin[k] + (voxels[k] + pad) * v));
+        corner += far_k * far_k;
+    }
+    corner = sqrt(corner);
+    for (int i = 0; i < MR_TSDF_MAX_FRAMES; ++i) {
+        a.f[i] = frames[i < num_frames ? i : 0];
+        if (i < num_frames) view_planes(frames[i], height, width, a.plane[i]);
+        else for (int p = 0; p < 5; ++p) for (int k = 0; k < 4; ++k) a.plane[i][p][k] = 0.0f;
+    }
+    const double margin = 1e-3 * v + FP32_SLACK * frames_reach(corner, frames, num_frames);
+    const double cull = radius + margin;
+    a.cull_radius = isfinite(cull) ? nextafterf((float)cull, INFINITY) : INFINITY;       // infinite: `dist < -inf` never holds
+    return margin;
+}
+
+// ---- what the surface entries of both volumes check alike
+constexpr long long MAX_VOXELS = 1ll << 40;      // of a volume, a pool or a gathered box: idx * 4 bytes and the block counts stay far from overflow
+constexpr float NO_ORIGIN[3] = {0.0f, 0.0f, 0.0f};               // of an entry that takes no positions (with a voxel of 1)
+
+// an output of 4-byte elements that may be null (count only) and the cursor beside it.  True: a bad argument.
+inline bool bad_output(const void* out, long long capacity, const int64_t* cursor) {
+    return !cursor || ((uintptr_t)cursor & 7) || ((uintptr_t)out & 3) || (out && capacity < 0);
+}
+
+// ---- the block-sparse volume: a table of one slot (or -1) per block of B^3 voxels, and a pool of BV voxels per slot
+constexpr int B = MR_TSDF_BLOCK, BV = B * B * B;
+static_assert(B == 8, "128 threads of four voxels along x; rows of 32 bytes; >> 3 and & 7 below");
+
+// the pool index of voxel (x, y, z) of slot s; the coordinates may be the volume's or, up to B + 1, those of a block with its + halo
+__device__ __forceinline__ long long pool_index(int s, int x, int y, int z) {
+    return (long long)s * BV + (((z & 7) * B + (y & 7)) * B + (x & 7));
+}
+
+// The checks the sparse entries share: the table and the pool.  True: a bad argument.  `blocks` returns nbx * nby * nbz.
+inline bool bad_sparse(const void* table, int nbx, int nby, int nbz, const void* tsdf, const void* weight, const void* colour, long long& blocks) {
+    if (!table || !tsdf || !weight || nbx < 1 || nby < 1 || nbz < 1) return true;
+    if (((uintptr_t)table & 3) || (((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)colour) & 15)) return true;
+    const long long xy = (long long)nbx * nby;                               // < 2^62
+    if (xy >= (1ll << 31)) return true;
+    blocks = xy * nbz;                                                       // < 2^62
+    return blocks >= (1ll << 31);
 }
 
 }  // namespace

@@ -11,7 +11,7 @@
 //   tsdf_mesh_vertices_kernel<7>, tsdf_mesh_triangles_kernel   the same surface as an indexed mesh (marching tetrahedra; further down):
 //                           the same kernel over all seven edges a voxel owns, which also writes vertex_base, and the triangles
 //   tsdf_skip_grid_kernel, tsdf_render_kernel   the volume seen from a camera (at the end)
-// All but reset and render sweep the volume in one tile, decoded from blockIdx by tile_of_block.
+// All but reset and render sweep the volume in one tile (tile_of_block); integrate and skip grid load a thread's four voxels with load_four.
 //
 // The integration sweeps the volume: 8 bytes (12 with colour) in and out per voxel and frame BATCH, the depth and colour images are
 // gathered through the caches (a keyframe is a few hundred KB).  Measured kernel time (DESIGN.md section 7, 512 x 512 x 128 voxels,
@@ -32,7 +32,7 @@
 #include <stdint.h>
 
 #include "../../include/monorec_hip.h"
-#include "tsdf_common.h"                     // what the block-sparse volume (tsdf_sparse.hip) runs too: the voxel update, the edge masks, the planes
+#include "tsdf_common.h"                     // the block-sparse volume's too: FrameArgs / frame_args, voxel update, edge masks, MAX_VOXELS, NO_ORIGIN, bad_output
 #include "tsdf_mesh.h"                       // what its mesh runs too: the tetrahedron tables and the cases of a cube
 #include "tsdf_render.h"                     // what its ray-cast (tsdf_sparse_render.hip) runs too: the ray, the cell, the clip, the pixel's outputs
 
@@ -40,7 +40,6 @@ namespace {
 
 constexpr int TX = MR_TSDF_TILE_X, TY = MR_TSDF_TILE_Y, TZ = MR_TSDF_TILE_Z;
 static_assert(TX == 32 && TY == 8 && TZ == 4, "256 threads, four voxels along x each");
-constexpr long long MAX_VOXELS = 1ll << 40;      // 64-bit voxel indices; the bound keeps idx * 4 bytes and the block counts far from overflow
 
 struct IntegrateArgs {
     float* tsdf;
@@ -48,11 +47,7 @@ struct IntegrateArgs {
     uint8_t* colour;                             // 4 bytes per voxel or null
     int nx, ny, nz;
     int tiles_x, tiles_y;
-    float ox, oy, oz, voxel, trunc, max_depth;
-    int num_frames, h, w;
-    float cull_radius;                           // bounding sphere of a tile plus the margin for the fp32 evaluation
-    mr_tsdf_view f[MR_TSDF_MAX_FRAMES];
-    float plane[MR_TSDF_MAX_FRAMES][5][4];       // (n, d) in world space, |n| = 1 or 0 (0: never culls); inside is n . p + d >= 0
+    FrameArgs fr;                                // the frames, their planes, the cull radius of a tile
 };
 
 __global__ __launch_bounds__(256) void tsdf_reset_kernel(float* __restrict__ tsdf, float* __restrict__ weight, unsigned* __restrict__ colour,
@@ -75,13 +70,30 @@ __device__ __forceinline__ Tile tile_of_block(int tiles_x, int tiles_y) {
     return {(tile % tiles_x) * UX, ((tile / tiles_x) % tiles_y) * UY, (tile / (tiles_x * tiles_y)) * UZ};
 }
 
+// tsdf and weight of a thread's four voxels along x, of which the first n are in the row (1 and 0 for the rest): one 16-byte load per
+// array where vec, else scalar loads.  Of the integrate and the skip-grid sweep.
+__device__ __forceinline__ void load_four(const float* tp, const float* wp, int n, bool vec, float t[4], float wgt[4]) {
+    if (vec) {
+        const float4 tv = *reinterpret_cast<const float4*>(tp);
+        const float4 wv = *reinterpret_cast<const float4*>(wp);
+        t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
+        wgt[0] = wv.x; wgt[1] = wv.y; wgt[2] = wv.z; wgt[3] = wv.w;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            t[j] = j < n ? tp[j] : 1.0f;
+            wgt[j] = j < n ? wp[j] : 0.0f;
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs a) {
     const Tile b = tile_of_block<1, 1, 1>(a.tiles_x, a.tiles_y);
     // which frames can reach this tile: the centre of the (full) tile against the five planes of each frame
-    const float ccx = a.ox + ((float)(b.x * TX) + 0.5f * (TX - 1)) * a.voxel;
-    const float ccy = a.oy + ((float)(b.y * TY) + 0.5f * (TY - 1)) * a.voxel;
-    const float ccz = a.oz + ((float)(b.z * TZ) + 0.5f * (TZ - 1)) * a.voxel;
-    const unsigned live = live_frames(a.plane, a.num_frames, ccx, ccy, ccz, a.cull_radius);
+    const float ccx = a.fr.ox + ((float)(b.x * TX) + 0.5f * (TX - 1)) * a.fr.voxel;
+    const float ccy = a.fr.oy + ((float)(b.y * TY) + 0.5f * (TY - 1)) * a.fr.voxel;
+    const float ccz = a.fr.oz + ((float)(b.z * TZ) + 0.5f * (TZ - 1)) * a.fr.voxel;
+    const unsigned live = live_frames(a.fr, ccx, ccy, ccz);
     if (live == 0) return;
 
     const int tid = threadIdx.x;
@@ -97,18 +109,7 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
 
     float t[4], wgt[4];
     unsigned col[4] = {0u, 0u, 0u, 0u};
-    if (vec) {
-        const float4 tv = *reinterpret_cast<const float4*>(tp);
-        const float4 wv = *reinterpret_cast<const float4*>(wp);
-        t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
-        wgt[0] = wv.x; wgt[1] = wv.y; wgt[2] = wv.z; wgt[3] = wv.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            t[j] = j < n ? tp[j] : 1.0f;
-            wgt[j] = j < n ? wp[j] : 0.0f;
-        }
-    }
+    load_four(tp, wp, n, vec, t, wgt);
     if (cp) {
         if (cvec) {
             const uint4 cv = *reinterpret_cast<const uint4*>(cp);
@@ -119,18 +120,19 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(const IntegrateArgs
         }
     }
 
-    const float py = a.oy + (float)y * a.voxel, pz = a.oz + (float)z * a.voxel;
-    const float wf = (float)a.w, hf = (float)a.h;
+    const FrameArgs& fr = a.fr;
+    const float py = fr.oy + (float)y * fr.voxel, pz = fr.oz + (float)z * fr.voxel;
+    const float wf = (float)fr.w, hf = (float)fr.h;
     unsigned touched = 0;
     bool band = false;                           // (the block-sparse volume's question; nobody asks here)
-    for (int fi = 0; fi < a.num_frames; ++fi) {
+    for (int fi = 0; fi < fr.num_frames; ++fi) {
         if (!(live & (1u << fi))) continue;
-        const mr_tsdf_view& f = a.f[fi];
+        const mr_tsdf_view& f = fr.f[fi];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= n) continue;
-            const float px = a.ox + (float)(x + j) * a.voxel;
-            tsdf_update_voxel(f, px, py, pz, a.w, wf, hf, a.trunc, a.max_depth, cp != nullptr, t[j], wgt[j], col[j], touched, 1u << j, band);
+            const float px = fr.ox + (float)(x + j) * fr.voxel;
+            tsdf_update_voxel(f, px, py, pz, fr.w, wf, hf, fr.trunc, fr.max_depth, cp != nullptr, t[j], wgt[j], col[j], touched, 1u << j, band);
         }
     }
     if (!touched) return;
@@ -352,7 +354,6 @@ long long voxel_count(int nx, int ny, int nz) {                  // MAX_VOXELS f
 }
 
 // The checks the entries share: the volume, and - where an entry takes them; the defaults pass - origin, voxel_size and min_weight.
-constexpr float NO_ORIGIN[3] = {0.0f, 0.0f, 0.0f};
 bool bad_volume(const void* tsdf, const void* weight, const void* colour, int nx, int ny, int nz, const float* origin = NO_ORIGIN,
                 float voxel_size = 1.0f, float min_weight = 0.0f) {
     if (!tsdf || !weight || nx < 1 || ny < 1 || nz < 1 || !origin) return true;
@@ -383,41 +384,17 @@ extern "C" int mr_tsdf_volume_reset_f32(float* tsdf, float* weight, uint8_t* col
 extern "C" int mr_tsdf_integrate_f32(float* tsdf, float* weight, uint8_t* colour, int32_t nx, int32_t ny, int32_t nz, const float* origin,
                                      float voxel_size, float trunc, float max_depth_m, const mr_tsdf_view* frames, int32_t num_frames,
                                      int32_t height, int32_t width, void* stream) {
-    if (bad_volume(tsdf, weight, colour, nx, ny, nz, origin, voxel_size) || !frames) return MR_ERR_BAD_ARGUMENT;
-    if (num_frames < 1 || num_frames > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return MR_ERR_BAD_ARGUMENT;
-    if (!(trunc > 0.0f) || max_depth_m != max_depth_m) return MR_ERR_BAD_ARGUMENT;
-    if ((long long)height * width * 3 >= (1ll << 40)) return MR_ERR_BAD_ARGUMENT;
-    for (int i = 0; i < num_frames; ++i)
-        if (!frames[i].depth_cm || (colour && !frames[i].colour)) return MR_ERR_BAD_ARGUMENT;
+    if (bad_volume(tsdf, weight, colour, nx, ny, nz, origin, voxel_size)) return MR_ERR_BAD_ARGUMENT;
     IntegrateArgs a;
+    // the sphere round the voxel CENTRES of a full tile; the tiles reach up to TX voxels beyond the volume
+    const double voxels[3] = {(double)nx, (double)ny, (double)nz};
+    const double radius = 0.5 * (double)voxel_size * sqrt((double)((TX - 1) * (TX - 1) + (TY - 1) * (TY - 1) + (TZ - 1) * (TZ - 1)));
+    if (frame_args(a.fr, origin, voxel_size, trunc, max_depth_m, frames, num_frames, height, width, colour != nullptr, voxels, TX, radius) < 0.0)
+        return MR_ERR_BAD_ARGUMENT;
     a.tsdf = tsdf; a.weight = weight; a.colour = colour;
     a.nx = nx; a.ny = ny; a.nz = nz;
     const unsigned tiles = tile_grid(nx, ny, nz, a.tiles_x, a.tiles_y);
     if (!tiles) return MR_ERR_BAD_ARGUMENT;
-    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
-    a.voxel = voxel_size; a.trunc = trunc; a.max_depth = max_depth_m;
-    a.num_frames = num_frames; a.h = height; a.w = width;
-    // sphere round the voxel CENTRES of a full tile, plus what fp32 can move (frames_reach in tsdf_common.h)
-    const double v = (double)voxel_size;
-    double corner = 0.0;
-    const int dims[3] = {nx, ny, nz};
-    for (int k = 0; k < 3; ++k) {
-        const double far_k = fmax(fabs((double)origin[k]), fabs((double)origin[k] + (dims[k] + TX) * v));
-        corner += far_k * far_k;
-    }
-    corner = sqrt(corner);
-    for (int i = 0; i < num_frames; ++i) {
-        a.f[i] = frames[i];
-        view_planes(frames[i], height, width, a.plane[i]);
-    }
-    const double reach = frames_reach(corner, frames, num_frames);
-    for (int i = num_frames; i < MR_TSDF_MAX_FRAMES; ++i) {
-        a.f[i] = frames[0];
-        for (int p = 0; p < 5; ++p) for (int k = 0; k < 4; ++k) a.plane[i][p][k] = 0.0f;
-    }
-    const double radius = 0.5 * v * sqrt((double)((TX - 1) * (TX - 1) + (TY - 1) * (TY - 1) + (TZ - 1) * (TZ - 1)));
-    const double cull = radius + 1e-3 * v + FP32_SLACK * reach;
-    a.cull_radius = isfinite(cull) ? nextafterf((float)cull, INFINITY) : INFINITY;       // infinite: `dist < -inf` never holds
     hipLaunchKernelGGL(tsdf_integrate_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
@@ -429,7 +406,7 @@ namespace {
 bool surface_args(MeshArgs& a, unsigned& tiles, const float* tsdf, const float* weight, const uint8_t* colour, int nx, int ny, int nz,
                   const float* origin, float voxel_size, float min_weight, const void* out, long long capacity, int64_t* cursor) {
     if (bad_volume(tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight)) return true;
-    if (!cursor || ((uintptr_t)cursor & 7) || ((uintptr_t)out & 3) || (out && capacity < 0)) return true;
+    if (bad_output(out, capacity, cursor)) return true;
     if (nx > 0x7fffffff - CSX || ny > 0x7fffffff - CSY || nz > 0x7fffffff - CSZ) return true;   // x0 + sx of a staged block stays an int
     a.tsdf = tsdf; a.weight = weight; a.colour = reinterpret_cast<const unsigned*>(colour);
     a.nx = nx; a.ny = ny; a.nz = nz;
@@ -522,18 +499,7 @@ __global__ __launch_bounds__(256) void tsdf_skip_grid_kernel(const SkipArgs a) {
     const float* tp = a.tsdf + idx;
     const float* wp = a.weight + idx;
     float t[4], wgt[4];
-    if (n == 4 && (((uintptr_t)tp | (uintptr_t)wp) & 15) == 0) {
-        const float4 tv = *reinterpret_cast<const float4*>(tp);
-        const float4 wv = *reinterpret_cast<const float4*>(wp);
-        t[0] = tv.x; t[1] = tv.y; t[2] = tv.z; t[3] = tv.w;
-        wgt[0] = wv.x; wgt[1] = wv.y; wgt[2] = wv.z; wgt[3] = wv.w;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            t[j] = j < n ? tp[j] : 1.0f;
-            wgt[j] = j < n ? wp[j] : 0.0f;
-        }
-    }
+    load_four(tp, wp, n, n == 4 && (((uintptr_t)tp | (uintptr_t)wp) & 15) == 0, t, wgt);
     bool any = false, first = false;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {

@@ -17,6 +17,7 @@
 //                                  (10^3, still only the seven + neighbours) and the 9^3 owner masks that follow from them (1.7 KB), then
 //                                  the dense triangle kernel's cases, count and fill; an owner's vertex_base is read in the owner's slot
 //   tsdf_sparse_gather_kernel      a box of voxels into dense arrays, 1 / 0 / 0 where a block has no slot
+// B, BV, pool_index (of the gather) and bad_sparse are in tsdf_common.h, with what the dense volume's kernels run too.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -27,11 +28,8 @@
 
 namespace {
 
-constexpr int B = MR_TSDF_BLOCK, BV = B * B * B;
-static_assert(B == 8, "128 threads of four voxels along x; rows of 32 bytes; >> 3 and & 7 below");
 constexpr int S = B + 1, SN = S * S * S;         // staged block of the vertex kernel, and the owner masks of the triangle kernel
 constexpr int C = B + 2, CN = C * C * C;         // staged codes of the triangle kernel
-constexpr long long MAX_VOXELS = 1ll << 40;      // of the pool, and of a gathered box: idx * 4 bytes stays far from overflow
 
 struct Pool {
     float* tsdf;
@@ -47,11 +45,7 @@ struct SparseIntegrateArgs {
     long long capacity;
     int nbx, nby;
     int x0, y0, z0, cx, cy;                      // the launch's box of blocks: its first block and its extent along x and y
-    float ox, oy, oz, voxel, trunc, max_depth;
-    int num_frames, h, w;
-    float cull_radius;
-    mr_tsdf_view f[MR_TSDF_MAX_FRAMES];
-    float plane[MR_TSDF_MAX_FRAMES][5][4];
+    FrameArgs fr;                                // the frames, their planes, the cull radius of a block
 };
 
 __global__ __launch_bounds__(128) void tsdf_sparse_integrate_kernel(const SparseIntegrateArgs a) {
@@ -59,10 +53,10 @@ __global__ __launch_bounds__(128) void tsdf_sparse_integrate_kernel(const Sparse
     const int box = blockIdx.x;
     const int bx = a.x0 + box % a.cx, by = a.y0 + (box / a.cx) % a.cy, bz = a.z0 + box / (a.cx * a.cy);
     const long long vx = (long long)bx * B, vy = (long long)by * B, vz = (long long)bz * B;         // (a block count may reach 2^31 - 1)
-    const float ccx = a.ox + ((float)vx + 0.5f * (B - 1)) * a.voxel;
-    const float ccy = a.oy + ((float)vy + 0.5f * (B - 1)) * a.voxel;
-    const float ccz = a.oz + ((float)vz + 0.5f * (B - 1)) * a.voxel;
-    const unsigned live = live_frames(a.plane, a.num_frames, ccx, ccy, ccz, a.cull_radius);
+    const float ccx = a.fr.ox + ((float)vx + 0.5f * (B - 1)) * a.fr.voxel;
+    const float ccy = a.fr.oy + ((float)vy + 0.5f * (B - 1)) * a.fr.voxel;
+    const float ccz = a.fr.oz + ((float)vz + 0.5f * (B - 1)) * a.fr.voxel;
+    const unsigned live = live_frames(a.fr, ccx, ccy, ccz);
     if (live == 0) return;
 
     const int tid = threadIdx.x;
@@ -82,18 +76,19 @@ __global__ __launch_bounds__(128) void tsdf_sparse_integrate_kernel(const Sparse
         }
     }
 
+    const FrameArgs& fr = a.fr;
     const long long x = vx + (tid & 1) * 4, y = vy + ((tid >> 1) & 7), z = vz + (tid >> 4);
-    const float py = a.oy + (float)y * a.voxel, pz = a.oz + (float)z * a.voxel;
-    const float wf = (float)a.w, hf = (float)a.h;
+    const float py = fr.oy + (float)y * fr.voxel, pz = fr.oz + (float)z * fr.voxel;
+    const float wf = (float)fr.w, hf = (float)fr.h;
     unsigned touched = 0;
     bool band = false;
-    for (int fi = 0; fi < a.num_frames; ++fi) {
+    for (int fi = 0; fi < fr.num_frames; ++fi) {
         if (!(live & (1u << fi))) continue;
-        const mr_tsdf_view& f = a.f[fi];
+        const mr_tsdf_view& f = fr.f[fi];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float px = a.ox + (float)(x + j) * a.voxel;
-            tsdf_update_voxel(f, px, py, pz, a.w, wf, hf, a.trunc, a.max_depth, a.pool.colour != nullptr, t[j], wgt[j], col[j], touched, 1u << j, band);
+            const float px = fr.ox + (float)(x + j) * fr.voxel;
+            tsdf_update_voxel(f, px, py, pz, fr.w, wf, hf, fr.trunc, fr.max_depth, a.pool.colour != nullptr, t[j], wgt[j], col[j], touched, 1u << j, band);
         }
     }
 
@@ -338,7 +333,7 @@ __global__ __launch_bounds__(256) void tsdf_sparse_gather_kernel(const SparseGat
         float t = 1.0f, w = 0.0f;
         unsigned c = 0u;
         if (s >= 0) {
-            const long long p = (long long)s * BV + (((z & 7) * B + (y & 7)) * B + (x & 7));
+            const long long p = pool_index(s, x, y, z);
             t = a.pool.tsdf[p];
             w = a.pool.weight[p];
             if (a.colour) c = a.pool.colour[p];
@@ -347,16 +342,6 @@ __global__ __launch_bounds__(256) void tsdf_sparse_gather_kernel(const SparseGat
         a.weight[i] = w;
         if (a.colour) a.colour[i] = c;
     }
-}
-
-// The checks the entries share: the table and the pool.  True: a bad argument.  `blocks` returns nbx * nby * nbz.
-bool bad_sparse(const void* table, int nbx, int nby, int nbz, const void* tsdf, const void* weight, const void* colour, long long& blocks) {
-    if (!table || !tsdf || !weight || nbx < 1 || nby < 1 || nbz < 1) return true;
-    if (((uintptr_t)table & 3) || (((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)colour) & 15)) return true;
-    const long long xy = (long long)nbx * nby;                               // < 2^62
-    if (xy >= (1ll << 31)) return true;
-    blocks = xy * nbz;                                                       // < 2^62
-    return blocks >= (1ll << 31);
 }
 
 // The box of blocks one frame can update, in double: a voxel is updated only if its camera-space point c = A p + t has 0 < c_2, projects
@@ -400,13 +385,12 @@ bool frame_box(const mr_tsdf_view& f, int h, int w, double depth, double push, d
 
 // What the three surface entries share: the checks of table, pool, slots, output and cursor, and the kernels' arguments with no output
 // set.  The triangle entry has no colour and no positions (NO_ORIGIN, a voxel of 1).  True: a bad argument.
-constexpr float NO_ORIGIN[3] = {0.0f, 0.0f, 0.0f};
 bool surface_args(SparseExtractArgs& a, const int32_t* table, int nbx, int nby, int nbz, const float* tsdf, const float* weight,
                   const uint8_t* colour, const int32_t* block_of_slot, long long num_slots, const float* origin, float voxel_size,
                   float min_weight, const void* out, long long capacity, int64_t* cursor) {
     long long blocks;
-    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !block_of_slot || !cursor || !origin) return true;
-    if (((uintptr_t)block_of_slot & 3) || ((uintptr_t)cursor & 7) || ((uintptr_t)out & 3) || (out && capacity < 0)) return true;
+    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !block_of_slot || !origin) return true;
+    if (((uintptr_t)block_of_slot & 3) || bad_output(out, capacity, cursor)) return true;
     if (num_slots < 0 || num_slots >= MAX_VOXELS / BV || num_slots > blocks) return true;
     if (!(voxel_size > 0.0f) || min_weight != min_weight) return true;
     a.table = table;
@@ -427,41 +411,24 @@ extern "C" int mr_tsdf_sparse_integrate_f32(int32_t* table, int32_t nbx, int32_t
                                             float trunc, float max_depth_m, const mr_tsdf_view* frames, int32_t num_frames, int32_t height,
                                             int32_t width, void* stream) {
     long long blocks;
-    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !block_of_slot || !cursor || !origin || !frames) return MR_ERR_BAD_ARGUMENT;
+    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks) || !block_of_slot || !cursor || !origin) return MR_ERR_BAD_ARGUMENT;
     if (((uintptr_t)block_of_slot & 3) || ((uintptr_t)cursor & 7)) return MR_ERR_BAD_ARGUMENT;
     if (capacity < 1 || capacity >= MAX_VOXELS / BV) return MR_ERR_BAD_ARGUMENT;
-    if (!(voxel_size > 0.0f) || !(trunc > 0.0f) || max_depth_m != max_depth_m) return MR_ERR_BAD_ARGUMENT;
-    if (num_frames < 1 || num_frames > MR_TSDF_MAX_FRAMES || height < 1 || width < 1) return MR_ERR_BAD_ARGUMENT;
-    if ((long long)height * width * 3 >= (1ll << 40)) return MR_ERR_BAD_ARGUMENT;
-    for (int i = 0; i < num_frames; ++i)
-        if (!frames[i].depth_cm || (colour && !frames[i].colour)) return MR_ERR_BAD_ARGUMENT;
+    if (!(voxel_size > 0.0f)) return MR_ERR_BAD_ARGUMENT;
     SparseIntegrateArgs a;
+    // the dense entry's margins, for the sphere round the voxel centres of a block
+    const double v = (double)voxel_size;
+    const int nb[3] = {nbx, nby, nbz};
+    const double voxels[3] = {(double)nbx * B, (double)nby * B, (double)nbz * B};
+    const double margin = frame_args(a.fr, origin, voxel_size, trunc, max_depth_m, frames, num_frames, height, width, colour != nullptr, voxels, B,
+                                     0.5 * v * sqrt(3.0 * (B - 1) * (B - 1)));
+    if (margin < 0.0) return MR_ERR_BAD_ARGUMENT;
     a.table = table;
     a.pool = {tsdf, weight, reinterpret_cast<unsigned*>(colour)};
     a.block_of_slot = block_of_slot;
     a.cursor = reinterpret_cast<unsigned long long*>(cursor);
     a.capacity = capacity;
     a.nbx = nbx; a.nby = nby;
-    a.ox = origin[0]; a.oy = origin[1]; a.oz = origin[2];
-    a.voxel = voxel_size; a.trunc = trunc; a.max_depth = max_depth_m;
-    a.num_frames = num_frames; a.h = height; a.w = width;
-    // the dense entry's margins, for the sphere round the voxel centres of a block
-    const double v = (double)voxel_size;
-    const int nb[3] = {nbx, nby, nbz};
-    double corner = 0.0;
-    for (int k = 0; k < 3; ++k) {
-        const double far_k = fmax(fabs((double)origin[k]), fabs((double)origin[k] + ((double)nb[k] * B + B) * v));
-        corner += far_k * far_k;
-    }
-    corner = sqrt(corner);
-    for (int i = 0; i < MR_TSDF_MAX_FRAMES; ++i) {
-        a.f[i] = frames[i < num_frames ? i : 0];
-        if (i < num_frames) view_planes(frames[i], height, width, a.plane[i]);
-        else for (int p = 0; p < 5; ++p) for (int k = 0; k < 4; ++k) a.plane[i][p][k] = 0.0f;
-    }
-    const double margin = 1e-3 * v + FP32_SLACK * frames_reach(corner, frames, num_frames);
-    const double cull = 0.5 * v * sqrt(3.0 * (B - 1) * (B - 1)) + margin;
-    a.cull_radius = isfinite(cull) ? nextafterf((float)cull, INFINITY) : INFINITY;       // infinite: `dist < -inf` never holds
     // The launch's box of blocks: no frame can update a voxel outside it, so leaving the rest of the table out changes no result.  Depths
     // come from int16 centimetres (at most 327.67 m) and count up to max_depth_m; a voxel trunc behind one is still updated.
     const double depth = (fmax(0.0, fmin((double)max_depth_m, 327.67)) + (double)trunc) * (1.0 + 1e-6) + margin;

@@ -2,6 +2,7 @@
 // the table and the pool of tsdf_sparse.hip, without a dense copy.  The ray, the cell of a sample, the clip, the interpolant and what a
 // pixel writes are the dense kernel's (tsdf_render.h; compiled with -ffp-contract=off); the rule is in include/monorec_hip.h,
 // tests/tsdf_sparse_render_ref.py restates it in numpy and the GPU tests compare bit for bit.
+// B, BV, MAX_VOXELS, pool_index and the checks of table and pool (bad_sparse) are tsdf_common.h's, shared with tsdf_sparse.hip.
 //
 //   tsdf_sparse_render_kernel   a thread per pixel, a wave a compact 8 x 8 pixel tile, a workgroup 16 x 16 pixels of one view
 //                               (blockIdx.z), as in the dense kernel: neighbouring rays walk neighbouring cells and blocks.  A sample
@@ -15,13 +16,11 @@
 #include <stdint.h>
 
 #include "../../include/monorec_hip.h"
+#include "tsdf_common.h"                     // the blocks, as tsdf_sparse.hip has them: B, BV, MAX_VOXELS, pool_index, bad_sparse
 #include "tsdf_render.h"
 
 namespace {
 
-constexpr int B = MR_TSDF_BLOCK, BV = B * B * B;
-static_assert(B == 8, ">> 3 and & 7 below");
-constexpr long long MAX_VOXELS = 1ll << 40;      // of the pool: idx * 4 bytes stays far from overflow
 constexpr int MAX_BLOCKS_PER_AXIS = 1 << 27;     // 8 nb_a voxels fit an int
 
 struct SparseRenderArgs {
@@ -42,11 +41,6 @@ struct SparseRenderArgs {
 __device__ __forceinline__ int slot_of(const SparseRenderArgs& a, int bx, int by, int bz) {
     const int s = a.table[((long long)bz * a.nby + by) * a.nbx + bx];
     return (unsigned)s < (unsigned)a.num_slots ? s : -1;
-}
-
-// the pool index of voxel (x, y, z) of slot s
-__device__ __forceinline__ long long pool_index(int s, int x, int y, int z) {
-    return (long long)s * BV + (((z & 7) * B + (y & 7)) * B + (x & 7));
 }
 
 // The pool indices of the 8 corners of the cell at i into P, -1 for a corner in a block without a slot; s0: the slot of i's own block.
@@ -135,13 +129,10 @@ extern "C" int mr_tsdf_sparse_render_f32(const int32_t* table, int32_t nbx, int3
                                          const uint8_t* colour, int64_t num_slots, const float* origin, float voxel_size, float min_weight,
                                          const mr_tsdf_ray_view* views, int32_t num_views, int32_t height, int32_t width, float t_min,
                                          float t_max, float step, void* stream) {
-    // the table and the pool, as the other sparse entries check them
-    if (!table || !tsdf || !weight || nbx < 1 || nby < 1 || nbz < 1) return MR_ERR_BAD_ARGUMENT;
-    if (((uintptr_t)table & 3) || (((uintptr_t)tsdf | (uintptr_t)weight | (uintptr_t)colour) & 15)) return MR_ERR_BAD_ARGUMENT;
+    long long blocks;
+    if (bad_sparse(table, nbx, nby, nbz, tsdf, weight, colour, blocks)) return MR_ERR_BAD_ARGUMENT;
     if (nbx > MAX_BLOCKS_PER_AXIS || nby > MAX_BLOCKS_PER_AXIS || nbz > MAX_BLOCKS_PER_AXIS) return MR_ERR_BAD_ARGUMENT;
-    const long long xy = (long long)nbx * nby;                               // < 2^54
-    if (xy >= (1ll << 31) || xy * nbz >= (1ll << 31)) return MR_ERR_BAD_ARGUMENT;
-    if (num_slots < 0 || num_slots >= MAX_VOXELS / BV || num_slots > xy * nbz) return MR_ERR_BAD_ARGUMENT;
+    if (num_slots < 0 || num_slots >= MAX_VOXELS / BV || num_slots > blocks) return MR_ERR_BAD_ARGUMENT;
     if (!origin || !(voxel_size > 0.0f) || min_weight != min_weight) return MR_ERR_BAD_ARGUMENT;
     if (bad_ray_views(views, num_views, height, width, t_min, t_max, step)) return MR_ERR_BAD_ARGUMENT;
     const long long last = last_sample(t_min, t_max, step);

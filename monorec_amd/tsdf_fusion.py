@@ -138,10 +138,12 @@ def volume_bytes(dims, colour=True):
 # ------------------------------------------------------------------------------------------ the volume
 class _Volume:
     """What `TSDFVolume` and `SparseTSDFVolume` share: the geometry of the constructor, the host half of the integration (checks, pose
-    inverse, `mr_tsdf_view` arrays), the count-then-fill protocol of the surface points and the host half of the ray-cast (poses,
-    intrinsics, `mr_tsdf_ray_view` arrays, outputs, the defaults of the range).  A subclass has `_integrate_launch` (one
-    launch of its integrate entry), `_extract_launch` (one launch of its extract entry and the read of the cursor), `_render_shared`
-    (what the launches of one `render` call share, made before the first) and `_render_launch` (one launch of its render entry)."""
+    inverse, `mr_tsdf_view` arrays), the count-then-fill protocol and the launches of the surface points and of the mesh, and the host
+    half of the ray-cast (poses, intrinsics, `mr_tsdf_ray_view` arrays, outputs, the defaults of the range).  A subclass has
+    `_integrate_launch` (one launch of its integrate entry), `_SURFACE_ENTRIES` (the names of its extract, mesh-vertex and mesh-triangle
+    entries), `_surface_args` (what those entries take ahead of the origin: the volume, or the table, the pool, `block_of_slot` and the
+    slots - with the colour, and without it for the triangle entry), `_mesh_voxels`, `_render_shared` (what the launches of one `render`
+    call share, made before the first) and `_render_launch` (one launch of its render entry)."""
 
     def _geometry(self, bounds, voxel_size, trunc, origin, dims):
         """Sets dims, origin, voxel_size and trunc as the entries will see them (fp32); returns voxel_size as given."""
@@ -249,6 +251,16 @@ class _Volume:
         """Number of records `extract(min_weight)` would return (the count launch alone)."""
         return self._extract_launch(min_weight)
 
+    def _extract_launch(self, min_weight, records=None):
+        """One launch of the extract entry on the current stream - counting, or filling `records` - and the read of its cursor."""
+        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
+        out = (None, 0) if records is None else (records.data_ptr(), records.shape[0])
+        name = self._SURFACE_ENTRIES[0]
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(_lib.load(), name)(*self._surface_args()[0], self._origin, self.voxel_size, float(min_weight), *out,
+                                                  cursor.data_ptr(), self._stream()), name)
+        return int(cursor.item())
+
     def save_ply(self, file, min_weight=0):
         """The surface points as a binary .ply (pointcloud.PLYSaver's header and records) to a path or a binary file object.  Returns
         the number of vertices."""
@@ -286,6 +298,21 @@ class _Volume:
             if cursor.tolist() != [n, m]:
                 raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launches")
         return vertices, triangles
+
+    def _mesh_launches(self, min_weight, cursor, vertices=None, triangles=None, vertex_base=None):
+        """The two mesh entries on the current stream, the vertex one first: counting (no outputs) or filling."""
+        lib, nothing = _lib.load(), (None, 0)
+        _, vertex_entry, triangle_entry = self._SURFACE_ENTRIES
+        with_colour, without_colour = self._surface_args(vertex_base)
+        base = vertex_base.data_ptr() if vertex_base is not None else None
+        out = nothing if vertices is None else (vertices.data_ptr(), vertices.shape[0])
+        if vertices is None or vertices.shape[0]:
+            _lib.check(getattr(lib, vertex_entry)(*with_colour, self._origin, self.voxel_size, float(min_weight), out[0], out[1], base,
+                                                  cursor.data_ptr(), self._stream()), vertex_entry)
+        out = nothing if triangles is None else (triangles.data_ptr(), triangles.shape[0])
+        if triangles is None or triangles.shape[0]:
+            _lib.check(getattr(lib, triangle_entry)(*without_colour, float(min_weight), base, out[0], out[1], cursor.data_ptr() + 8,
+                                                    self._stream()), triangle_entry)
 
     def save_mesh_ply(self, file, min_weight=0):
         """The mesh as a binary .ply (`pointcloud.write_mesh_ply`) to a path or a binary file object.  Returns (vertices, triangles)."""
@@ -398,28 +425,11 @@ class TSDFVolume(_Volume):
                                              size[0], size[1], self._stream()), "mr_tsdf_integrate_f32")
 
     # -- surface
-    def _extract_launch(self, min_weight, records=None):
-        """One launch of the entry on the current stream - counting, or filling `records` - and the read of its cursor."""
-        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
-        out = (None, 0) if records is None else (records.data_ptr(), records.shape[0])
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().mr_tsdf_extract_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), *out,
-                                                       cursor.data_ptr(), self._stream()), "mr_tsdf_extract_f32")
-        return int(cursor.item())
+    _SURFACE_ENTRIES = ("mr_tsdf_extract_f32", "mr_tsdf_mesh_vertices_f32", "mr_tsdf_mesh_triangles_f32")
 
-    # -- the surface as a mesh
-    def _mesh_launches(self, min_weight, cursor, vertices=None, triangles=None, vertex_base=None):
-        """The two mesh entries on the current stream, the vertex one first: counting (no outputs) or filling."""
-        lib, nothing = _lib.load(), (None, 0)
-        base = vertex_base.data_ptr() if vertex_base is not None else None
-        out = nothing if vertices is None else (vertices.data_ptr(), vertices.shape[0])
-        if vertices is None or vertices.shape[0]:
-            _lib.check(lib.mr_tsdf_mesh_vertices_f32(*self._volume_args(), self._origin, self.voxel_size, float(min_weight), out[0], out[1], base,
-                                                     cursor.data_ptr(), self._stream()), "mr_tsdf_mesh_vertices_f32")
-        out = nothing if triangles is None else (triangles.data_ptr(), triangles.shape[0])
-        if triangles is None or triangles.shape[0]:
-            _lib.check(lib.mr_tsdf_mesh_triangles_f32(self.tsdf.data_ptr(), self.weight.data_ptr(), *self.dims, float(min_weight), base, out[0], out[1],
-                                                      cursor.data_ptr() + 8, self._stream()), "mr_tsdf_mesh_triangles_f32")
+    def _surface_args(self, vertex_base=None):
+        args = self._volume_args()
+        return args, args[:2] + args[3:]
 
     def _mesh_voxels(self):
         """Elements of `mesh()`'s vertex_base: one per voxel of the grid."""
@@ -583,38 +593,17 @@ class SparseTSDFVolume(_Volume):
         return sparse_bytes(self.blocks, 0) + self.allocated_blocks() * BLOCK ** 3 * (12 if self.has_colour else 8)
 
     # -- surface
-    def _extract_launch(self, min_weight, records=None):
-        """One launch of the entry over the allocated slots on the current stream - counting, or filling `records` - and the read of
-        its cursor."""
-        cursor = torch.zeros(1, dtype=torch.int64, device=self.device)
-        out = (None, 0) if records is None else (records.data_ptr(), records.shape[0])
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().mr_tsdf_sparse_extract_f32(*self._table_args(), self.block_of_slot.data_ptr(), self.allocated_blocks(), self._origin,
-                                                              self.voxel_size, float(min_weight), *out, cursor.data_ptr(), self._stream()),
-                       "mr_tsdf_sparse_extract_f32")
-        return int(cursor.item())
+    _SURFACE_ENTRIES = ("mr_tsdf_sparse_extract_f32", "mr_tsdf_sparse_mesh_vertices_f32", "mr_tsdf_sparse_mesh_triangles_f32")
 
-    # -- the surface as a mesh
+    def _surface_args(self, vertex_base=None):
+        """Over the allocated slots (one read of the cursor), or over those a mesh's `vertex_base` was sized for."""
+        slots = self.allocated_blocks() if vertex_base is None else vertex_base.numel() // BLOCK ** 3
+        args = self._table_args()
+        return args + (self.block_of_slot.data_ptr(), slots), args[:6] + (self.block_of_slot.data_ptr(), slots)
+
     def _mesh_voxels(self):
         """Elements of `mesh()`'s vertex_base: one per pool voxel of the allocated blocks (one read of the cursor)."""
         return self.allocated_blocks() * BLOCK ** 3
-
-    def _mesh_launches(self, min_weight, cursor, vertices=None, triangles=None, vertex_base=None):
-        """The two sparse mesh entries over the allocated slots on the current stream, the vertex one first: counting (no outputs) or
-        filling, then over the slots `vertex_base` was sized for."""
-        lib, nothing = _lib.load(), (None, 0)
-        slots = self.allocated_blocks() if vertex_base is None else vertex_base.numel() // BLOCK ** 3
-        base = vertex_base.data_ptr() if vertex_base is not None else None
-        out = nothing if vertices is None else (vertices.data_ptr(), vertices.shape[0])
-        if vertices is None or vertices.shape[0]:
-            _lib.check(lib.mr_tsdf_sparse_mesh_vertices_f32(*self._table_args(), self.block_of_slot.data_ptr(), slots, self._origin, self.voxel_size,
-                                                            float(min_weight), out[0], out[1], base, cursor.data_ptr(), self._stream()),
-                       "mr_tsdf_sparse_mesh_vertices_f32")
-        out = nothing if triangles is None else (triangles.data_ptr(), triangles.shape[0])
-        if triangles is None or triangles.shape[0]:
-            _lib.check(lib.mr_tsdf_sparse_mesh_triangles_f32(*self._table_args()[:6], self.block_of_slot.data_ptr(), slots, float(min_weight), base,
-                                                             out[0], out[1], cursor.data_ptr() + 8, self._stream()),
-                       "mr_tsdf_sparse_mesh_triangles_f32")
 
     # -- the volume seen from a camera
     def _render_shared(self, march, min_weight, skip):
