@@ -147,35 +147,67 @@ def lds_bytes(geo, taps, cpads, mb, ck, split_k=1, bf16=False, reduce_bytes=0):
     return max(nbuf * 4 * (ck * geo["plane"] + taps * ck_max * mb * (8 if int(bf16) == 1 else 16)), reduce_bytes)    # bf16x3 blocks: hi + lo = fp32 size
 
 
-# LAUNCH_* kind -> the C-ABI entry that runs one descriptor of that kind: mirrors the mr_run_launches switch (csrc/eltwise.hip)
-_NATIVE_ENTRY = {
-    _lib.LAUNCH_CONV2D: lambda lib, d, arg, s: lib.mr_conv2d_f32(d, s),
-    _lib.LAUNCH_WINO3X3: lambda lib, d, arg, s: lib.mr_conv3x3_winograd_f32(d, s),
-    _lib.LAUNCH_WINO_T: lambda lib, d, arg, s: lib.mr_convt4x4s2_winograd_f32(d, s),
-    _lib.LAUNCH_WINO_1D: lambda lib, d, arg, s: lib.mr_conv1d3_winograd_f32(d, arg, s),
-    _lib.LAUNCH_UPCONV: lambda lib, d, arg, s: lib.mr_upconv2x2_winograd_f32(d, s),
-    _lib.LAUNCH_WINO44: lambda lib, d, arg, s: lib.mr_conv3x3_winograd44_f32(d, s),
-    _lib.LAUNCH_WINO44S: lambda lib, d, arg, s: lib.mr_conv3x3_winograd44s_f32(d, s),
-    _lib.LAUNCH_WINO44W: lambda lib, d, arg, s: lib.mr_conv3x3_winograd44w_f32(d, s),
-    _lib.LAUNCH_CONV_B8: lambda lib, d, arg, s: lib.mr_conv2d_b8(d, s),
-    _lib.LAUNCH_COOKTOOM_1D: lambda lib, d, arg, s: lib.mr_conv1d_cooktoom_f32(d, arg & 15, (arg >> 4) & 15, (arg >> 8) & 15, s),
-}
-
-# The 3x3 stride-1 reduced-multiply forms, by WINOGRAD code variant (decode_form("", code).variant): weight count / pack entries (taking the
-# code's mbw, or no parameter), LDS query, launch kind, output rows x columns x channels (x mbw where the entries take it) per workgroup, the
-# ck / waves conv_log reports, multiplies per output of the direct sum, and whether it is the tail form (32 a + 1..16 channels, mbw 1).
-Wino3x3Form = collections.namedtuple("Wino3x3Form", "count pack takes_mbw lds kind rows cols ch ck waves ratio tail")
-_W22, _W44 = ("mr_wino_packed_weight_floats", "mr_wino_pack_weights_f32"), ("mr_wino44_packed_weight_floats", "mr_wino44_pack_weights_f32")
+# One reduced-multiply form (csrc/conv_wino*.hip, convt_wino.hip, conv1d_wino.hip; every one fills a mr_wino_desc) as Plan._reduced builds it:
+#   count, pack   weight count / pack entries; `params`: which of (mbw, m, taps) they take behind the sources
+#   lds, lds_args LDS query and which of (axis, m, taps) it takes behind the descriptor
+#   kind, arg     LAUNCH_* kind and the fields of mr_launch_item.arg as (one of axis / m / taps, shift)
+#   rows, cols, ch  positions of the kernel's (height, width) plane x output channels (x mbw where the entries take it) per workgroup;
+#                 wgs_per_tile: workgroups per such tile (Refine: one per output parity)
+#   scale         destination plane / kernel plane (2: Refine, Upconv)
+#   k, pad, phases, ratio, ck, waves   what conv_log reports: filter and padding of the direct sum per phase, phases, multiplies per multiply of
+#                 the direct sum, channels per LDS chunk, waves per workgroup
+#   variant       mr_wino_desc.variant; tail: the form of 32 a + 1..16 channels (mbw 1); prefix: of the WINOGRAD key; log: conv_log keys of the family
+ReducedForm = collections.namedtuple(
+    "ReducedForm", "count pack params lds kind rows cols ch k ratio lds_args arg wgs_per_tile scale pad phases ck waves variant tail prefix axis m taps log",
+    defaults=((), (), 1, 1, (0, 0), 1, 8, 8, 0, False, "", 0, 0, 0, {}))
+_W22 = dict(count="mr_wino_packed_weight_floats", pack="mr_wino_pack_weights_f32", params=("mbw",), lds="mr_conv3x3_winograd_lds_bytes",
+            kind=_lib.LAUNCH_WINO3X3, rows=8, cols=32, ch=32, k=(3, 3), pad=(1, 1), ratio=(4, 9))
+_W44 = dict(count="mr_wino44_packed_weight_floats", pack="mr_wino44_pack_weights_f32", params=(), lds="mr_conv3x3_winograd44_lds_bytes",
+            kind=_lib.LAUNCH_WINO44, rows=16, cols=64, ch=32, k=(3, 3), pad=(1, 1), ratio=(1, 4))
+# The 3x3 stride-1 forms, by WINOGRAD code variant (decode_form("", code).variant)
 WINO3X3_FORMS = {
-    0: Wino3x3Form(*_W22, True, "mr_conv3x3_winograd_lds_bytes", _lib.LAUNCH_WINO3X3, 8, 32, 32, 8, 8, (4, 9), False),     # F(2x2,3x3), LDS buffer (conv_wino.hip)
-    1: Wino3x3Form(*_W22, True, "mr_conv3x3_winograd_lds_bytes", _lib.LAUNCH_WINO3X3, 8, 32, 32, 8, 8, (4, 9), False),     # input transform in registers
-    2: Wino3x3Form("mr_wino_packed_weight_floats_tail", "mr_wino_pack_weights_tail_f32", False, "mr_conv3x3_winograd_lds_bytes", _lib.LAUNCH_WINO3X3,
-                   8, 32, 32, 8, 8, (4, 9), True),            # 32 a + (1..16) channels: the tail by 16-row workgroups (conv_wino.hip: wino_rb_tail)
-    3: Wino3x3Form(*_W44, False, "mr_conv3x3_winograd44_lds_bytes", _lib.LAUNCH_WINO44, 16, 64, 32, 8, 8, (1, 4), False),  # F(4x4,3x3) (conv_wino44.hip)
-    4: Wino3x3Form("mr_wino44s_packed_weight_floats", "mr_wino44s_pack_weights_f32", False, "mr_conv3x3_winograd44s_lds_bytes", _lib.LAUNCH_WINO44S,
-                   8, 64, 32, 4, 8, (1, 4), False),           # F(4x4,3x3), a tile's positions over two waves: two workgroups per CU (conv_wino44s.hip)
-    5: Wino3x3Form(*_W44, False, "mr_conv3x3_winograd44w_lds_bytes", _lib.LAUNCH_WINO44W, 16, 64, 32, 4, 4, (1, 4), False),  # one wave per SIMD (conv_wino44w.hip)
+    0: ReducedForm(**_W22, variant=0),                                     # F(2x2,3x3), LDS buffer (conv_wino.hip)
+    1: ReducedForm(**_W22, variant=1),                                     # input transform in registers
+    2: ReducedForm(**dict(_W22, count="mr_wino_packed_weight_floats_tail", pack="mr_wino_pack_weights_tail_f32", params=()), variant=2,
+                   tail=True),                                             # 32 a + (1..16) channels: the tail by 16-row workgroups (conv_wino.hip: wino_rb_tail)
+    3: ReducedForm(**_W44, variant=3),                                     # F(4x4,3x3) (conv_wino44.hip)
+    4: ReducedForm(**dict(_W44, count="mr_wino44s_packed_weight_floats", pack="mr_wino44s_pack_weights_f32", lds="mr_conv3x3_winograd44s_lds_bytes",
+                          kind=_lib.LAUNCH_WINO44S, rows=8), variant=4, ck=4),   # F(4x4,3x3), a tile's positions over two waves: two workgroups per CU (conv_wino44s.hip)
+    5: ReducedForm(**dict(_W44, lds="mr_conv3x3_winograd44w_lds_bytes", kind=_lib.LAUNCH_WINO44W), variant=5, ck=4, waves=4),   # one wave per SIMD (conv_wino44w.hip)
 }
+# layers.Refine on mr_convt4x4s2_winograd_f32 (csrc/convt_wino.hip: F(2x2,2x2), 9 instead of 16 multiplies per 2x2 parity tile), by 't_' code variant
+_T22 = dict(count="mr_wino_t_packed_weight_floats", pack="mr_wino_t_pack_weights_f32", params=("mbw",), lds="mr_convt4x4s2_winograd_lds_bytes",
+            kind=_lib.LAUNCH_WINO_T, rows=8, cols=32, ch=32, k=(2, 2), ratio=(9, 16), wgs_per_tile=4, scale=2, phases=4, prefix="t_")
+REFINE_FORMS = {
+    0: ReducedForm(**_T22, variant=0),
+    1: ReducedForm(**_T22, variant=1),                                     # input transform in registers
+    2: ReducedForm(**dict(_T22, count="mr_wino_t_packed_weight_floats_tail", pack="mr_wino_t_pack_weights_tail_f32", params=()), variant=2,
+                   tail=True),                                             # 32 a + (1..16) output channels, the tail group by 16-row workgroups (convt_rb_tail)
+}
+# layers.Upconv on mr_upconv2x2_winograd_f32 (csrc/conv1d_wino.hip: 4 multiplies per 2x2 output block instead of the 9 of the four parity phases /
+# the 16 of the reference), 16 * mbw output channels per workgroup
+UPCONV_FORM = ReducedForm(count="mr_wino1d_packed_weight_floats", pack="mr_upconv_pack_weights_f32", params=("mbw",), lds="mr_conv1d3_winograd_lds_bytes",
+                          kind=_lib.LAUNCH_UPCONV, rows=8, cols=32, ch=16, k=(2, 2), ratio=(1, 4), scale=2, phases=4, prefix="u_", log=dict(upconv=True))
+
+
+def wino1d_prefix(axis, taps):
+    """WINOGRAD key prefix of a 1-D layer: 'x_' / 'y_' (3 taps along x / y), 'x7_' / 'y7_' (7 taps)."""
+    return ("x", "y")[axis] + ("" if taps == 3 else str(taps)) + "_"
+
+
+def wino1d_form(axis, m, taps):
+    """The form of a `taps`-tap stride-1 convolution along x (axis 0) / y (axis 1) with m outputs per tile: mr_conv1d3_winograd_f32 (csrc/conv1d_wino.hip:
+    F(2,3), 4 instead of 6 multiplies per output pair, 8 x 32 outputs per workgroup), every other (m, taps) mr_conv1d_cooktoom_f32 (F(m, taps):
+    m + taps - 1 multiplies per m outputs; 8 x 16 m (along x) / 4 m x 32 (along y) outputs per workgroup)."""
+    k = (1, taps) if axis == 0 else (taps, 1)
+    common = dict(ch=16, k=k, pad=(k[0] // 2, k[1] // 2), ratio=(m + taps - 1, m * taps), prefix=wino1d_prefix(axis, taps), axis=axis, m=m, taps=taps,
+                  log=dict(wino_axis=axis, wino_m=m, wino_taps=taps))
+    if (m, taps) == (2, 3):
+        return ReducedForm(count="mr_wino1d_packed_weight_floats", pack="mr_wino1d_pack_weights_f32", params=("mbw",), lds="mr_conv1d3_winograd_lds_bytes",
+                           kind=_lib.LAUNCH_WINO_1D, arg=(("axis", 0),), rows=8, cols=32, **common)
+    return ReducedForm(count="mr_cooktoom1d_packed_weight_floats", pack="mr_cooktoom1d_pack_weights_f32", params=("mbw", "m", "taps"),
+                       lds="mr_conv1d_cooktoom_lds_bytes", lds_args=("axis", "m", "taps"), kind=_lib.LAUNCH_COOKTOOM_1D,
+                       arg=(("axis", 0), ("m", 4), ("taps", 8)), rows=8 if axis == 0 else 4 * m, cols=16 * m if axis == 0 else 32, **common)
 
 
 def _conv_spec(**given):
@@ -283,7 +315,7 @@ def decode_form(prefix, code):
     per workgroup (32 each for 3x3 / Refine, 16 for 1-D / Upconv / stride-2).
       ''  3x3, 't_' Refine:             10 variant + mbw  (choose_winograd / choose_winograd_t)
       'x_' 'y_' 'x7_' 'y7_' 1-D:         10 m + mbw, m = 2 (F(2,3)) below 10  (choose_winograd_1d)
-      'u_' Upconv:                      mbw
+      'u_' Upconv:                      mbw  (choose_upconv)
       's2k<taps>_' stride-2 pair:        10 mbw (the k x 1 half) + mbw_x (the 1 x k half; 0: on the direct kernel)  (choose_stride2)"""
     if prefix in ("", "t_"):
         return FormCode(mbw=code % 10, variant=code // 10)
@@ -309,6 +341,15 @@ def nearest_form(prefix, cout, cin, pixels, batch, valid=lambda code: True, excl
     return None if best is None else best[2]
 
 
+def tabled_form(prefix, cout, src_channels, h, w, batch, valid):
+    """The lookup rule of every reduced-multiply family -> (code, key): the WINOGRAD entry of the layer's signature and that key; without an entry
+    the code of the nearest measured signature that is launchable here (nearest_form with `valid`; None when there is none) and no key."""
+    key = prefix + winograd_signature(cout, src_channels, h, w, batch)
+    if key in WINOGRAD:
+        return WINOGRAD[key], key
+    return nearest_form(prefix, cout, sum(src_channels), h * w, batch, valid=valid), None
+
+
 def choose_winograd(cout, src_channels, h, w, batch, f2=False):
     """0 = direct MFMA kernel, 1 / 2 = Winograd F(2x2,3x3) kernel (csrc/conv_wino.hip) with 32 / 64 output channels per workgroup,
     11 / 12 = the same with the input transform in registers (mr_wino_desc.variant = 1), 21 = variant 2 (11 whose 1..16 tail channels
@@ -320,12 +361,6 @@ def choose_winograd(cout, src_channels, h, w, batch, f2=False):
     the table (32 channels per workgroup: transform in registers, two workgroups per CU; 64: the LDS buffer)."""
     if w % 4:
         return 0
-    sig = winograd_signature(cout, src_channels, h, w, batch)
-    if sig in WINOGRAD:
-        code = WINOGRAD[sig]
-        if f2 and decode_form("", code).variant in (3, 4, 5):     # F(4x4,3x3), any kernel -> the F(2x2,3x3) variant measured before it (else: transform in registers, 32 channels)
-            code = WINOGRAD_F2.get(sig, 11)
-        return code
 
     def ok(code):
         f = decode_form("", code)
@@ -336,10 +371,10 @@ def choose_winograd(cout, src_channels, h, w, batch, f2=False):
         if f.variant in (0, 1):
             return f.mbw == 1 or cout > 32
         return f.variant in (3, 4, 5)
-    code = nearest_form("", cout, sum(src_channels), h * w, batch, valid=ok)
+    code, key = tabled_form("", cout, src_channels, h, w, batch, ok)
     if code is not None:
-        if f2 and decode_form("", code).variant in (3, 4, 5):
-            code = 11
+        if f2 and decode_form("", code).variant in (3, 4, 5):     # F(4x4,3x3), any kernel -> the F(2x2,3x3) variant measured before it (else: transform in registers, 32 channels)
+            code = WINOGRAD_F2.get(key, 11)
         return code
     tiles = math.ceil(h / 8) * math.ceil(w / 32) * batch
     if tiles * math.ceil(cout / 32) < 256:
@@ -354,15 +389,7 @@ def choose_winograd_t(cout, src_channels, h, w, batch):
     know stay on the direct kernel."""
     if w % 4:
         return 0
-    key = "t_" + winograd_signature(cout, src_channels, h, w, batch)
-    if key in WINOGRAD:
-        return WINOGRAD[key]
-    return nearest_form("t_", cout, sum(src_channels), h * w, batch, valid=lambda c: c == 0 or decode_form("t_", c).mbw * 32 <= max(32, cout)) or 0
-
-
-def wino1d_prefix(axis, taps):
-    """WINOGRAD key prefix of a 1-D layer: 'x_' / 'y_' (3 taps along x / y), 'x7_' / 'y7_' (7 taps)."""
-    return ("x", "y")[axis] + ("" if taps == 3 else str(taps)) + "_"
+    return tabled_form("t_", cout, src_channels, h, w, batch, lambda c: decode_form("t_", c).mbw * 32 <= max(32, cout))[0] or 0
 
 
 def choose_winograd_1d(axis, cout, src_channels, h, w, batch, taps=3, f2=False):
@@ -374,16 +401,10 @@ def choose_winograd_1d(axis, cout, src_channels, h, w, batch, taps=3, f2=False):
     if w % 4:
         return 0
     prefix = wino1d_prefix(axis, taps)
-    key = prefix + winograd_signature(cout, src_channels, h, w, batch)
-    if key in WINOGRAD:
-        code = WINOGRAD[key]
-    else:                                    # no entry: the form of the nearest measured signature of the same axis / tap count
-        code = nearest_form(prefix, cout, sum(src_channels), h * w, batch, valid=lambda c: c == 0 or decode_form(prefix, c).mbw <= math.ceil(cout / 16)) or 0
-        if f2 and decode_form(prefix, code).m >= 4:
-            return 0
-    if f2 and decode_form(prefix, code).m >= 4:     # F(4,.) -> what was measured best among F(2,.) and the direct kernel before the larger forms
-        code = WINOGRAD_F2.get(key, 0)
-    return code
+    code, key = tabled_form(prefix, cout, src_channels, h, w, batch, lambda c: decode_form(prefix, c).mbw <= math.ceil(cout / 16))
+    if f2 and decode_form(prefix, code or 0).m >= 4:     # F(4,.) -> what was measured best among F(2,.) and the direct kernel before the larger forms (no entry: the direct kernel)
+        return WINOGRAD_F2.get(key, 0)
+    return code or 0
 
 
 def stride2_signature(taps, cout, cin, out_h, out_w, batch):
@@ -397,12 +418,17 @@ def choose_stride2(taps, cout, cin, out_h, out_w, batch):
     kernel), or 0 = both halves on the direct MFMA kernel.  Only what the measured table says (tools/bench_stride2.py --emit; keys `s2k<taps>_co<cout>_ci<cin>_o<out_h>x<out_w>_b<batch>`)."""
     if taps not in (5, 7) or out_w % 4:
         return 0
-    key = stride2_signature(taps, cout, cin, out_h, out_w, batch)
-    if key in WINOGRAD:
-        return WINOGRAD[key]
-    cb = math.ceil(cout / 16)
-    return nearest_form(f"s2k{taps}_", cout, cin, out_h * out_w, batch,
-                        valid=lambda c: c == 0 or (decode_form("s2k", c).mbw <= cb and decode_form("s2k", c).mbw_x <= cb)) or 0
+    cb = math.ceil(cout / 16)      # (the key tabled_form looks up is stride2_signature's)
+    return tabled_form(f"s2k{taps}_", cout, [cin], out_h, out_w, batch,
+                       lambda c: decode_form("s2k", c).mbw <= cb and decode_form("s2k", c).mbw_x <= cb)[0] or 0
+
+
+def choose_upconv(cout, src_channels, h, w, batch):
+    """layers.Upconv on an input of h x w: 0 = the four parity phases on the direct MFMA kernel, 1.. = mr_upconv2x2_winograd_f32 (csrc/conv1d_wino.hip)
+    with 16 x that many output channels per workgroup.  Only what the measured table says (tools/bench_wino1d.py --emit; keys prefixed `u_`)."""
+    if w % 4:
+        return 0
+    return tabled_form("u_", cout, src_channels, h, w, batch, lambda c: decode_form("u_", c).mbw <= math.ceil(cout / 16))[0] or 0
 
 
 def stride2_unified_weights(w, n, axis):
@@ -637,7 +663,6 @@ class Plan:
         self._pending_ws = []     # so every stage gets its own split-K workspace
         self.bound = {}           # output buffer name -> base pointer its launches currently use (rebind_outputs)
         self._relocs = []         # (ctypes object, field name, index or None, output buffer name, byte offset): see _index_outputs
-        self._ptr_arrays = []     # ctypes pointer arrays handed to launches (scanned by _index_outputs)
         if build:
             self._build()
             self.finalize()
@@ -688,9 +713,10 @@ class Plan:
         return _Ref(self, name, off, t.data_ptr())
 
     def _index_outputs(self):
-        """Relocation table of the output buffers: every pointer slot of a descriptor (or of a pointer array handed to a launch) that
-        points into one of OUTPUT_BUFFERS, found by address.  Descriptors are referenced by the native launch lists, so patching
-        them in place re-targets the launches."""
+        """Relocation table of the output buffers: every pointer slot of what `keep` holds for the launches - the c_void_p fields and
+        c_void_p array elements of a descriptor or of an array of descriptors, the elements of a pointer array handed to a launch - that
+        points into one of OUTPUT_BUFFERS, found by field type and address: a pointer field added to a descriptor is covered without being
+        named here.  Descriptors are referenced by the native launch lists, so patching them in place re-targets the launches."""
         self.bound = {n: self.buf[n].data_ptr() for n in OUTPUT_BUFFERS if n in self.buf}
         self._resident = dict(self.bound)
         self._relocs = []
@@ -702,26 +728,23 @@ class Plan:
             name, off = self._out_range(int(ptr))
             if name is not None:
                 self._relocs.append((obj, field, idx, name, off))
+
+        def elements(obj, field, array):
+            for i in range(len(array)):
+                slot(obj, field, i, array[i])
         for obj in self.keep:
-            if id(obj) in seen:
+            if id(obj) in seen or not isinstance(obj, (ctypes.Structure, ctypes.Array)):
                 continue
             seen.add(id(obj))
-            if isinstance(obj, (ConvDesc, WinoDesc)):
-                for i in range(obj.num_src):
-                    slot(obj, "src", i, obj.src[i])
-                slot(obj, "dst", None, obj.dst)
-                slot(obj, "residual", None, obj.residual)
-            elif isinstance(obj, B8ConvDesc):
-                for i in range(obj.num_src):
-                    slot(obj, "src", i, obj.src[i])
-                slot(obj, "dst", None, obj.dst)
-            elif isinstance(obj, ctypes.Array) and getattr(obj, "_type_", None) is HeadDesc:
-                for i in range(len(obj)):
-                    slot(obj[i], "src", None, obj[i].src)
-                    slot(obj[i], "dst", None, obj[i].dst)
-        for arr in self._ptr_arrays:
-            for i in range(len(arr)):
-                slot(arr, None, i, arr[i])
+            if isinstance(obj, ctypes.Array) and obj._type_ is ctypes.c_void_p:
+                elements(obj, None, obj)
+                continue
+            for desc in ([obj] if isinstance(obj, ctypes.Structure) else obj if issubclass(obj._type_, ctypes.Structure) else ()):
+                for field, ftype in desc._fields_:
+                    if ftype is ctypes.c_void_p:
+                        slot(desc, field, None, getattr(desc, field))
+                    elif issubclass(ftype, ctypes.Array) and ftype._type_ is ctypes.c_void_p:
+                        elements(desc, field, getattr(desc, field))
 
     def rebind_outputs(self, bases=None):
         """Point every launch at `bases[name]` (device pointers of caller-owned memory, one per output buffer, same layout) - or, with
@@ -769,17 +792,19 @@ class Plan:
     def _emit(self, stage, name, desc, kind, arg=0, keep=()):
         """Append one native launch: `desc` (ConvDesc / WinoDesc / B8ConvDesc, complete) run by the C-ABI entry of LAUNCH_* `kind`.  Its
         keyframe source slots follow bind_inputs; the descriptor and `keep` (what its raw pointers name) live as long as the plan.  The
-        closure runs the launch on its own (tools call plan.stages[...][i][1](stream)); run_stage folds runs of such closures into one
-        mr_run_launches call through `.native`."""
+        closure runs the launch on its own (tools call plan.stages[...][i][1](stream)) as a mr_run_launches list of one item; run_stage
+        folds runs of such closures into one mr_run_launches call through `.native`."""
         kf = self.buf.get("keyframe")
         for i in range(desc.num_src):
             if kf is not None and desc.src[i] == kf.data_ptr():
                 self._input_srcs.append((desc, i, "keyframe"))
-        self.keep += [desc] + list(keep)
-        lib, entry = self.lib, _NATIVE_ENTRY[kind]
+        item = (_lib.LaunchItem * 1)()
+        item[0].kind, item[0].arg, item[0].desc = kind, arg, ctypes.addressof(desc)
+        self.keep += [desc, item] + list(keep)
+        lib = self.lib
 
         def run(stream):
-            _lib.check(entry(lib, ctypes.byref(desc), arg, stream), name)
+            _lib.check(lib.mr_run_launches(item, 1, stream, None), name)
         run.native = (kind, desc, arg)
         self.stages[stage].append((name, run))
 
@@ -829,7 +854,8 @@ class Plan:
         if dense and (kh, kw) == (3, 3) and tuple(pad) == (1, 1):
             code = choose_winograd(cout, src_channels, hs, ws, n, f2=self.conv_forms == "f2")
             if code:
-                return self._conv_winograd(stage, name, srcs, weight, bias, out, act, p0, residual, decode_form("", code))
+                f = decode_form("", code)
+                return self._reduced(stage, name, WINO3X3_FORMS[f.variant], f.mbw, srcs, weight, cout, bias, out, act, p0, residual)
         if dense and (kh, kw) in ((1, 3), (3, 1), (1, 7), (7, 1)) and tuple(pad) == (kh // 2, kw // 2) and residual is None:
             axis, taps = (0 if kh == 1 else 1), max(kh, kw)
             code = choose_winograd_1d(axis, cout, src_channels, hs, ws, n, taps, f2=self.conv_forms == "f2")
@@ -907,77 +933,57 @@ class Plan:
         self._emit(stage, name, d, _lib.LAUNCH_CONV2D, keep=[out, residual] + list(srcs))
         return out
 
-    def _conv_winograd(self, stage, name, srcs, weight, bias, out, act, p0, residual, form):
-        """One launch of the 3x3 stride-1 reduced-multiply form WINO3X3_FORMS[form.variant] in place of a mr_conv2d_f32 launch."""
-        rec, mbw = WINO3X3_FORMS[form.variant], form.mbw
-        n, hs, ws, src_channels = self._dense_srcs(srcs)
-        cout, cin = int(weight.shape[0]), int(weight.shape[1])
-        assert not rec.tail or (mbw == 1 and 0 < cout % 32 <= 16), (name, cout)
-        packed = pack_weights(rec.count, rec.pack, weight, cout, _int32s(src_channels), len(src_channels), *((mbw,) if rec.takes_mbw else ()))
-        assert out.is_contiguous() and tuple(out.shape) == (n, cout, hs, ws)
-        d = self._wino_desc([s_.data_ptr() for s_ in srcs], src_channels, n, hs, ws, out, cout, packed, bias, act, p0, mbw, form.variant)
-        if residual is not None:
-            assert residual.shape == out.shape
-            d.residual = residual.data_ptr()
-        lds = self._check_lds(getattr(self.lib, rec.lds)(ctypes.byref(d)), f"plan {name} winograd")
-        ref = n * hs * ws * cout * cin * 9
-        wg_ch = rec.ch * (mbw if rec.takes_mbw else 1)
-        self._log(name, macs=ref * rec.ratio[0] // rec.ratio[1], ref_macs=ref, mb=mbw, ck=rec.ck, waves=rec.waves,
-                  wgs=math.ceil(hs / rec.rows) * math.ceil(ws / rec.cols) * n * math.ceil(cout / wg_ch), lds=lds, cout=cout, cin=cin, k=(3, 3),
-                  out=(hs, ws), batch=n, winograd=mbw, wino_variant=form.variant, sig=winograd_signature(cout, src_channels, hs, ws, n),
-                  spec=_conv_spec(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 3, 3), pad=(1, 1), grid=(hs, ws), act=act, p0=p0,
-                                  residual=residual is not None, out_shape=tuple(out.shape)))
-        self._emit(stage, name, d, rec.kind, keep=[out, residual] + list(srcs))
-        return out
-
-    def _conv_winograd_1d(self, stage, name, srcs, weight, bias, out, act, p0, axis, mbw, m=2, view=None, dst_split=False, ref_macs=None, ref_k=None,
-                          sig=None):
-        """One mr_conv1d3_winograd_f32 launch (csrc/conv1d_wino.hip: F(2,3), 4 instead of 6 multiplies per output pair) - or, for m = 4 or
-        7 taps, one mr_conv1d_cooktoom_f32 launch (F(m, taps): m + taps - 1 multiplies per m outputs) - in place of a k x 1 / 1 x k
-        stride-1 mr_conv2d_f32 launch."""
+    def _reduced(self, stage, name, rec, mbw, srcs, weight, cout, bias, out, act, p0, residual=None, *, view=None, dst_split=False, ref_macs=None,
+                 ref_k=None, stride=(1, 1), sig=None, **log):
+        """One launch of the reduced-multiply form `rec` (ReducedForm) with `mbw` blocks of output channels per workgroup, in place of a
+        mr_conv2d_f32 launch.  `weight` in the layout rec.pack takes; `log`: further conv_log keys of the caller.  The stride-2 halves
+        (_conv_relu2_stride2) pass `view` - strided source views, dict(ptrs, channels, batch, height, width, row_pitch, plane): `srcs` then only
+        keeps the underlying tensors alive -, `dst_split` - out = (2, n, cout, hs, ws / 2): even columns, odd columns -, and `ref_macs` /
+        `ref_k` / `stride` / `sig`: the reference's multiply-adds, filter and stride and the pair's table key, for conv_log."""
         if view is None:
             n, hs, ws, src_channels = self._dense_srcs(srcs)
             src_ptrs = [s_.data_ptr() for s_ in srcs]
         else:
-            # strided source views (the k x 1 stride-(2,1) half of a ConvReLU2 pair as a stride-1 form over [even rows | odd rows]):
-            # view = dict(ptrs, channels, batch, height, width, row_pitch, plane) - `srcs` only keeps the underlying tensors alive
             n, hs, ws = view["batch"], view["height"], view["width"]
             src_channels, src_ptrs = list(view["channels"]), list(view["ptrs"])
-        cout, cin = int(weight.shape[0]), int(weight.shape[1])
-        taps = int(weight.shape[3] if axis == 0 else weight.shape[2])
-        assert tuple(weight.shape[2:]) == ((1, taps) if axis == 0 else (taps, 1)) and cin == sum(src_channels), (name, weight.shape)
-        general = (m, taps) != (2, 3)
-        if general:         # Cook-Toom F(m, taps): 8 x 16 m (along x) / 4 m x 32 (along y) outputs per workgroup
-            count, pack, params = "mr_cooktoom1d_packed_weight_floats", "mr_cooktoom1d_pack_weights_f32", (mbw, m, taps)
-            kind, arg, (rh, rw) = _lib.LAUNCH_COOKTOOM_1D, axis | (m << 4) | (taps << 8), ((8, 16 * m) if axis == 0 else (4 * m, 32))
-        else:               # F(2,3): 8 x 32 outputs per workgroup
-            count, pack, params = "mr_wino1d_packed_weight_floats", "mr_wino1d_pack_weights_f32", (mbw,)
-            kind, arg, (rh, rw) = _lib.LAUNCH_WINO_1D, axis, (8, 32)
-        packed = pack_weights(count, pack, weight, cout, _int32s(src_channels), len(src_channels), *params)
-        if dst_split:            # (2, n, cout, hs, ws / 2): even columns, odd columns - the two sources of the 1 x k stride-(1,2) half
-            assert general and axis == 1 and out.is_contiguous() and tuple(out.shape) == (2, n, cout, hs, ws // 2), (name, tuple(out.shape))
-        else:
-            assert out.is_contiguous() and tuple(out.shape) == (n, cout, hs, ws)
-        d = self._wino_desc(src_ptrs, src_channels, n, hs, ws, out, cout, packed, bias, act, p0, mbw)
+        cin = sum(src_channels)
+        assert {int(weight.shape[0]), int(weight.shape[1])} == {cout, cin}, (name, weight.shape, src_channels)
+        assert not rec.tail or (mbw == 1 and 0 < cout % 32 <= 16), (name, cout)
+        given = dict(mbw=mbw, axis=rec.axis, m=rec.m, taps=rec.taps)
+        packed = pack_weights(rec.count, rec.pack, weight, cout, _int32s(src_channels), len(src_channels), *[given[p] for p in rec.params])
+        assert out.is_contiguous() and tuple(out.shape) == ((2, n, cout, hs, ws // 2) if dst_split else (n, cout, rec.scale * hs, rec.scale * ws)), \
+            (name, tuple(out.shape))
+        d = self._wino_desc(src_ptrs, src_channels, n, hs, ws, out, cout, packed, bias, act, p0, mbw, rec.variant)
         d.dst_split_columns = int(dst_split)
         if view is not None:
-            assert general, name
             d.src_row_pitch, d.src_plane_floats = int(view["row_pitch"]), int(view["plane"])
-        lds = self._check_lds(self.lib.mr_conv1d_cooktoom_lds_bytes(ctypes.byref(d), axis, m, taps) if general else
-                              self.lib.mr_conv1d3_winograd_lds_bytes(ctypes.byref(d)), f"plan {name} winograd-1d")
-        ref = n * hs * ws * cout * cin * taps
-        kk = (1, taps) if axis == 0 else (taps, 1)
-        # (ref_macs / ref_k: the reference's multiply-adds and filter of a stride-2 layer run as a stride-1 form over [even | odd] - the unified
-        # filter has 2 * ceil(k / 2) >= k taps per input channel, of which the padded one is a zero weight)
-        self._log(name, macs=ref * (m + taps - 1) // (m * taps), ref_macs=ref if ref_macs is None else ref_macs, mb=mbw,
-                  wgs=math.ceil(hs / rh) * math.ceil(ws / rw) * n * math.ceil(cout / (16 * mbw)), lds=lds, cout=cout, cin=cin,
-                  k=kk if ref_k is None else ref_k, out=(hs, ws), batch=n, winograd=mbw, wino_variant=0, wino_axis=axis, wino_m=m, wino_taps=taps,
-                  stride2=ref_k is not None, sig=sig or (wino1d_prefix(axis, taps) + winograd_signature(cout, src_channels, hs, ws, n)),
-                  spec=_conv_spec(src_shapes=[(n, c_, hs, ws) for c_ in src_channels], w_shape=(cout, cin) + kk,
-                                  stride=(1, 1) if ref_k is None else ((2, 1) if axis == 1 else (1, 2)), pad=(kk[0] // 2, kk[1] // 2),
-                                  grid=(hs, ws), act=act, p0=p0, out_shape=tuple(out.shape)))
-        self._emit(stage, name, d, kind, arg, keep=[out] + list(srcs))
+        if residual is not None:
+            assert residual.shape == out.shape
+            d.residual = residual.data_ptr()
+        lds = self._check_lds(getattr(self.lib, rec.lds)(ctypes.byref(d), *[given[a] for a in rec.lds_args]), f"plan {name} {rec.lds}")
+        ref = n * hs * ws * cout * cin * rec.k[0] * rec.k[1] * rec.phases
+        wg_ch = rec.ch * (mbw if "mbw" in rec.params else 1)
+        self._log(name, macs=ref * rec.ratio[0] // rec.ratio[1], ref_macs=ref if ref_macs is None else ref_macs, mb=mbw, ck=rec.ck, waves=rec.waves,
+                  wgs=math.ceil(hs / rec.rows) * math.ceil(ws / rec.cols) * n * rec.wgs_per_tile * math.ceil(cout / wg_ch), lds=lds, cout=cout, cin=cin,
+                  k=rec.k if ref_k is None else ref_k, out=(hs, ws), batch=n, phases=rec.phases, winograd=mbw, wino_variant=rec.variant, **rec.log, **log,
+                  sig=sig or rec.prefix + winograd_signature(cout, src_channels, hs, ws, n),
+                  spec=_conv_spec(src_shapes=[(n, c_, hs, ws) for c_ in src_channels], w_shape=(cout, cin) + rec.k, stride=stride, pad=rec.pad,
+                                  grid=(hs, ws), act=act, p0=p0, residual=residual is not None, out_shape=tuple(out.shape),
+                                  out_step=(rec.scale, rec.scale)))
+        self._emit(stage, name, d, rec.kind, sum(given[f] << shift for f, shift in rec.arg), keep=[out, residual] + list(srcs))
         return out
+
+    def _conv_winograd_1d(self, stage, name, srcs, weight, bias, out, act, p0, axis, mbw, m=2, view=None, dst_split=False, ref_macs=None, ref_k=None,
+                          sig=None):
+        """One launch of wino1d_form(axis, m, taps) in place of a k x 1 / 1 x k stride-1 mr_conv2d_f32 launch.  (ref_macs / ref_k: the
+        reference's multiply-adds and filter of a stride-2 layer run as a stride-1 form over [even | odd] - the unified filter has
+        2 * ceil(k / 2) >= k taps per input channel, of which the padded one is a zero weight.)"""
+        rec = wino1d_form(axis, m, int(weight.shape[3] if axis == 0 else weight.shape[2]))
+        assert tuple(weight.shape[2:]) == rec.k, (name, weight.shape)
+        # strided views and the column-split destination (of a k x 1 half) are the Cook-Toom kernel's
+        assert (view is None and not dst_split) or (rec.kind == _lib.LAUNCH_COOKTOOM_1D and (axis == 1 or not dst_split)), name
+        return self._reduced(stage, name, rec, mbw, srcs, weight, int(weight.shape[0]), bias, out, act, p0, view=view, dst_split=dst_split, ref_macs=ref_macs,
+                             ref_k=ref_k, stride=(1, 1) if ref_k is None else ((2, 1) if axis == 1 else (1, 2)), sig=sig, stride2=ref_k is not None)
 
     @staticmethod
     def _b8_operands(srcs, out):
@@ -1055,26 +1061,10 @@ class Plan:
         b8 = self._b8_operands(srcs, out)
         if not b8 and self.winograd and self.bf16 == 0 and name not in self.schedule_override and tuple(out.shape[2:]) == (2 * h, 2 * w):
             code = choose_winograd_t(int(wt.shape[1]), [int(s_.shape[1]) for s_ in srcs], h, w, int(srcs[0].shape[0]))
-            if code:        # one mr_convt4x4s2_winograd_f32 launch (csrc/convt_wino.hip: F(2x2,2x2), 9 instead of 16 multiplies per 2x2 parity tile)
+            if code:
                 form = decode_form("t_", code)
-                n, hs, ws, src_channels = self._dense_srcs(srcs)
-                cin, cout = int(wt.shape[0]), int(wt.shape[1])
-                assert cin == sum(src_channels) and tuple(wt.shape[2:]) == (4, 4), (name, wt.shape, src_channels)
-                mbw, tail = form.mbw, form.variant == 2   # tail: 32 a + (1..16) output channels, the tail group by 16-row workgroups (convt_rb_tail)
-                assert not tail or (mbw == 1 and 0 < cout % 32 <= 16), (name, cout)
-                entries = ("mr_wino_t_packed_weight_floats_tail", "mr_wino_t_pack_weights_tail_f32") if tail else ("mr_wino_t_packed_weight_floats", "mr_wino_t_pack_weights_f32")
-                packed = pack_weights(*entries, wt, cout, _int32s(src_channels), len(src_channels), *(() if tail else (mbw,)))
-                assert out.is_contiguous() and tuple(out.shape) == (n, cout, 2 * hs, 2 * ws)
-                d = self._wino_desc([s_.data_ptr() for s_ in srcs], src_channels, n, hs, ws, out, cout, packed, bias, ACT_LEAKY_RELU, LEAKY_SLOPE, mbw, form.variant)
-                lds = self._check_lds(self.lib.mr_convt4x4s2_winograd_lds_bytes(ctypes.byref(d)), f"plan {name} winograd-t")
-                ref = n * hs * ws * cout * cin * 16
-                self._log(name, macs=ref * 9 // 16, ref_macs=ref, mb=mbw, wgs=math.ceil(hs / 8) * math.ceil(ws / 32) * n * 4 * math.ceil(cout / (32 * mbw)),
-                          lds=lds, cout=cout, cin=cin, k=(2, 2), out=(hs, ws), batch=n, phases=4, winograd=mbw, wino_variant=form.variant,
-                          sig="t_" + winograd_signature(cout, src_channels, hs, ws, n),
-                          spec=_conv_spec(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 2, 2), grid=(hs, ws), act=ACT_LEAKY_RELU,
-                                          p0=LEAKY_SLOPE, out_shape=tuple(out.shape), out_step=(2, 2)))
-                self._emit(stage, name, d, _lib.LAUNCH_WINO_T, keep=[out] + list(srcs))
-                return out
+                assert tuple(wt.shape[2:]) == (4, 4), (name, wt.shape)
+                return self._reduced(stage, name, REFINE_FORMS[form.variant], form.mbw, srcs, wt, int(wt.shape[1]), bias, out, ACT_LEAKY_RELU, LEAKY_SLOPE)
         phases = [(wp, pt, pl, py, px) for (py, px), (wp, pt, pl) in transposed_phase_weights(wt).items()]
         return (self.conv_b8 if b8 else self.conv)(stage, name, srcs, None, bias, out, grid=(h, w), act=ACT_LEAKY_RELU, p0=LEAKY_SLOPE,
                                                     out_step=(2, 2), phases=phases)
@@ -1087,27 +1077,12 @@ class Plan:
         cout, cin = self.sd[wkey].shape[:2]
         bias = self.sd[bkey] if bkey else None
         b8 = self._b8_operands(srcs, out)
-        if not b8 and self.winograd and self.bf16 == 0 and name not in self.schedule_override and w % 4 == 0 and tuple(out.shape[2:]) == (2 * h, 2 * w):
-            ukey = "u_" + winograd_signature(int(cout), [int(s_.shape[1]) for s_ in srcs], h, w, int(srcs[0].shape[0]))
-            code = WINOGRAD[ukey] if ukey in WINOGRAD else (nearest_form("u_", int(cout), int(cin), h * w, int(srcs[0].shape[0]),
-                                                                         valid=lambda c: decode_form("u_", c).mbw <= math.ceil(int(cout) / 16)) or 0)
-            if code:       # measured table (tools/bench_wino1d.py --emit): one mr_upconv2x2_winograd_f32 launch (csrc/conv1d_wino.hip: 4 multiplies per
-                # 2x2 output block instead of the 9 of the four parity phases / the 16 of the reference), 16 * mbw output channels per workgroup
-                weight, mbw = self.sd[wkey], decode_form("u_", code).mbw
-                n, hs, ws, src_channels = self._dense_srcs(srcs)
-                assert tuple(weight.shape[2:]) == (2, 2) and cin == sum(src_channels), (name, weight.shape)
-                packed = pack_weights("mr_wino1d_packed_weight_floats", "mr_upconv_pack_weights_f32", weight, cout, _int32s(src_channels), len(src_channels), mbw)
-                assert out.is_contiguous() and tuple(out.shape) == (n, cout, 2 * hs, 2 * ws)
-                d = self._wino_desc([s_.data_ptr() for s_ in srcs], src_channels, n, hs, ws, out, cout, packed, bias, ACT_NONE, 0.0, mbw)
-                lds = self._check_lds(self.lib.mr_conv1d3_winograd_lds_bytes(ctypes.byref(d)), f"plan {name} upconv-winograd")
-                ref = n * 4 * hs * ws * cout * cin * 4
-                self._log(name, macs=ref // 4, ref_macs=ref, mb=mbw, wgs=math.ceil(hs / 8) * math.ceil(ws / 32) * n * math.ceil(cout / (16 * mbw)), lds=lds,
-                          cout=cout, cin=cin, k=(2, 2), out=(hs, ws), batch=n, phases=4, winograd=mbw, wino_variant=0, upconv=True,
-                          sig="u_" + winograd_signature(cout, src_channels, hs, ws, n),
-                          spec=_conv_spec(src_shapes=[tuple(s_.shape) for s_ in srcs], w_shape=(cout, cin, 2, 2), grid=(hs, ws), out_shape=tuple(out.shape),
-                                          out_step=(2, 2)))
-                self._emit(stage, name, d, _lib.LAUNCH_UPCONV, keep=[out] + list(srcs))
-                return out
+        if not b8 and self.winograd and self.bf16 == 0 and name not in self.schedule_override and tuple(out.shape[2:]) == (2 * h, 2 * w):
+            code = choose_upconv(int(cout), [int(s_.shape[1]) for s_ in srcs], h, w, int(srcs[0].shape[0]))
+            if code:
+                weight = self.sd[wkey]
+                assert tuple(weight.shape[2:]) == (2, 2), (name, weight.shape)
+                return self._reduced(stage, name, UPCONV_FORM, decode_form("u_", code).mbw, srcs, weight, cout, bias, out, ACT_NONE, 0.0)
         phases = [(wp, 0, 0, py, px) for (py, px), wp in upconv_phase_weights(self.sd[wkey]).items()]
         return (self.conv_b8 if b8 else self.conv)(stage, name, srcs, None, bias, out, grid=(h, w), act=ACT_NONE, out_step=(2, 2), phases=phases,
                                                     ref_macs=srcs[0].shape[0] * 4 * h * w * cout * cin * 4)
@@ -1275,8 +1250,7 @@ class Plan:
         cv = self.alloc("cost_volume", B, D, H, W)
         frame_ptrs = (ctypes.c_void_p * F)(*[frames[f].data_ptr() for f in range(F)])
         sfcv_ptrs = (ctypes.c_void_p * F)(*[sfcv[f].data_ptr() for f in range(F)])
-        self.keep += [frame_ptrs, sfcv_ptrs]
-        self._ptr_arrays.append(sfcv_ptrs)
+        self.keep += [frame_ptrs, sfcv_ptrs]       # (sfcv_ptrs follows rebind_outputs: _index_outputs scans the pointer arrays in `keep`)
         self._frame_ptrs = frame_ptrs
         kinv, proj, depths = self.buf["kinv"], self.buf["proj"], self.buf["depths"]
         cv_ref = self.ref(cv)
