@@ -23,7 +23,10 @@
 // Arithmetic follows the reference operation by operation with contraction disabled
 // (-ffp-contract=off) and explicit fmaf where the CPU reference fuses (MKL sgemm k-ascending FMA
 // chain; ATen grid_sampler unnormalise + bilinear FMA chain; see oracle/make_golden.py for the
-// bitwise pinning), so the projection, the warped samples and the validity mask reproduce the CPU bits.  Two places are within an ulp
+// bitwise pinning), so the projection, the warped samples and the validity mask reproduce the CPU bits - of a host whose MKL fuses the
+// multiply-adds of the two small matrix products (the Intel hosts of the reference fixtures).  MKL on an AMD EPYC host keeps the k-ascending
+// order but rounds every product and sum: its grid is an ulp from this one on about a third of the entries, inside every bar, no validity
+// flipped (tests/test_cost_volume_geometry.py probes which host it runs on and pins both forms).  Two places are within an ulp
 // instead (round 3): the SSIM ratio (v_rcp_f32 + multiply, ssim_ratio below: sad moves by <= 1e-7; single-frame volumes stay
 // <= 2e-6 from the reference fixtures) and nothing else.  A non-finite u / v (pz + 1e-7 == 0) goes through div_const's fast path as NaN
 // and leaves the clamp as -2 where the reference's +-inf leaves it as +-2: both are outside the image on the same side of the validity

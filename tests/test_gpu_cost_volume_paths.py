@@ -87,15 +87,17 @@ def _guarded(elems, guard, dtype=torch.float32):
     return torch.full((elems + guard,), float("nan"), device=DEV, dtype=dtype)
 
 
-def _run(lib, k, entry, batch, pix):
-    """One launch of `entry` with the options of case `k` on (batch, pix).  Returns dict(cv, sf [, b8]) on the CPU after checking the guards."""
+def _run(lib, k, entry, batch, pix, depths=None):
+    """One launch of `entry` with the options of case `k` on (batch, pix).  Returns dict(cv, sf [, b8]) on the CPU after checking the guards.
+    `depths`: the hypothesis ladder (D) when it is not the model's."""
     kf = batch["keyframe"].to(DEV)
     b, _, h, w = kf.shape
     nf, d = len(batch["frames"]), k.d
     frames = [f.to(DEV).contiguous() for f in batch["frames"]]
     kinv, proj = host_geometry(batch["keyframe_intrinsics"], batch["keyframe_pose"], batch["intrinsics"], batch["poses"])
     kinv, proj = kinv.to(DEV), proj.to(DEV)
-    depths = depth_hypotheses((0.33, 0.0025), d).to(DEV)
+    depths = (depth_hypotheses((0.33, 0.0025), d) if depths is None else depths).to(DEV).contiguous()
+    assert depths.shape == (d,) and depths.dtype == torch.float32
     pixd = None if pix is None else pix.to(DEV).contiguous()
     n, g = b * d * h * w, h * w
     backing = [_guarded(n, g) for _ in range(nf + 1)]
@@ -144,8 +146,9 @@ def _same_outputs(got, want, what, b8=True):
             assert torch.equal(x.view(torch.int16), y.view(torch.int16)), f"{what} B8 copy {f}"
 
 
-def _oracle_leg(k, got, batch, pix):
-    ocv, osf = cp.oracle_of(k, batch, pix)
+def _oracle_leg(k, got, batch, pix, oracle=None):
+    """`oracle`: (cost volume, single-frame volumes) of cp.oracle_of(k, batch, pix) when the caller has them already."""
+    ocv, osf = cp.oracle_of(k, batch, pix) if oracle is None else oracle
     bars = cp.bars(k)
     report, ok_all = [], True
     for f in range(k.f):
@@ -171,26 +174,20 @@ def _oracle_leg(k, got, batch, pix):
     assert 0.2 < float((got["cv"] != 0).any(1).float().mean()) < 1.0          # not trivially all-invalid
 
 
-@pytest.mark.parametrize("name", [k.name for k in cp.CASES])
-def test_cost_volume_path(hip_lib, name):
-    k = cp.BY_NAME[name]
-    L = cp.query(hip_lib, k.f, k.b, k.d, k.h, k.w, k.use_ssim, k.pixd, k.mult_mask, k.patch, tiled=k.entry == "tiled", b8=k.entry in ("b8", "lean"),
-                 relaxed=k.entry == "relaxed", lean=k.entry == "lean")
-    assert cp.launched(L)[:2] == (k.sad, k.fuse)
-    batch, pix = cp.operands(k)
-    got = _run(hip_lib, k, k.entry, batch, pix)
+def _exact_legs(lib, k, L, got, batch, pix, depths=None):
+    """The bit-for-bit legs of the head of this file that apply to case `k` (launch decision `L`, outputs `got`); returns their names."""
     legs = []
     # -- the exact marching kernels against the tiled kernels
     if k.entry == "mode" and L["family"] == 1:
-        _same_outputs(got, _run(hip_lib, k, "tiled", batch, pix), "march vs tiled")
+        _same_outputs(got, _run(lib, k, "tiled", batch, pix, depths), "march vs tiled")
         legs.append("tiled")
     # -- a relaxed entry that falls back to the exact kernels
     if k.entry == "relaxed" and not L["relaxed"]:
-        _same_outputs(got, _run(hip_lib, k, "mode", batch, pix), "relaxed fallback vs exact entry")
+        _same_outputs(got, _run(lib, k, "mode", batch, pix, depths), "relaxed fallback vs exact entry")
         legs.append("fallback")
     # -- B8 / lean: the entry that runs the same sad kernel, the rounding of the copies, the un-finalised scratch of lean
     if k.entry in ("b8", "lean"):
-        twin = _run(hip_lib, k, "relaxed" if L["family"] == 1 and L["relaxed"] else "mode", batch, pix)
+        twin = _run(lib, k, "relaxed" if L["family"] == 1 and L["relaxed"] else "mode", batch, pix, depths)
         assert (L["family"] == 1 and L["relaxed"]) == (k.use_ssim == 1 and not k.pixd)
         _same(got["cv"], twin["cv"], "b8 cv vs the fp32 entry")
         for f in range(k.f):
@@ -205,7 +202,7 @@ def test_cost_volume_path(hip_lib, name):
     if k.b > 1:
         for n in range(k.b):
             bn, pn = cp.select_sample(batch, pix, n)
-            alone = _run(hip_lib, k, k.entry, bn, pn)
+            alone = _run(lib, k, k.entry, bn, pn, depths)
             part = dict(cv=got["cv"][n:n + 1], sf=[s[n:n + 1] for s in got["sf"]])
             if "b8" in got:
                 part["b8"] = [t[n:n + 1] for t in got["b8"]]
@@ -214,11 +211,23 @@ def test_cost_volume_path(hip_lib, name):
     # -- frame independence of the single-frame volumes
     if k.f > 1 and k.mult_mask:
         for f in range(k.f):
-            alone = _run(hip_lib, k, k.entry, cp.select_frame(batch, f), pix)
+            alone = _run(lib, k, k.entry, cp.select_frame(batch, f), pix, depths)
             _same(got["sf"][f], alone["sf"][0], f"frame {f} alone")
             if "b8" in got:
                 assert torch.equal(got["b8"][f].view(torch.int16), alone["b8"][0].view(torch.int16)), f"B8 copy of frame {f} alone"
         legs.append("frames")
+    return legs
+
+
+@pytest.mark.parametrize("name", [k.name for k in cp.CASES])
+def test_cost_volume_path(hip_lib, name):
+    k = cp.BY_NAME[name]
+    L = cp.query(hip_lib, k.f, k.b, k.d, k.h, k.w, k.use_ssim, k.pixd, k.mult_mask, k.patch, tiled=k.entry == "tiled", b8=k.entry in ("b8", "lean"),
+                 relaxed=k.entry == "relaxed", lean=k.entry == "lean")
+    assert cp.launched(L)[:2] == (k.sad, k.fuse)
+    batch, pix = cp.operands(k)
+    got = _run(hip_lib, k, k.entry, batch, pix)
+    legs = _exact_legs(hip_lib, k, L, got, batch, pix)
     if k.oracle:
         _oracle_leg(k, got, batch, pix)
         legs.append("oracle")
