@@ -40,6 +40,7 @@ extern "C" {
 #define MR_MAX_HEADS   4   /* one-channel 3x3 heads per mr_depth_heads_f32 launch (DepthModule has 4 predictors) */
 #define MR_MAX_VOTE_MASKS 8   /* masks voted over by mr_pointcloud_append_f32 / mr_tsdf_frame_f32 (the reference buffers 5) */
 #define MR_TSDF_MAX_FRAMES 8  /* keyframes integrated by one mr_tsdf_integrate_f32 launch */
+#define MR_CONSISTENCY_MAX_VIEWS 8   /* neighbouring keyframes checked by one mr_depth_consistency_f32 launch */
 #define MR_TSDF_TILE_X 32     /* voxels of one workgroup of mr_tsdf_integrate_f32 - the unit of its frustum culling */
 #define MR_TSDF_TILE_Y 8
 #define MR_TSDF_TILE_Z 4
@@ -700,6 +701,42 @@ int mr_pointcloud_append_f32(const float* inv_depth, const float* const* static_
 int mr_tsdf_frame_f32(const float* inv_depth, const float* keyframe, const float* const* static_masks, int32_t num_masks,
                       float vote_above, const int32_t* crop, float min_cm, float max_cm, int32_t batch, int32_t height,
                       int32_t width, int16_t* depth, uint8_t* colour, void* stream);
+
+/* ---- Cross-view depth consistency (an addition inside ABI 24, symbols only; monorec_amd/consistency.py): a keyframe's inverse depth
+ * checked against the inverse depth of neighbouring keyframes before it goes into a point cloud, an export or a volume.  No reference
+ * lines stand behind it: the arithmetic below is the definition. */
+
+/* One neighbouring keyframe of mr_depth_consistency_f32, passed by value in the launch arguments. */
+typedef struct mr_consistency_view {
+    float m[12];                 /* neighbour camera <- reference camera, 3 x 4 row-major (formed on the host in double, rounded once) */
+    float back[12];              /* reference camera <- neighbour camera: the inverse of m, likewise */
+    float fx, fy, cx, cy;        /* pixel intrinsics of the neighbour */
+    const float* inv_depth;      /* height x width, device memory: the neighbour's inverse depth (the model's `result`), unfiltered */
+} mr_consistency_view;
+
+/* Filter inv_depth (height x width, intrinsics fx fy cx cy) against views[0 .. num_views) (HOST array, 1 <= num_views <=
+ * MR_CONSISTENCY_MAX_VIEWS, all height x width).  All fp32, every operation rounded on its own, in this order; roundf rounds halves away
+ * from zero.  A depth value `inv` is VALID iff inv > 0 and d = 1 / inv is finite and > 0 (NaN, 0, negative values, +inf and values whose
+ * reciprocal overflows are not).  For reference pixel (x, y) with inv = inv_depth[y][x], d = 1 / inv:
+ *   invalid: hits = 0, out = 0.  Otherwise
+ *   X = ((x - cx) / fx) * d,  Y = ((y - cy) / fy) * d,  Z = d;  sum = d, n = 0;  for view j = 0 .. num_views - 1 in this order
+ *   (the first failing step ends that view):
+ *     1  q_r = ((m[4r] * X + m[4r+1] * Y) + m[4r+2] * Z) + m[4r+3]                                      require q_2 > 0
+ *     2  u = roundf(fx_j * (q_0 / q_2) + cx_j),  v = roundf(fy_j * (q_1 / q_2) + cy_j)                  require 0 <= u < width, 0 <= v < height
+ *     3  invn = views[j].inv_depth[v][u],  dn = 1 / invn  (nearest pixel, as mr_tsdf_integrate_f32)     require invn VALID
+ *     4                                                                                                 require fabsf(dn - q_2) <= rel_tol * q_2
+ *     5  Xn = ((u - cx_j) / fx_j) * dn,  Yn = ((v - cy_j) / fy_j) * dn,  Zn = dn;  p_r from `back` like q_r from m      require p_2 > 0
+ *        unless max_reproj_px is +INFINITY:  ex = (fx * (p_0 / p_2) + cx) - x,  ey = (fy * (p_1 / p_2) + cy) - y
+ *                                                                                    require ex * ex + ey * ey <= max_reproj_px * max_reproj_px
+ *     6  n += 1,  sum = sum + p_2
+ *   hits[y][x] = n;  out[y][x] = n < min_views ? 0 : average ? 1 / (sum / (float)(1 + n)) : inv
+ * out (fp32) or hits (bytes) may be NULL, not both; out must not alias an input (the views hold unfiltered depth).  One asynchronous launch
+ * on `stream`, no allocation, no synchronisation.  Null inv_depth or views, both outputs NULL, num_views outside 1 .. MR_CONSISTENCY_MAX_VIEWS,
+ * a view without inv_depth, height / width < 1, height * width >= 2^31, NaN or negative rel_tol or max_reproj_px, min_views < 0:
+ * MR_ERR_BAD_ARGUMENT, nothing is launched. */
+int mr_depth_consistency_f32(const float* inv_depth, float fx, float fy, float cx, float cy, const mr_consistency_view* views,
+                             int32_t num_views, float rel_tol, float max_reproj_px, int32_t min_views, int32_t average,
+                             int32_t height, int32_t width, float* out, uint8_t* hits, void* stream);
 
 /* ---- TSDF fusion (ABI 24; monorec_amd/tsdf_fusion.py): a dense voxel volume in device memory, the packed keyframes of mr_tsdf_frame_f32
  * integrated into it, the zero-crossing surface points out.  No reference lines stand behind these: the arithmetic below is the definition.

@@ -106,7 +106,16 @@ class TsdfView(ctypes.Structure):
                 ("depth_cm", ctypes.c_void_p), ("colour", ctypes.c_void_p)]
 
 
-MR_TSDF_BLOCK = 8              # edge of one block of the block-sparse volume (mr_tsdf_sparse_*_f32) in voxels
+MR_CONSISTENCY_MAX_VIEWS = 8
+
+
+class ConsistencyView(ctypes.Structure):
+    """mirror of `mr_consistency_view` (include/monorec_hip.h): m is neighbour camera <- reference camera, back its inverse."""
+    _fields_ = [("m", ctypes.c_float * 12), ("back", ctypes.c_float * 12), ("fx", ctypes.c_float), ("fy", ctypes.c_float),
+                ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("inv_depth", ctypes.c_void_p)]
+
+
+MR_TSDF_BLOCK = 8            # edge of one block of the block-sparse volume (mr_tsdf_sparse_*_f32) in voxels
 MR_TSDF_BRICK = 4              # edge of one brick of mr_tsdf_skip_grid_u8 in voxels
 
 
@@ -279,6 +288,9 @@ ABI = {
     "mr_tsdf_frame_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
                                          ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.c_float, ctypes.c_float,
                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_depth_consistency_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                                ctypes.POINTER(ConsistencyView), ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32,
+                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mr_tsdf_volume_reset_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                 ctypes.c_void_p]),
     "mr_tsdf_integrate_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -22,6 +22,7 @@ SOURCES = [
     ("cost_volume.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("pointcloud.hip", ["-ffp-contract=off"]),
     ("tsdf_export.hip", ["-ffp-contract=off"]),        # depth / colour packing of save_frame_for_tsdf: the reference's roundings, one by one
+    ("depth_consistency.hip", ["-ffp-contract=off"]),  # cross-view consistency filter: the roundings of include/monorec_hip.h, one by one
     ("tsdf_fusion.hip", ["-ffp-contract=off"]),        # TSDF integration / surface extraction: the roundings of include/monorec_hip.h, one by one
     ("tsdf_sparse.hip", ["-ffp-contract=off"]),        # the block-sparse volume: the same roundings through csrc/tsdf_common.h
     ("tsdf_sparse_render.hip", ["-ffp-contract=off"]), # its ray-cast: the dense render kernel's roundings through csrc/tsdf_render.h

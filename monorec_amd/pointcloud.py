@@ -172,12 +172,18 @@ class PLYSaver(torch.nn.Module):
 
 class PointcloudBuilder:
     """The keyframe loop body of create_pointcloud.py:66-102: static mask per keyframe, buffers of `buffer_length`,
-    vote + masked depth of the middle keyframe into the PLYSaver.  Feed it the model's input/output dicts."""
+    vote + masked depth of the middle keyframe into the PLYSaver.  Feed it the model's input/output dicts.
+    `consistency` (None: nothing; else what monorec_amd.consistency.settings accepts): the middle keyframe's depth is first filtered
+    against the other buffered keyframes, at most 8 of them, oldest first (`consistency.filter_depth`)."""
 
-    def __init__(self, plysaver, mask_fill=32, buffer_length=5, min_hits=1, use_mask=True):
+    def __init__(self, plysaver, mask_fill=32, buffer_length=5, min_hits=1, use_mask=True, consistency=None):
+        from .consistency import MAX_VIEWS, settings
         self.ply = plysaver
         self.mask_fill, self.buffer_length, self.min_hits, self.use_mask = mask_fill, buffer_length, min_hits, use_mask
         self.key_index = buffer_length // 2
+        self.consistency = settings(consistency)
+        if self.consistency is not None and not 2 <= buffer_length <= MAX_VIEWS + 1:
+            raise ValueError(f"PointcloudBuilder: consistency needs a buffer of 2 to {MAX_VIEWS + 1} keyframes, not {buffer_length}")
         self._buf = []
 
     def add(self, data, result):
@@ -188,10 +194,17 @@ class PointcloudBuilder:
         self._buf.append(dict(pose=data["keyframe_pose"].clone(), intrinsics=data["keyframe_intrinsics"].clone(),
                               mask=static_mask(cv_mask, self.mask_fill), keyframe=data["keyframe"].clone(),
                               depth=output.clone()))
+        if self.consistency is not None:           # the relative poses are formed on the host: one copy per keyframe, not one per use
+            self._buf[-1]["host"] = (data["keyframe_pose"].cpu(), data["keyframe_intrinsics"].cpu())
         if len(self._buf) >= self.buffer_length:
             k = self._buf[self.key_index]
             masks = [e["mask"] for e in self._buf] if self.use_mask else None
-            self.ply.add_depthmap(k["depth"], k["keyframe"], k["intrinsics"], k["pose"], static_masks=masks,
+            depth = k["depth"]
+            if self.consistency is not None:
+                from .consistency import filter_depth
+                others = [(e["depth"],) + e["host"] for e in self._buf if e is not k]
+                depth, _ = filter_depth(depth, k["host"][0], k["host"][1], others, **self.consistency)
+            self.ply.add_depthmap(depth, k["keyframe"], k["intrinsics"], k["pose"], static_masks=masks,
                                   min_hits=self.min_hits)
             del self._buf[0]
 
@@ -215,7 +228,9 @@ def run(config, model=None, dataset=None, out=None, dropout=.75, device="cuda:0"
     `start` / `end` (DS_Wrapper), batch size 1 -> `arch.args` -> MonoRecModel -> PointcloudBuilder (static masks, 5-keyframe vote)
     -> PLYSaver(`min_d`, `max_d`, `roi`, dropout) -> `output_dir/file_name`.  `model` / `dataset`: use these instead of building them
     from the config; `out`: a path or a binary file object instead of `output_dir/file_name`; `dropout`: the random thinning the
-    script hard-wires to .75 (:52).  Returns the number of records written."""
+    script hard-wires to .75 (:52).  Optional key `consistency` (absent or false: nothing; else monorec_amd.consistency.settings): the
+    middle keyframe's depth is filtered against the other four buffered ones before it goes to the saver.  Returns the number of
+    records written."""
     import os
     from .kitti import DeviceLoader
     if dataset is None:
@@ -234,7 +249,8 @@ def run(config, model=None, dataset=None, out=None, dropout=.75, device="cuda:0"
     saver = PLYSaver(height, width, min_d=config.get("min_d", 3), max_d=config.get("max_d", 30), batch_size=loader.batch_size,
                      roi=config.get("roi", None), dropout=dropout)
     saver.to(device)
-    builder = PointcloudBuilder(saver, mask_fill=32, buffer_length=5, min_hits=1, use_mask=config.get("use_mask", True))
+    builder = PointcloudBuilder(saver, mask_fill=32, buffer_length=5, min_hits=1, use_mask=config.get("use_mask", True),
+                                consistency=config.get("consistency", None))
     with torch.no_grad():
         for data, _ in loader:
             result = model(data)

@@ -349,15 +349,27 @@ class KeyframeStream:
     create_pointcloud.py's shape unless they are handed in, plans the window (`plan_shard`), checks that the model keeps enough slots
     in flight for the vote, and `run(emit)` drives the pipelined loop (prepare / submit / synchronize), calling
     `emit(number, entry, masks)` once per exported keyframe in export order: `entry` holds keyframe, depth (views of the model's
-    resident buffers, valid until the next submit), pose, intrinsics, sequence, image_id; `masks` the static masks to vote over, or None."""
+    resident buffers, valid until the next submit), pose, intrinsics, sequence, image_id; `masks` the static masks to vote over, or None.
+
+    With the config key `consistency` (monorec_amd.consistency.settings) the stream buffers BUFFER_LENGTH keyframes whether or not
+    `use_mask` is set - the window is planned as `plan_shard(window, use_mask or consistency)`, so the first and last two keyframes of
+    the window are not exported, as with the vote - and `entry["depth"]` is the middle keyframe's depth filtered against the other four
+    buffered ones (`consistency.filter_depth`, the two older ones first): a buffer of the stream's own, valid until the next emit.  The
+    vote multiplies afterwards; zeroing commutes with it.  The buffered depths are then not views of the model's slots: every collected
+    depth is copied, device to device on the caller's stream, into a ring of BUFFER_LENGTH maps that the stream owns, like the static
+    masks an output of its own - a buffered keyframe needs no slot after its collect, and without `use_mask` the model's whole
+    `hip_in_flight` stays in flight."""
 
     def __init__(self, config, model=None, dataset=None, shard=(0, 1), device="cuda:0", who="monorec_amd.tsdf_export"):
+        from . import consistency
         from .pointcloud import _dataset_class
         self.who = who
         rank, world = int(shard[0]), int(shard[1])
         self.rank, self.world = rank, world
         self.use_mask = use_mask = bool(config.get("use_mask", True))
-        plan_shard(0, use_mask, rank, world)                                # a bad shard is reported before anything is built
+        self.consistency = consistency.settings(config.get("consistency", None))                 # None: no filter, nothing below differs from a run without the key
+        self.buffered = buffered = use_mask or self.consistency is not None
+        plan_shard(0, buffered, rank, world)                                # a bad shard is reported before anything is built
         if model is None and config["arch"]["type"] != "MonoRecModel":
             raise ValueError(f"{who}: arch.type {config['arch']['type']!r} is not MonoRecModel")
         if dataset is None:
@@ -375,8 +387,8 @@ class KeyframeStream:
         self.model, self.dataset, self.device = model, dataset, device
         self.start, end = int(config.get("start", 0)), int(config.get("end", -1))
         self.window = max(0, (len(dataset) if end == -1 else end) - self.start)
-        self.plan = plan_shard(self.window, use_mask, rank, world)
-        halo = self.plan["halo"]
+        self.plan = plan_shard(self.window, buffered, rank, world)
+        halo = self.plan["halo"] if use_mask else 0                         # (the vote's rule is kept as it is, with or without the filter)
         self.slots = int(getattr(model, "hip_in_flight", 1))
         # keyframe e is packed when keyframe e + halo has been collected, and that must come before submit number e + slots, which reuses its
         # slot: with P forwards pending the collect of e + halo precedes submit e + halo + P, so P <= slots - halo
@@ -395,13 +407,16 @@ class KeyframeStream:
 
     def run(self, emit):
         import collections
+        from .consistency import filter_depth
         from .kitti import DeviceLoader
         from .pointcloud import static_mask
         model, plan, slots, use_mask = self.model, self.plan, self.slots, self.use_mask
         first, last = plan["items"]
         loader = DeviceLoader(self.dataset, batch_size=1, start=self.start + first, end=self.start + last) if last > first else ()
         pending, buffer = collections.deque(), []
-        state = {"submitted": 0, "exported": 0}
+        state = {"submitted": 0, "exported": 0, "collected": 0}
+        settings, ring = self.consistency, None
+        middle = BUFFER_LENGTH // 2
 
         def export(entry, masks):
             # the submit that overwrites this keyframe's resident outputs is number entry.item + slots: it must not have happened yet
@@ -411,19 +426,45 @@ class KeyframeStream:
             state["exported"] += 1
             emit(number, entry, masks)
 
+        def export_filtered(masks):
+            # the buffered depths are ring copies: the collect that overwrites the oldest one's is number oldest.item + BUFFER_LENGTH
+            if state["collected"] > buffer[0]["item"] + BUFFER_LENGTH or [e["item"] for e in buffer] != list(range(buffer[0]["item"], buffer[0]["item"] + BUFFER_LENGTH)):
+                raise RuntimeError(f"{self.who}: a buffered keyframe's depth copy was overwritten before the consistency filter read it (internal)")
+            entry = buffer[middle]
+            others = [(e["depth"], e["pose"], e["intrinsics"]) for k, e in enumerate(buffer) if k != middle]
+            filtered, _ = filter_depth(entry["depth"], entry["pose"], entry["intrinsics"], others, out=ring[BUFFER_LENGTH], **settings)
+            number = plan["exports"][0] + state["exported"]
+            state["exported"] += 1
+            emit(number, dict(entry, depth=filtered), masks)
+
         def collect():
+            nonlocal ring
             item, data, handle = pending.popleft()
             out = handle.synchronize()                                  # the host waits: no blocked wait packet on the stream
             entry = dict(item=item, keyframe=data["keyframe"], depth=out["result"], pose=data["keyframe_pose"],
                          intrinsics=data["keyframe_intrinsics"], sequence=data.get("sequence"), image_id=data.get("image_id"))
-            if not use_mask:
+            if not self.buffered:
                 export(entry, None)
                 return
-            cv_mask = out["cv_mask"] if "cv_mask" in out else out["result"].new_zeros(out["result"].shape)
-            entry["mask"] = static_mask(cv_mask, 32)                    # create_pointcloud.py:76-77; an output of its own, not a view
+            if settings is not None:
+                # the copy reads the slot's resident output: the submit that overwrites it, number item + slots, must not have happened yet
+                if state["submitted"] > item + slots:
+                    raise RuntimeError(f"{self.who}: a collected keyframe's slot was reused before its depth was copied (internal)")
+                if ring is None:                                        # BUFFER_LENGTH buffered depths and the filtered map
+                    ring = torch.empty((BUFFER_LENGTH + 1,) + tuple(out["result"].shape), dtype=torch.float32, device=out["result"].device)
+                entry["depth"] = ring[item % BUFFER_LENGTH]
+                entry["depth"].copy_(out["result"])                     # device to device, on the caller's stream
+                state["collected"] += 1
+            if use_mask:
+                cv_mask = out["cv_mask"] if "cv_mask" in out else out["result"].new_zeros(out["result"].shape)
+                entry["mask"] = static_mask(cv_mask, 32)                # create_pointcloud.py:76-77; an output of its own, not a view
             buffer.append(entry)
             if len(buffer) >= BUFFER_LENGTH:
-                export(buffer[BUFFER_LENGTH // 2], [e["mask"] for e in buffer])
+                masks = [e["mask"] for e in buffer] if use_mask else None
+                if settings is not None:
+                    export_filtered(masks)
+                else:
+                    export(buffer[middle], masks)
                 del buffer[0]
 
         with torch.no_grad():
@@ -445,7 +486,10 @@ def run(config, model=None, dataset=None, shard=(0, 1), device="cuda:0", export=
     """Export the keyframes of a config of create_pointcloud.py's shape (configs/test/pointcloud_monorec*.json): `data_set` -> device
     dataset windowed by `start` / `end`, `arch` -> MonoRecModel, `roi` -> the crop, `min_d` / `max_d` -> the thresholds (absent: none),
     `use_mask` -> the 5-keyframe vote, `output_dir` -> the directory.  Optional keys: `export_ring`, `export_workers`,
-    `png_compress_level`.  `model` / `dataset`: use these instead of building them.
+    `png_compress_level`, `consistency` (absent or false: nothing; true or a dict of `rel_tol` .01, `max_reproj_px` 1, `min_views` 2,
+    `average` false: every exported depth is first filtered against the two keyframes before and the two after it,
+    monorec_amd.consistency - the first and last two keyframes of the window are then not exported, with or without `use_mask`).
+    `model` / `dataset`: use these instead of building them.
 
     The loop (KeyframeStream) is pipelined (prepare / submit / synchronize with the model's `hip_in_flight`).  The outputs of submit() are
     views of the slot's resident buffers; nothing is cloned but the static masks (outputs of their own launch): the pack launch of a

@@ -1015,7 +1015,9 @@ def run(config, model=None, dataset=None, device="cuda:0"):
     `tsdf_max_bytes` as well; a pool that ran out raises after the loop), `sparse_render` (false; true, with `sparse_volume` only: renders and
     score come from the sparse volume itself, `SparseTSDFVolume.render` - the same bits without the dense copy), `sparse_mesh` (false; true,
     with `sparse_volume` only: `mesh_file_name` is written from the sparse volume itself, `SparseTSDFVolume.save_mesh_ply` - the same mesh
-    without the dense copy; with both keys nothing asks for room for one).
+    without the dense copy; with both keys nothing asks for room for one), `consistency` (absent or false: nothing; as for
+    `tsdf_export.run`: every keyframe's depth is filtered against the two keyframes before and after it before it is packed,
+    monorec_amd.consistency, and the first and last two keyframes of the window are not fused, with or without `use_mask`).
 
     Per keyframe `pack_frames` (vote, crop, thresholds: the depths are exactly the ones the export writes to the PNG) fills a staging slot
     on the device; after `fuse_batch` keyframes, or at the end, one integrate launch follows on the same stream.  Every keyframe is
