@@ -1026,6 +1026,69 @@ int mr_tsdf_sparse_mesh_triangles_f32(const int32_t* table, int32_t nbx, int32_t
                                       const int32_t* block_of_slot, int64_t num_slots, float min_weight, const int32_t* vertex_base,
                                       int32_t* triangles, int64_t capacity_triangles, int64_t* cursor, void* stream);
 
+/* Vertex normals and a clustered level of detail for both meshes (six entries added within ABI 24: the change only adds symbols).
+ * Everything is fp32, every operation rounded on its own; tests/tsdf_mesh_lod_ref.py restates it in numpy.  No float atomics.
+ *
+ * Normals.  A voxel is SEEN when it lies inside the volume, has weight > min_weight and - in the sparse volume - its block has a slot
+ * below num_slots.  For a seen voxel v and an axis i
+ *   g_i[v] = hi - lo,  hi = tsdf[v + e_i] if that voxel is seen, else tsdf[v];  lo = tsdf[v - e_i] if that voxel is seen, else tsdf[v]
+ * The vertex on the active edge from a = v to b = v + d_e, at the parameter s = tsdf[a] / (tsdf[a] - tsdf[b]) of its position, has
+ *   m_i = g_i[a] + s * (g_i[b] - g_i[a]);  len = sqrtf((m_0 * m_0 + m_1 * m_1) + m_2 * m_2);  normal_i = m_i / len if len > 0, else 0
+ * Tsdf grows from the inside to the outside, so the normal points where (b - a) x (c - a) of the triangles points.
+ * The two _normals_ entries are mr_tsdf_mesh_vertices_f32 and mr_tsdf_sparse_mesh_vertices_f32 - the same tile code, records, order,
+ * vertex_base and cursor - that also write normal x y z of the vertex with index i to normals[3 i .. 3 i + 3).  normals may be NULL only
+ * when vertices is; it needs a 4-byte boundary and room for 3 floats per vertex below the capacity.
+ *
+ * Clusters.  With c = cell in {2, 4, 8}, cluster (X, Y, Z) holds the voxels with x / c = X, y / c = Y, z / c = Z (integer division);
+ * the dense volume has ceil(n_a / c) clusters per axis - partial ones on the high side where c does not divide n_a -, a block of the
+ * sparse volume (8 / c)^3.  A cluster that owns at least one vertex of the full mesh - one of its voxels has a mask other than 0 -
+ * emits ONE vertex.  Its members are visited in one fixed order: the cluster's voxels with z outermost, then y, x fastest - voxel
+ * i = (dz * c + dy) * c + dx -, within a voxel its active edges e = 0 .. 6.  The sum is a tree of a fixed shape: the voxels are cut
+ * into RUNS of 8 in that order, run r = i / 8 (a cluster of 2^3 is one run, of 4^3 eight runs of two rows, of 8^3 sixty-four runs of
+ * one row).  Over the six floats of a member's record and the three of its normal (as above):
+ *   run_k[r] starts at 0.0f and takes run_k[r] = run_k[r] + value_k per member of run r, in the order above (one lane per run)
+ *   sum_k starts at 0.0f and takes sum_k = sum_k + run_k[r] for r = 0, 1, ... (one lane per cluster; a run without a member adds 0.0f)
+ *   record_k = sum_k / (float)count  for x y z red green blue (the colours are NOT rounded again)
+ *   len = sqrtf((sum_nx * sum_nx + sum_ny * sum_ny) + sum_nz * sum_nz);  normal = sum_n / len if len > 0, else 0
+ * Every triangle of the full mesh is mapped to the clusters of the owner voxels of its three vertices (corners c0, c1, c2 of its
+ * tetrahedron).  If two of the three clusters coincide the triangle is dropped; the others are written with their winding kept, as three
+ * indices of cluster vertices.  Triangles that repeat are kept.
+ * cluster_base: int32, caller-owned.  Dense: one element per cluster, ((Z * cy) + Y) * cx + X with c_a = ceil(n_a / c).  Sparse:
+ * (8 / c)^3 per slot, s * (8 / c)^3 + ((Z * (8 / c)) + Y) * (8 / c) + X with the cluster's place in its block.  The vertex entry writes
+ * the vertex index of every cluster that owns a vertex and leaves the rest untouched; the triangle entry recomputes cases and clusters
+ * from the same volume and min_weight and reads it - across a block face in the slot of a + neighbour.
+ * Workgroups: the dense vertex entry gives a workgroup MR_TSDF_CLUSTER_TILE_X x _Y x _Z voxels - whole clusters for every c -, the
+ * sparse one a slot; the triangle entries use the tile of mr_tsdf_mesh_triangles_f32 and a slot.  Cursor protocol (one atomicAdd per
+ * workgroup), capacity rule and the count-only mode (vertices / triangles NULL: capacity, normals and cluster_base are ignored) are the
+ * mesh entries'.  normals NULL with vertices: no normals are computed.
+ * MR_ERR_BAD_ARGUMENT, nothing is launched: every case of the mesh entries of the same volume, with cluster_base in the place of
+ * vertex_base; a cell other than 2, 4 or 8; normals off a 4-byte boundary; normals without vertices (for the _normals_ entries also
+ * vertices without normals); nz > 2^31 - 10 (dense vertex entry); num_slots * (8 / c)^3 >= 2^31 (sparse). */
+#define MR_TSDF_CLUSTER_TILE_X 32
+#define MR_TSDF_CLUSTER_TILE_Y 8
+#define MR_TSDF_CLUSTER_TILE_Z 8
+int mr_tsdf_mesh_vertices_normals_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                                      const float* origin, float voxel_size, float min_weight, float* vertices, int64_t capacity_vertices,
+                                      float* normals, int32_t* vertex_base, int64_t* cursor, void* stream);
+int mr_tsdf_mesh_cluster_vertices_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny, int32_t nz,
+                                      const float* origin, float voxel_size, float min_weight, int32_t cell, float* vertices,
+                                      int64_t capacity_vertices, float* normals, int32_t* cluster_base, int64_t* cursor, void* stream);
+int mr_tsdf_mesh_cluster_triangles_f32(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz, float min_weight,
+                                       int32_t cell, const int32_t* cluster_base, int32_t* triangles, int64_t capacity_triangles,
+                                       int64_t* cursor, void* stream);
+int mr_tsdf_sparse_mesh_vertices_normals_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf,
+                                             const float* weight, const uint8_t* colour, const int32_t* block_of_slot, int64_t num_slots,
+                                             const float* origin, float voxel_size, float min_weight, float* vertices,
+                                             int64_t capacity_vertices, float* normals, int32_t* vertex_base, int64_t* cursor, void* stream);
+int mr_tsdf_sparse_mesh_cluster_vertices_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf,
+                                             const float* weight, const uint8_t* colour, const int32_t* block_of_slot, int64_t num_slots,
+                                             const float* origin, float voxel_size, float min_weight, int32_t cell, float* vertices,
+                                             int64_t capacity_vertices, float* normals, int32_t* cluster_base, int64_t* cursor, void* stream);
+int mr_tsdf_sparse_mesh_cluster_triangles_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf,
+                                              const float* weight, const int32_t* block_of_slot, int64_t num_slots, float min_weight,
+                                              int32_t cell, const int32_t* cluster_base, int32_t* triangles, int64_t capacity_triangles,
+                                              int64_t* cursor, void* stream);
+
 /* ---- input pipeline: KittiOdometryDataset.preprocess_image, kitti_odometry_dataset.py:120-134 ------
  *
  * img.crop(box) -> img.resize((W,H), Image.BILINEAR) -> float32 / 255 - .5 -> CHW (a 1-channel image is stacked 3x),

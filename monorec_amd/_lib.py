@@ -117,6 +117,8 @@ class ConsistencyView(ctypes.Structure):
 
 MR_TSDF_BLOCK = 8            # edge of one block of the block-sparse volume (mr_tsdf_sparse_*_f32) in voxels
 MR_TSDF_BRICK = 4              # edge of one brick of mr_tsdf_skip_grid_u8 in voxels
+MR_TSDF_CLUSTER_TILE = (32, 8, 8)    # MR_TSDF_CLUSTER_TILE_X / _Y / _Z: voxels of one workgroup of mr_tsdf_mesh_cluster_vertices_f32
+MR_TSDF_MESH_CELLS = (1, 2, 4, 8)    # cluster edges of the mesh entries: the divisors of MR_TSDF_BLOCK (1: the full mesh)
 
 
 class TsdfRayView(ctypes.Structure):
@@ -330,7 +332,27 @@ ABI = {
     "mr_tsdf_sparse_mesh_triangles_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
                                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_resample_ksize_bilinear": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "mr_tsdf_mesh_vertices_normals_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_int32, _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_mesh_cluster_vertices_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_int32, _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p,
+                                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_mesh_cluster_triangles_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                          ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_sparse_mesh_vertices_normals_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_float_p,
+                                                                ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_sparse_mesh_cluster_vertices_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_float_p,
+                                                                ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
+                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_tsdf_sparse_mesh_cluster_triangles_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
+                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_int32,
+                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "mr_resample_ksize_bilinear":(ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "mr_resample_coeffs_bilinear": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                    ctypes.c_void_p, ctypes.c_void_p]),
     "mr_preprocess_image_u8_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,

@@ -10,6 +10,9 @@
 //                           no output it only counts
 //   tsdf_mesh_vertices_kernel<7>, tsdf_mesh_triangles_kernel   the same surface as an indexed mesh (marching tetrahedra; further down):
 //                           the same kernel over all seven edges a voxel owns, which also writes vertex_base, and the triangles
+//   tsdf_mesh_vertex_normals_kernel   the <7> vertex tile code with the unit normal of every vertex beside its record
+//   tsdf_mesh_cluster_vertices_kernel, tsdf_mesh_cluster_triangles_kernel   the mesh at a level of detail: one vertex per cluster of
+//                           2^3, 4^3 or 8^3 voxels, the triangles between three different clusters (below the mesh kernels)
 //   tsdf_skip_grid_kernel, tsdf_render_kernel   the volume seen from a camera (at the end)
 // All but reset and render sweep the volume in one tile (tile_of_block); integrate and skip grid load a thread's four voxels with load_four.
 //
@@ -184,10 +187,24 @@ struct MeshArgs {
     unsigned long long* cursor;
 };
 
+// is voxel (x, y, z) inside the volume and seen?  Then t is its tsdf: what the normals ask of the volume (voxel_gradient, tsdf_mesh.h)
+struct VolumeSample {
+    const MeshArgs& a;
+    __device__ __forceinline__ bool operator()(int x, int y, int z, float& t) const {
+        if ((unsigned)x >= (unsigned)a.nx || (unsigned)y >= (unsigned)a.ny || (unsigned)z >= (unsigned)a.nz) return false;
+        const long long g = ((long long)z * a.ny + y) * a.nx + x;
+        if (!(a.weight[g] > a.min_weight)) return false;
+        t = a.tsdf[g];
+        return true;
+    }
+};
+
 // EDGES = 7: the vertices of the mesh, and vertex_base.  EDGES = 3: the axis edges alone, the points of mr_tsdf_extract_f32; nothing
 // of it indexes with int32, so it serves volumes past 2^31 voxels.
-template <int EDGES>
-__global__ __launch_bounds__(256) void tsdf_mesh_vertices_kernel(const MeshArgs a) {
+// NORMALS (the variant tsdf_mesh_vertex_normals_kernel alone): the unit normal of every vertex into normals[3 * index], its gradients
+// read from the volume, not from the staged block - they reach a voxel further on every side.
+template <int EDGES, bool NORMALS>
+__device__ __forceinline__ void mesh_vertices_tile(const MeshArgs& a, float* normals) {
     static_assert(EDGES == 3 || EDGES == 7, "the axis edges, or all a voxel owns");
     __shared__ float s_t[VSN];
     __shared__ uint8_t s_code[VSN];
@@ -254,11 +271,17 @@ __global__ __launch_bounds__(256) void tsdf_mesh_vertices_kernel(const MeshArgs 
 #pragma unroll
                 for (int k = 0; k < 3; ++k) r[k] = (along[e] >> k) & 1u ? p[k] + step : p[k];
                 write_colour(r, cv, a.colour ? a.colour[g + g_far[e]] : 0u, s);
+                if constexpr (NORMALS) vertex_normal(VolumeSample{a}, gx, gy, gz, tv, e, s_t[at + s_far[e]], s, normals + rec * 3);
             }
             ++rec;
         }
     }
 }
+
+template <int EDGES>
+__global__ __launch_bounds__(256) void tsdf_mesh_vertices_kernel(const MeshArgs a) { mesh_vertices_tile<EDGES, false>(a, nullptr); }
+
+__global__ __launch_bounds__(256) void tsdf_mesh_vertex_normals_kernel(const MeshArgs a, float* normals) { mesh_vertices_tile<7, true>(a, normals); }
 
 __global__ __launch_bounds__(256) void tsdf_mesh_triangles_kernel(const MeshArgs a) {
     __shared__ uint8_t s_code[CSN];
@@ -347,7 +370,179 @@ __global__ __launch_bounds__(256) void tsdf_mesh_triangles_kernel(const MeshArgs
     }
 }
 
-long long voxel_count(int nx, int ny, int nz) {                  // MAX_VOXELS for anything at or beyond the bound, without overflow
+// ---- the clustered level of detail: one vertex per cluster of cell^3 voxels that owns a vertex of the full mesh, the full mesh's
+// triangles between three different clusters (include/monorec_hip.h has the rules, tsdf_mesh.h the code the sparse volume runs too)
+//   tsdf_mesh_cluster_vertices_kernel   a workgroup owns MR_TSDF_CLUSTER_TILE_X x _Y x _Z = 32 x 8 x 8 voxels - whole clusters for every
+//                               cell - and stages tsdf and codes of the tile plus one voxel beyond its high faces (33 x 9 x 9, 13 KB) as
+//                               the vertex kernel does, then the masks of its voxels.  The tile is 256 runs of 8 voxels for every cell
+//                               (tsdf_mesh.h): a lane sums the vertices of one run in the fixed order, the run sums go through LDS
+//                               (in the place of the staged tsdf) and the first lane of each cluster - 256, 32 or 4 of them - adds its 1, 8 or 64 runs in
+//                               order; no atomics but the one on the cursor per workgroup.  It writes cluster_base.
+//   tsdf_mesh_cluster_triangles_kernel  the triangle kernel's tile, cases and walk over the codes of the tile plus ONE voxel (no masks:
+//                               a vertex is its owner's cluster), the count over the triangles that survive
+constexpr int KX = MR_TSDF_CLUSTER_TILE_X, KY = MR_TSDF_CLUSTER_TILE_Y, KZ = MR_TSDF_CLUSTER_TILE_Z;
+constexpr int KSX = KX + 1, KSY = KY + 1, KSZ = KZ + 1, KSN = KSX * KSY * KSZ;
+static_assert(KX == 32 && KY == 8 && KZ == 8 && KX % B == 0 && KY % B == 0 && KZ % B == 0, "2048 voxels: 256, 32 or 4 whole clusters");
+static_assert(KSN >= 10 * 256, "the run sums (9 floats and a count per run) take the place of the staged tsdf");
+
+struct ClusterArgs {
+    float* normals;                              // vertices only; null: none
+    int* cluster_base;                           // written by the vertex kernel, read by the triangle kernel
+    int shift;                                   // cell = 1 << shift
+    int cx, cy;                                  // clusters of the volume along x and y
+};
+
+template <bool NORMALS>
+__global__ __launch_bounds__(256) void tsdf_mesh_cluster_vertices_kernel(const MeshArgs a, const ClusterArgs k) {
+    __shared__ float s_t[KSN];
+    __shared__ uint8_t s_code[KSN];
+    __shared__ uint8_t s_mask[KSN];
+    __shared__ uint8_t s_owns[256];
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x;
+    const Tile o = tile_of_block<KX, KY, KZ>(a.tiles_x, a.tiles_y);
+    const int x0 = o.x, y0 = o.y, z0 = o.z;
+    const long long plane = (long long)a.nx * a.ny;
+    int any_neg = 0;
+    for (int i = tid; i < KSN; i += 256) {
+        const int sx = i % KSX, sy = (i / KSX) % KSY, sz = i / (KSX * KSY);
+        const int gx = x0 + sx, gy = y0 + sy, gz = z0 + sz;
+        float t = 1.0f;
+        unsigned c = 0u;
+        if (gx < a.nx && gy < a.ny && gz < a.nz) {
+            const long long g = (long long)gz * plane + (long long)gy * a.nx + gx;
+            if (a.weight[g] > a.min_weight) {
+                t = a.tsdf[g];
+                c = t < 0.0f ? (SEEN | NEG) : SEEN;
+            }
+        }
+        s_t[i] = t;
+        s_code[i] = (uint8_t)c;
+        any_neg |= (int)(c & NEG);
+    }
+    if (!__syncthreads_or(any_neg)) return;
+    for (int i = tid; i < KX * KY * KZ; i += 256) {
+        const int at = ((i / (KX * KY)) * KSY + (i / KX) % KY) * KSX + i % KX;
+        s_mask[at] = (uint8_t)edge_mask<7>(s_code, at, KSX, KSX * KSY);
+    }
+    __syncthreads();
+
+    // the thread's run: the tile has 256 runs of 8 voxels for every cell; run `run` of cluster q of the tile's is on thread q * runs + run
+    const int sh = k.shift;
+    const int qnx = KX >> sh, qny = KY >> sh, runs = (1 << (3 * sh)) / RUN;
+    const int q = tid / runs, run = tid % runs;
+    const int lx = (q % qnx) << sh, ly = ((q / qnx) % qny) << sh, lz = (q / (qnx * qny)) << sh;      // the cluster's first voxel in the tile
+    const int at0 = (lz * KSY + ly) * KSX + lx;
+    const int owns = run_owns(s_mask, at0, KSX, KSX * KSY, sh, run);
+    s_owns[tid] = (uint8_t)owns;
+    __syncthreads();
+    int has = 0;                                 // of the lane of the cluster's first run: does the cluster own a vertex?
+    if (run == 0)
+        for (int r = 0; r < runs; ++r) has |= s_owns[tid + r];
+    int total;
+    const int before = workgroup_prefix(has, wave_tot, total);
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);       // one per workgroup
+    if (!a.vertices) return;
+    constexpr int N = NORMALS ? 9 : 6;
+    float sum[N];
+    int count = 0;
+    if (owns) {
+        const auto vertex = [&](int dx, int dy, int dz, int at, int e, float* r) {
+            const int gx = x0 + lx + dx, gy = y0 + ly + dy, gz = z0 + lz + dz;
+            const long long g = (long long)gz * plane + (long long)gy * a.nx + gx;
+            const int far = (int)(EDGE_ALONG[e] & 1u) + (int)((EDGE_ALONG[e] >> 1) & 1u) * KSX + (int)(EDGE_ALONG[e] >> 2) * (KSX * KSY);
+            const long long g_far = (long long)(EDGE_ALONG[e] & 1u) + (long long)((EDGE_ALONG[e] >> 1) & 1u) * a.nx + (long long)(EDGE_ALONG[e] >> 2) * plane;
+            const float p[3] = {a.ox + (float)gx * a.voxel, a.oy + (float)gy * a.voxel, a.oz + (float)gz * a.voxel};
+            const float tv = s_t[at], tn = s_t[at + far];
+            const float s = edge_record(tv, tn, p, e, a.voxel, a.colour ? a.colour[g] : 0u, a.colour ? a.colour[g + g_far] : 0u, r);
+            if constexpr (NORMALS) vertex_normal(VolumeSample{a}, gx, gy, gz, tv, e, tn, s, r + 6);
+        };
+        count = run_sum<NORMALS>(s_mask, at0, KSX, KSX * KSY, sh, run, sum, vertex);
+    }
+    // the sums of the runs and, last, their counts go through LDS as [sum][run], in the place of the staged tsdf, which every lane has
+    // finished reading
+    __syncthreads();
+    float* s_part = s_t;
+#pragma unroll
+    for (int c = 0; c < N; ++c) s_part[c * 256 + tid] = owns ? sum[c] : 0.0f;
+    s_part[N * 256 + tid] = (float)count;
+    __syncthreads();                             // (also: s_base is there)
+    if (!has) return;
+    const long long rec = (long long)s_base + before;
+    // (a cluster that owns a vertex holds a voxel of the volume: its place in cluster_base exists)
+    k.cluster_base[((long long)((z0 + lz) >> sh) * k.cy + ((y0 + ly) >> sh)) * k.cx + ((x0 + lx) >> sh)] = (int)rec;
+    if (rec >= a.capacity) return;
+    float out[9];
+    cluster_combine<NORMALS>(s_part + tid, 256, runs, out);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) a.vertices[rec * 6 + c] = out[c];
+    if constexpr (NORMALS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) k.normals[rec * 3 + c] = out[6 + c];
+    }
+}
+
+__global__ __launch_bounds__(256) void tsdf_mesh_cluster_triangles_kernel(const MeshArgs a, const ClusterArgs k) {
+    __shared__ uint8_t s_code[VSN];
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x;
+    const Tile o = tile_of_block<TX, TY, TZ>(a.tiles_x, a.tiles_y);
+    const int x0 = o.x, y0 = o.y, z0 = o.z;
+    const long long plane = (long long)a.nx * a.ny;
+    int any_neg = 0;
+    for (int i = tid; i < VSN; i += 256) {
+        const int sx = i % VSX, sy = (i / VSX) % VSY, sz = i / (VSX * VSY);
+        const int gx = x0 + sx, gy = y0 + sy, gz = z0 + sz;
+        unsigned c = 0u;
+        if (gx < a.nx && gy < a.ny && gz < a.nz) {
+            const long long g = (long long)gz * plane + (long long)gy * a.nx + gx;
+            if (a.weight[g] > a.min_weight) c = a.tsdf[g] < 0.0f ? (SEEN | NEG) : SEEN;
+        }
+        s_code[i] = (uint8_t)c;
+        any_neg |= (int)(c & NEG);
+    }
+    if (!__syncthreads_or(any_neg)) return;
+
+    const int lx = tid & 31, ly = tid >> 5, sh = k.shift;
+    unsigned cases[TZ];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < TZ; ++j) {
+        cases[j] = cube_cases(s_code, (j * VSY + ly) * VSX + lx, VSX, VSX * VSY);
+        if (!cases[j]) continue;
+        const auto cid = [&](int dx, int dy, int dz) {           // below the voxel count: below 2^31
+            return (int)(((long long)((z0 + j + dz) >> sh) * k.cy + ((y0 + ly + dy) >> sh)) * k.cx + ((x0 + lx + dx) >> sh));
+        };
+        cluster_cube_triangles(cases[j], cid, [&](int, int, int) { ++mine; });
+    }
+    int total;
+    const int before = workgroup_prefix(mine, wave_tot, total);
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);       // one per workgroup
+    if (!a.triangles) return;
+    __syncthreads();
+    if (!mine) return;
+    long long tri = (long long)s_base + before;
+#pragma unroll
+    for (int j = 0; j < TZ; ++j) {
+        if (!cases[j]) continue;
+        const auto cid = [&](int dx, int dy, int dz) {
+            return (int)(((long long)((z0 + j + dz) >> sh) * k.cy + ((y0 + ly + dy) >> sh)) * k.cx + ((x0 + lx + dx) >> sh));
+        };
+        cluster_cube_triangles(cases[j], cid, [&](int va, int vb, int vc) {
+            if (tri < a.capacity) {
+                int* r = a.triangles + tri * 3;
+                r[0] = k.cluster_base[va]; r[1] = k.cluster_base[vb]; r[2] = k.cluster_base[vc];
+            }
+            ++tri;
+        });
+    }
+}
+
+long long voxel_count(int nx, int ny, int nz) {                // MAX_VOXELS for anything at or beyond the bound, without overflow
     const long long xy = (long long)nx * ny;                     // < 2^62
     if (xy >= MAX_VOXELS || nz > MAX_VOXELS / xy) return MAX_VOXELS;
     return xy * nz;
@@ -460,6 +655,67 @@ extern "C" int mr_tsdf_mesh_triangles_f32(const float* tsdf, const float* weight
         return MR_ERR_BAD_ARGUMENT;
     a.triangles = triangles; a.vertex_base = const_cast<int*>(vertex_base);
     hipLaunchKernelGGL(tsdf_mesh_triangles_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_mesh_vertices_normals_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny,
+                                                 int32_t nz, const float* origin, float voxel_size, float min_weight, float* vertices,
+                                                 int64_t capacity_vertices, float* normals, int32_t* vertex_base, int64_t* cursor,
+                                                 void* stream) {
+    MeshArgs a;
+    unsigned tiles;
+    if (surface_args(a, tiles, tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight, vertices, capacity_vertices, cursor) ||
+        bad_mesh(nx, ny, nz, vertex_base, vertices) || ((uintptr_t)normals & 3) || (!vertices != !normals))
+        return MR_ERR_BAD_ARGUMENT;
+    a.vertices = vertices; a.vertex_base = vertex_base;
+    hipLaunchKernelGGL(tsdf_mesh_vertex_normals_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a, normals);
+    return (int)hipGetLastError();
+}
+
+namespace {
+
+// beyond surface_args and bad_mesh, of the two cluster entries: the cell and the clusters per axis.  True: a bad argument.
+bool cluster_args(ClusterArgs& k, int cell, int nx, int ny, int* cluster_base) {
+    k.shift = cluster_shift(cell);
+    if (k.shift < 0) return true;
+    k.normals = nullptr; k.cluster_base = cluster_base;
+    k.cx = (nx - 1) / cell + 1; k.cy = (ny - 1) / cell + 1;
+    return false;
+}
+
+}  // namespace
+
+extern "C" int mr_tsdf_mesh_cluster_vertices_f32(const float* tsdf, const float* weight, const uint8_t* colour, int32_t nx, int32_t ny,
+                                                 int32_t nz, const float* origin, float voxel_size, float min_weight, int32_t cell,
+                                                 float* vertices, int64_t capacity_vertices, float* normals, int32_t* cluster_base,
+                                                 int64_t* cursor, void* stream) {
+    MeshArgs a;
+    ClusterArgs k;
+    unsigned tiles;
+    if (surface_args(a, tiles, tsdf, weight, colour, nx, ny, nz, origin, voxel_size, min_weight, vertices, capacity_vertices, cursor) ||
+        bad_mesh(nx, ny, nz, cluster_base, vertices) || cluster_args(k, cell, nx, ny, cluster_base) || ((uintptr_t)normals & 3) ||
+        (normals && !vertices) || nz > 0x7fffffff - KSZ)
+        return MR_ERR_BAD_ARGUMENT;
+    a.vertices = vertices;
+    k.normals = vertices ? normals : nullptr;
+    a.tiles_x = (nx - 1) / KX + 1; a.tiles_y = (ny - 1) / KY + 1;                        // no more tiles than surface_args counted
+    tiles = (unsigned)((long long)a.tiles_x * a.tiles_y * ((nz - 1) / KZ + 1));
+    if (k.normals) hipLaunchKernelGGL(tsdf_mesh_cluster_vertices_kernel<true>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a, k);
+    else hipLaunchKernelGGL(tsdf_mesh_cluster_vertices_kernel<false>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a, k);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_mesh_cluster_triangles_f32(const float* tsdf, const float* weight, int32_t nx, int32_t ny, int32_t nz,
+                                                  float min_weight, int32_t cell, const int32_t* cluster_base, int32_t* triangles,
+                                                  int64_t capacity_triangles, int64_t* cursor, void* stream) {
+    MeshArgs a;
+    ClusterArgs k;
+    unsigned tiles;
+    if (surface_args(a, tiles, tsdf, weight, nullptr, nx, ny, nz, NO_ORIGIN, 1.0f, min_weight, triangles, capacity_triangles, cursor) ||
+        bad_mesh(nx, ny, nz, cluster_base, triangles) || cluster_args(k, cell, nx, ny, const_cast<int*>(cluster_base)))
+        return MR_ERR_BAD_ARGUMENT;
+    a.triangles = triangles;
+    hipLaunchKernelGGL(tsdf_mesh_cluster_triangles_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a, k);
     return (int)hipGetLastError();
 }
 

@@ -16,6 +16,9 @@
 //   tsdf_sparse_mesh_triangles_kernel   a workgroup per slot again: the code byte of its block plus TWO voxels beyond the high faces
 //                                  (10^3, still only the seven + neighbours) and the 9^3 owner masks that follow from them (1.7 KB), then
 //                                  the dense triangle kernel's cases, count and fill; an owner's vertex_base is read in the owner's slot
+//   tsdf_sparse_vertex_normals_kernel, tsdf_sparse_cluster_vertices_kernel, tsdf_sparse_cluster_triangles_kernel   the mesh with a unit
+//                                  normal per vertex, and at a level of detail (one vertex per cluster of 2^3, 4^3 or 8^3 voxels): the
+//                                  dense kernels' rules through tsdf_mesh.h, a workgroup per slot
 //   tsdf_sparse_gather_kernel      a box of voxels into dense arrays, 1 / 0 / 0 where a block has no slot
 // B, BV, pool_index (of the gather) and bad_sparse are in tsdf_common.h, with what the dense volume's kernels run too.
 #include <hip/hip_runtime.h>
@@ -138,9 +141,28 @@ __device__ __forceinline__ void stage_slots(const SparseExtractArgs& a, int* s_s
     s_slot[tid] = s < a.num_slots ? s : -1;
 }
 
+// Is voxel (x, y, z) - counted from the first voxel of block (bx, by, bz), from -1 to 9 - inside the volume, in a block with a slot, and
+// seen?  Then t is its tsdf: what the normals ask of the volume (voxel_gradient, tsdf_mesh.h).  Through the table, not the staged slots:
+// it reaches the - neighbours too.
+struct BlockSample {
+    const SparseExtractArgs& a;
+    int bx, by, bz;
+    __device__ __forceinline__ bool operator()(int x, int y, int z, float& t) const {
+        const int nx = bx + (x >> 3), ny = by + (y >> 3), nz = bz + (z >> 3);        // (>> of -1 is -1)
+        if ((unsigned)nx >= (unsigned)a.nbx || (unsigned)ny >= (unsigned)a.nby || (unsigned)nz >= (unsigned)a.nbz) return false;
+        const int s = a.table[((long long)nz * a.nby + ny) * a.nbx + nx];
+        if (s < 0 || s >= a.num_slots) return false;
+        const long long p = pool_index(s, x, y, z);
+        if (!(a.pool.weight[p] > a.min_weight)) return false;
+        t = a.pool.tsdf[p];
+        return true;
+    }
+};
+
 // EDGES = 3: the axis edges alone, the points of mr_tsdf_sparse_extract_f32.  EDGES = 7: the vertices of the mesh, and vertex_base.
-template <int EDGES>
-__global__ __launch_bounds__(256) void tsdf_sparse_extract_kernel(const SparseExtractArgs a) {
+// NORMALS (the variant tsdf_sparse_vertex_normals_kernel alone): the unit normal of every vertex into normals[3 * index].
+template <int EDGES, bool NORMALS>
+__device__ __forceinline__ void sparse_extract_tile(const SparseExtractArgs& a, float* normals) {
     static_assert(EDGES == 3 || EDGES == 7, "the axis edges, or all a voxel owns");
     __shared__ float s_t[SN];
     __shared__ unsigned s_col[SN];
@@ -210,9 +232,193 @@ __global__ __launch_bounds__(256) void tsdf_sparse_extract_kernel(const SparseEx
 #pragma unroll
                 for (int k = 0; k < 3; ++k) r[k] = (along[e] >> k) & 1u ? p[k] + step : p[k];
                 write_colour(r, cv, s_col[at + s_far[e]], s);
+                if constexpr (NORMALS)
+                    vertex_normal(BlockSample{a, bx, by, bz}, lx, ly, lz + 4 * j, tv, e, s_t[at + s_far[e]], s, normals + rec * 3);
             }
             ++rec;
         }
+    }
+}
+
+template <int EDGES>
+__global__ __launch_bounds__(256) void tsdf_sparse_extract_kernel(const SparseExtractArgs a) { sparse_extract_tile<EDGES, false>(a, nullptr); }
+
+__global__ __launch_bounds__(256) void tsdf_sparse_vertex_normals_kernel(const SparseExtractArgs a, float* normals) {
+    sparse_extract_tile<7, true>(a, normals);
+}
+
+// ---- the clustered level of detail (the dense kernels' rules and code: tsdf_mesh.h): a workgroup per slot, whose block is 64, 8 or 1
+// whole clusters
+struct ClusterArgs {
+    float* normals;                              // vertices only; null: none
+    int* cluster_base;                           // (8 / cell)^3 per slot: written by the vertex kernel, read by the triangle kernel
+    int shift;                                   // cell = 1 << shift
+};
+
+// the vertex kernel's staging (tsdf, colour and code of the block plus one voxel) and masks, then the dense kernel's runs: a lane sums
+// one of the block's 64 runs in the fixed order, the first lane of each cluster - 64, 8 or 1 of them - adds its 1, 8 or 64 runs in order
+constexpr int UNITS = BV / RUN;
+static_assert(SN >= 10 * UNITS, "the run sums (9 floats and a count per run) take the place of the staged tsdf");
+template <bool NORMALS>
+__global__ __launch_bounds__(256) void tsdf_sparse_cluster_vertices_kernel(const SparseExtractArgs a, const ClusterArgs k) {
+    __shared__ float s_t[SN];
+    __shared__ unsigned s_col[SN];
+    __shared__ uint8_t s_code[SN];
+    __shared__ uint8_t s_mask[SN];
+    __shared__ uint8_t s_owns[UNITS];
+    __shared__ int s_slot[8];
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x;
+    const int bi = a.block_of_slot[blockIdx.x];
+    if (bi < 0 || bi >= a.blocks) return;                                    // (a slot the caller counts but no launch filled)
+    const int bx = bi % a.nbx, by = (bi / a.nbx) % a.nby, bz = bi / (a.nbx * a.nby);
+    if (tid < 8) stage_slots(a, s_slot, tid, bx, by, bz);
+    __syncthreads();
+    int any_neg = 0;
+    for (int i = tid; i < SN; i += 256) {
+        const int sx = i % S, sy = (i / S) % S, sz = i / (S * S);
+        const int s = s_slot[(sx >> 3) | ((sy >> 3) << 1) | ((sz >> 3) << 2)];
+        float t = 1.0f;
+        unsigned c = 0u, rgb = 0u;
+        if (s >= 0) {
+            const long long p = (long long)s * BV + (((sz & 7) * B + (sy & 7)) * B + (sx & 7));
+            if (a.pool.weight[p] > a.min_weight) {
+                t = a.pool.tsdf[p];
+                c = t < 0.0f ? (SEEN | NEG) : SEEN;
+                if (a.pool.colour) rgb = a.pool.colour[p];
+            }
+        }
+        s_t[i] = t;
+        s_col[i] = rgb;
+        s_code[i] = (uint8_t)c;
+        any_neg |= (int)(c & NEG);
+    }
+    if (!__syncthreads_or(any_neg)) return;
+    for (int i = tid; i < BV; i += 256) {
+        const int at = ((i >> 6) * S + ((i >> 3) & 7)) * S + (i & 7);
+        s_mask[at] = (uint8_t)edge_mask<7>(s_code, at, S, S * S);
+    }
+    __syncthreads();
+
+    // the block is 64 runs of 8 voxels for every cell (tsdf_mesh.h): run `run` of cluster q of the block's is unit q * runs + run, on
+    // thread 4 * unit - sixteen of them in every wave
+    const int sh = k.shift, qn = B >> sh, runs = (1 << (3 * sh)) / RUN;
+    const int unit = tid >> 2, q = unit / runs, run = unit % runs;
+    const bool mine = (tid & 3) == 0;
+    const int lx = (q % qn) << sh, ly = ((q / qn) % qn) << sh, lz = (q / (qn * qn)) << sh;           // the cluster's first voxel in the block
+    const int at0 = (lz * S + ly) * S + lx;
+    const int owns = mine ? run_owns(s_mask, at0, S, S * S, sh, run) : 0;
+    if (mine) s_owns[unit] = (uint8_t)owns;
+    __syncthreads();
+    int has = 0;                                 // of the lane of the cluster's first run: does the cluster own a vertex?
+    if (mine && run == 0)
+        for (int r = 0; r < runs; ++r) has |= s_owns[unit + r];
+    int total;
+    const int before = workgroup_prefix(has, wave_tot, total);
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);   // one per workgroup
+    if (!a.records) return;
+    constexpr int N = NORMALS ? 9 : 6;
+    float sum[N];
+    int count = 0;
+    if (owns) {
+        const auto vertex = [&](int dx, int dy, int dz, int at, int e, float* r) {
+            const int x = lx + dx, y = ly + dy, z = lz + dz;
+            const int far = (int)(EDGE_ALONG[e] & 1u) + (int)((EDGE_ALONG[e] >> 1) & 1u) * S + (int)(EDGE_ALONG[e] >> 2) * (S * S);
+            const float p[3] = {a.ox + (float)((long long)bx * B + x) * a.voxel, a.oy + (float)((long long)by * B + y) * a.voxel,
+                                a.oz + (float)((long long)bz * B + z) * a.voxel};
+            const float tv = s_t[at], tn = s_t[at + far];
+            const float s = edge_record(tv, tn, p, e, a.voxel, s_col[at], s_col[at + far], r);
+            if constexpr (NORMALS) vertex_normal(BlockSample{a, bx, by, bz}, x, y, z, tv, e, tn, s, r + 6);
+        };
+        count = run_sum<NORMALS>(s_mask, at0, S, S * S, sh, run, sum, vertex);
+    }
+    // the sums of the runs and, last, their counts go through LDS as [sum][run], in the place of the staged tsdf, which every lane has
+    // finished reading
+    __syncthreads();
+    float* s_part = s_t;
+    if (mine) {
+#pragma unroll
+        for (int c = 0; c < N; ++c) s_part[c * UNITS + unit] = owns ? sum[c] : 0.0f;
+        s_part[N * UNITS + unit] = (float)count;
+    }
+    __syncthreads();                             // (also: s_base is there)
+    if (!has) return;
+    const long long rec = (long long)s_base + before;
+    k.cluster_base[(long long)blockIdx.x * (qn * qn * qn) + q] = (int)rec;
+    if (rec >= a.capacity) return;
+    float out[9];
+    cluster_combine<NORMALS>(s_part + unit, UNITS, runs, out);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) a.records[rec * 6 + c] = out[c];
+    if constexpr (NORMALS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) k.normals[rec * 3 + c] = out[6 + c];
+    }
+}
+
+// the triangle kernel's cubes, two per thread, over the codes of the block plus ONE voxel (no masks: a vertex is its owner's cluster)
+__global__ __launch_bounds__(256) void tsdf_sparse_cluster_triangles_kernel(const SparseExtractArgs a, const ClusterArgs k) {
+    __shared__ uint8_t s_code[SN];
+    __shared__ int s_slot[8];
+    __shared__ int wave_tot[4];
+    __shared__ unsigned long long s_base;
+    const int tid = threadIdx.x;
+    const int bi = a.block_of_slot[blockIdx.x];
+    if (bi < 0 || bi >= a.blocks) return;                                    // (a slot the caller counts but no launch filled)
+    const int bx = bi % a.nbx, by = (bi / a.nbx) % a.nby, bz = bi / (a.nbx * a.nby);
+    if (tid < 8) stage_slots(a, s_slot, tid, bx, by, bz);
+    __syncthreads();
+    int any_neg = 0;
+    for (int i = tid; i < SN; i += 256) {
+        const int sx = i % S, sy = (i / S) % S, sz = i / (S * S);            // 8 lies in the + neighbour
+        const int s = s_slot[(sx >> 3) | ((sy >> 3) << 1) | ((sz >> 3) << 2)];
+        unsigned c = 0u;
+        if (s >= 0) {
+            const long long p = (long long)s * BV + (((sz & 7) * B + (sy & 7)) * B + (sx & 7));
+            if (a.pool.weight[p] > a.min_weight) c = a.pool.tsdf[p] < 0.0f ? (SEEN | NEG) : SEEN;
+        }
+        s_code[i] = (uint8_t)c;
+        any_neg |= (int)(c & NEG);
+    }
+    if (!__syncthreads_or(any_neg)) return;
+
+    const int lx = tid & 7, ly = (tid >> 3) & 7, lz = tid >> 6, sh = k.shift, qn = B >> sh;
+    // the cluster of voxel (x, y, z) of the staged block, 0 .. 8, in its own slot's part of cluster_base: below 2^31 (checked by the
+    // entry).  A corner of a cube with a case is seen, so its block has a slot.
+    const auto cluster_at = [&](int x, int y, int z) {
+        const int s = s_slot[(x >> 3) | ((y >> 3) << 1) | ((z >> 3) << 2)];
+        return (s * qn + ((z & 7) >> sh)) * qn * qn + ((y & 7) >> sh) * qn + ((x & 7) >> sh);
+    };
+    unsigned cases[2];
+    int mine = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        cases[j] = cube_cases(s_code, ((lz + 4 * j) * S + ly) * S + lx, S, S * S);
+        if (!cases[j]) continue;
+        const auto cid = [&](int dx, int dy, int dz) { return cluster_at(lx + dx, ly + dy, lz + 4 * j + dz); };
+        cluster_cube_triangles(cases[j], cid, [&](int, int, int) { ++mine; });
+    }
+    int total;
+    const int before = workgroup_prefix(mine, wave_tot, total);
+    if (total == 0) return;
+    if (tid == 0) s_base = atomicAdd(a.cursor, (unsigned long long)total);   // one per workgroup
+    if (!a.triangles) return;
+    __syncthreads();
+    if (!mine) return;
+    long long tri = (long long)s_base + before;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (!cases[j]) continue;
+        const auto cid = [&](int dx, int dy, int dz) { return cluster_at(lx + dx, ly + dy, lz + 4 * j + dz); };
+        cluster_cube_triangles(cases[j], cid, [&](int va, int vb, int vc) {
+            if (tri < a.capacity) {
+                int* r = a.triangles + tri * 3;
+                r[0] = k.cluster_base[va]; r[1] = k.cluster_base[vb]; r[2] = k.cluster_base[vc];
+            }
+            ++tri;
+        });
     }
 }
 
@@ -499,6 +705,71 @@ extern "C" int mr_tsdf_sparse_mesh_triangles_f32(const int32_t* table, int32_t n
     if (num_slots == 0) return 0;
     a.triangles = triangles; a.vertex_base = const_cast<int*>(vertex_base);
     hipLaunchKernelGGL(tsdf_sparse_mesh_triangles_kernel, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_sparse_mesh_vertices_normals_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf,
+                                                        const float* weight, const uint8_t* colour, const int32_t* block_of_slot,
+                                                        int64_t num_slots, const float* origin, float voxel_size, float min_weight,
+                                                        float* vertices, int64_t capacity_vertices, float* normals, int32_t* vertex_base,
+                                                        int64_t* cursor, void* stream) {
+    SparseExtractArgs a;
+    if (surface_args(a, table, nbx, nby, nbz, tsdf, weight, colour, block_of_slot, num_slots, origin, voxel_size, min_weight, vertices,
+                     capacity_vertices, cursor) ||
+        ((uintptr_t)vertex_base & 3) || (vertices && !vertex_base) || ((uintptr_t)normals & 3) || (!vertices != !normals))
+        return MR_ERR_BAD_ARGUMENT;
+    if (num_slots == 0) return 0;
+    a.records = vertices; a.vertex_base = vertex_base;
+    hipLaunchKernelGGL(tsdf_sparse_vertex_normals_kernel, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a, normals);
+    return (int)hipGetLastError();
+}
+
+namespace {
+
+// beyond surface_args, of the two cluster entries: the cell, cluster_base and its int32 indices.  True: a bad argument.
+bool cluster_args(ClusterArgs& k, int cell, long long num_slots, const int* cluster_base, const void* out) {
+    k.shift = cluster_shift(cell);
+    if (k.shift < 0 || ((uintptr_t)cluster_base & 3) || (out && !cluster_base)) return true;
+    const int qn = B >> k.shift;
+    if (num_slots * (qn * qn * qn) >= (1ll << 31)) return true;
+    k.normals = nullptr; k.cluster_base = const_cast<int*>(cluster_base);
+    return false;
+}
+
+}  // namespace
+
+extern "C" int mr_tsdf_sparse_mesh_cluster_vertices_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf,
+                                                        const float* weight, const uint8_t* colour, const int32_t* block_of_slot,
+                                                        int64_t num_slots, const float* origin, float voxel_size, float min_weight,
+                                                        int32_t cell, float* vertices, int64_t capacity_vertices, float* normals,
+                                                        int32_t* cluster_base, int64_t* cursor, void* stream) {
+    SparseExtractArgs a;
+    ClusterArgs k;
+    if (surface_args(a, table, nbx, nby, nbz, tsdf, weight, colour, block_of_slot, num_slots, origin, voxel_size, min_weight, vertices,
+                     capacity_vertices, cursor) ||
+        cluster_args(k, cell, num_slots, cluster_base, vertices) || ((uintptr_t)normals & 3) || (normals && !vertices))
+        return MR_ERR_BAD_ARGUMENT;
+    if (num_slots == 0) return 0;
+    a.records = vertices;
+    k.normals = vertices ? normals : nullptr;
+    if (k.normals) hipLaunchKernelGGL(tsdf_sparse_cluster_vertices_kernel<true>, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a, k);
+    else hipLaunchKernelGGL(tsdf_sparse_cluster_vertices_kernel<false>, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a, k);
+    return (int)hipGetLastError();
+}
+
+extern "C" int mr_tsdf_sparse_mesh_cluster_triangles_f32(const int32_t* table, int32_t nbx, int32_t nby, int32_t nbz, const float* tsdf,
+                                                         const float* weight, const int32_t* block_of_slot, int64_t num_slots,
+                                                         float min_weight, int32_t cell, const int32_t* cluster_base, int32_t* triangles,
+                                                         int64_t capacity_triangles, int64_t* cursor, void* stream) {
+    SparseExtractArgs a;
+    ClusterArgs k;
+    if (surface_args(a, table, nbx, nby, nbz, tsdf, weight, nullptr, block_of_slot, num_slots, NO_ORIGIN, 1.0f, min_weight, triangles,
+                     capacity_triangles, cursor) ||
+        cluster_args(k, cell, num_slots, cluster_base, triangles))
+        return MR_ERR_BAD_ARGUMENT;
+    if (num_slots == 0) return 0;
+    a.triangles = triangles;
+    hipLaunchKernelGGL(tsdf_sparse_cluster_triangles_kernel, dim3((unsigned)num_slots), dim3(256), 0, (hipStream_t)stream, a, k);
     return (int)hipGetLastError();
 }
 

@@ -55,16 +55,23 @@ def write_ply(file, data):
         file.write(data.tobytes())
 
 
-def write_mesh_ply(file, vertices, triangles):
+def write_mesh_ply(file, vertices, triangles, normals=None):
     """A triangle mesh as a binary little-endian .ply: `write_ply`'s six float vertex properties, then `element face M` with
     `property list uchar int vertex_indices` (13 bytes per triangle).  `vertices`: (n, 6) fp32 numpy array x y z red green blue,
-    `triangles`: (m, 3) integer numpy array of indices into it (what monorec_amd.tsdf_fusion.TSDFVolume.mesh returns, on the host)."""
+    `triangles`: (m, 3) integer numpy array of indices into it (what monorec_amd.tsdf_fusion.TSDFVolume.mesh returns, on the host).
+    `normals`: None, or (n, 3) fp32 - the vertex records then are 9 floats, with the properties nx ny nz after blue."""
     vertices = np.ascontiguousarray(vertices, dtype="<f4").reshape(-1, 6)
     triangles = np.asarray(triangles).reshape(-1, 3)
     if len(triangles) and (triangles.min() < 0 or triangles.max() >= len(vertices)):
         raise ValueError(f"write_mesh_ply: triangle indices outside the {len(vertices)} vertices")
+    names = ("x", "y", "z", "red", "green", "blue")
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype="<f4").reshape(-1, 3)
+        if len(normals) != len(vertices):
+            raise ValueError(f"write_mesh_ply: {len(normals)} normals for {len(vertices)} vertices")
+        vertices, names = np.concatenate([vertices, normals], axis=1), names + ("nx", "ny", "nz")
     lines = ["ply", "format binary_little_endian 1.0", f"element vertex {len(vertices)}"]
-    lines += [f"property float {name}" for name in ("x", "y", "z", "red", "green", "blue")]
+    lines += [f"property float {name}" for name in names]
     lines += [f"element face {len(triangles)}", "property list uchar int vertex_indices", "end_header"]
     file.write(("\n".join(lines) + "\n").encode("ascii"))
     file.write(vertices.tobytes())

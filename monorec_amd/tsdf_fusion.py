@@ -39,8 +39,16 @@ integrate launch on the same stream; nothing is copied to the host before the su
 `Fusion.score()` renders the fused volume into every exported keyframe again and scores it against the dataset's targets; with
 `render_dir`, `write()` also writes those views as 16-bit centimetre PNGs and JPEGs.
 
-Not here: vertex normals for the mesh (the render has per-pixel normals), decimation or marching cubes; a mesh of a region of the
-sparse volume (it meshes the whole of it), growth of its pool, eviction or hashing; a cap on the weight; fusing across ranks (`run` is single-process)."""
+`mesh(normals=True)` adds a unit normal per vertex (the gradient of the tsdf at the two ends of the vertex's edge, interpolated like
+its position), `mesh(cell=2 | 4 | 8)` returns a clustered level of detail: one vertex per cluster of cell^3 voxels that owns a vertex
+of the full mesh, and the full mesh's triangles between three different clusters (`mr_tsdf_mesh_cluster_vertices_f32`,
+`mr_tsdf_mesh_cluster_triangles_f32` and their `mr_tsdf_sparse_` twins; a cluster is summed as a tree of a fixed shape, so there are no
+float atomics and tests/tsdf_mesh_lod_ref.py pins the result bit for bit).  The runner keys `mesh_cell` and `mesh_normals` pass them to the
+mesh file.
+
+Not here: quadric or edge-collapse decimation, marching cubes; repeated triangles of a clustered mesh are kept (removing one would
+leave a directed edge without its reverse); a mesh of a region of the sparse volume (it meshes the whole of it), growth of its pool,
+eviction or hashing; a cap on the weight; fusing across ranks (`run` is single-process)."""
 import contextlib
 import ctypes
 import functools
@@ -59,6 +67,8 @@ MAX_FRAMES = _lib.MR_TSDF_MAX_FRAMES          # keyframes per integrate launch
 TILE = _lib.MR_TSDF_TILE                      # (x, y, z) voxels of one workgroup of the integrate kernel: the unit of its frustum culling
 BLOCK = _lib.MR_TSDF_BLOCK                    # edge of one block of `SparseTSDFVolume` in voxels
 BRICK = _lib.MR_TSDF_BRICK                    # edge of one brick of `TSDFVolume.skip_grid` in voxels
+MESH_CELLS = _lib.MR_TSDF_MESH_CELLS          # the `cell` of `mesh`: 1 (the full mesh) or the cluster edge of a level of detail, in voxels
+CLUSTER_TILE = _lib.MR_TSDF_CLUSTER_TILE      # (x, y, z) voxels of one workgroup of the dense volume's clustered vertex kernel
 MAX_RENDER_SAMPLES = 1 << 20                  # samples per ray of one render launch
 
 
@@ -129,6 +139,17 @@ def dims_of_bounds(bounds, voxel_size):
     if lo.shape != (3,) or hi.shape != (3,) or not np.all(hi >= lo):
         raise ValueError(f"bounds {bounds}: expected ((x0, y0, z0), (x1, y1, z1)) with hi >= lo")
     return tuple(int(math.ceil(float(d) / float(voxel_size) - 1e-9)) + 1 for d in hi - lo)
+
+
+def _mesh_options(cell, normals):
+    """`cell` checked, and the keywords of `mesh` that differ from its defaults: none for the full mesh without normals."""
+    if isinstance(cell, bool) or cell not in MESH_CELLS:
+        raise ValueError(f"monorec_amd.tsdf_fusion: cell {cell!r} must be one of {', '.join(str(c) for c in MESH_CELLS)} "
+                         f"(1: the full mesh; the others divide the block of {BLOCK} voxels)")
+    more = {} if cell == 1 else {"cell": int(cell)}
+    if normals:
+        more["normals"] = True
+    return more
 
 
 def volume_bytes(dims, colour=True):
@@ -269,56 +290,78 @@ class _Volume:
         return records.shape[0]
 
     # -- the surface as a mesh
-    def mesh_counts(self, min_weight=0):
-        """(vertices, triangles) `mesh(min_weight)` would return: the two count launches and one read."""
+    def mesh_counts(self, min_weight=0, cell=1):
+        """(vertices, triangles) `mesh(min_weight, cell)` would return: the two count launches and one read."""
+        more = _mesh_options(cell, False)
         cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
         with torch.cuda.device(self.device):
-            self._mesh_launches(min_weight, cursor)
+            self._mesh_launches(min_weight, cursor, **more)
         n, m = cursor.tolist()
         return int(n), int(m)
 
-    def mesh(self, min_weight=0):
+    def mesh(self, min_weight=0, cell=1, normals=False):
         """The zero-crossing surface between voxels of weight > min_weight as a welded triangle mesh on the device: vertices (n, 6) fp32
         x y z red green blue - those on the grid's axis edges are `extract(min_weight)`'s records - and triangles (m, 3) int32 indices
         into them, wound so that (b - a) x (c - a) points from inside (tsdf < 0) to outside.  Marching tetrahedra: closed wherever the
         voxels are seen, about twice the triangles of marching cubes.  A count launch per array, one read of both counts, a fill launch per
         array; 4 bytes per voxel of workspace for the time of the call - per voxel of the grid for `TSDFVolume`, per voxel of the allocated
         blocks for `SparseTSDFVolume`, which meshes its blocks as they are (`mr_tsdf_sparse_mesh_vertices_f32`,
-        `mr_tsdf_sparse_mesh_triangles_f32`).  The order of both arrays is unspecified."""
-        n, m = self.mesh_counts(min_weight)
+        `mr_tsdf_sparse_mesh_triangles_f32`).  The order of both arrays is unspecified.
+
+        `normals=True` returns (vertices, triangles, vertex_normals): (n, 3) fp32, unit length or exactly 0 - the gradient of the tsdf
+        (central differences, one-sided where a neighbour is outside the grid, unseen or without storage) at the two ends of the
+        vertex's edge, interpolated like its position; it points where the winding does.  `cell` = 2, 4 or 8 returns a level of
+        detail: the voxels are grouped into clusters of cell^3, every cluster that owns a vertex of the full mesh emits one vertex -
+        the mean position and colour of those it owns, the normalised sum of their normals - and every triangle of the full mesh
+        between three different clusters is kept, with its winding; the others are dropped.  Every directed edge is still matched by
+        its reverse wherever the full mesh is closed; triangles that repeat are kept, or that would break.  The sums run in one fixed
+        order (include/monorec_hip.h; tests/tsdf_mesh_lod_ref.py restates them), so the result is deterministic.  The workspace is 4
+        bytes per cluster.  `cell=1, normals=False` is exactly the call without them.  Another cell raises a ValueError."""
+        more = _mesh_options(cell, normals)
+        n, m = self.mesh_counts(min_weight, cell)
         if n >= 2 ** 31:
             raise ValueError(f"monorec_amd.tsdf_fusion: a mesh of {n} vertices does not fit int32 indices; raise min_weight or mesh a part")
         vertices = torch.empty(n, 6, dtype=torch.float32, device=self.device)
         triangles = torch.empty(m, 3, dtype=torch.int32, device=self.device)
+        if normals:
+            more["normals"] = torch.empty(n, 3, dtype=torch.float32, device=self.device)
         if n:
             cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
-            vertex_base = torch.empty(self._mesh_voxels(), dtype=torch.int32, device=self.device)
+            vertex_base = torch.empty(self._mesh_voxels() if cell == 1 else self._mesh_clusters(cell), dtype=torch.int32, device=self.device)
             with torch.cuda.device(self.device):
-                self._mesh_launches(min_weight, cursor, vertices, triangles, vertex_base)
+                self._mesh_launches(min_weight, cursor, vertices, triangles, vertex_base, **more)
             if cursor.tolist() != [n, m]:
                 raise RuntimeError("monorec_amd.tsdf_fusion: the volume changed between the count and the fill launches")
-        return vertices, triangles
+        return (vertices, triangles, more["normals"]) if normals else (vertices, triangles)
 
-    def _mesh_launches(self, min_weight, cursor, vertices=None, triangles=None, vertex_base=None):
-        """The two mesh entries on the current stream, the vertex one first: counting (no outputs) or filling."""
+    def _mesh_launches(self, min_weight, cursor, vertices=None, triangles=None, vertex_base=None, cell=1, normals=None):
+        """The two mesh entries on the current stream, the vertex one first: counting (no outputs) or filling.  `cell` > 1: the cluster
+        entries, with `vertex_base` their cluster_base; `normals`: the tensor the vertex entry fills beside `vertices`."""
         lib, nothing = _lib.load(), (None, 0)
         _, vertex_entry, triangle_entry = self._SURFACE_ENTRIES
-        with_colour, without_colour = self._surface_args(vertex_base)
+        with_colour, without_colour = self._surface_args(vertex_base, cell)
         base = vertex_base.data_ptr() if vertex_base is not None else None
         out = nothing if vertices is None else (vertices.data_ptr(), vertices.shape[0])
+        cells, beside = (), ()
+        if cell != 1:
+            vertex_entry, triangle_entry = (name.replace("_mesh_", "_mesh_cluster_") for name in (vertex_entry, triangle_entry))
+            cells, beside = (int(cell),), (normals.data_ptr() if normals is not None else None,)
+        elif normals is not None:
+            vertex_entry, beside = vertex_entry.replace("_vertices_", "_vertices_normals_"), (normals.data_ptr(),)
         if vertices is None or vertices.shape[0]:
-            _lib.check(getattr(lib, vertex_entry)(*with_colour, self._origin, self.voxel_size, float(min_weight), out[0], out[1], base,
-                                                  cursor.data_ptr(), self._stream()), vertex_entry)
+            _lib.check(getattr(lib, vertex_entry)(*with_colour, self._origin, self.voxel_size, float(min_weight), *cells, out[0], out[1], *beside,
+                                                  base, cursor.data_ptr(), self._stream()), vertex_entry)
         out = nothing if triangles is None else (triangles.data_ptr(), triangles.shape[0])
         if triangles is None or triangles.shape[0]:
-            _lib.check(getattr(lib, triangle_entry)(*without_colour, float(min_weight), base, out[0], out[1], cursor.data_ptr() + 8,
+            _lib.check(getattr(lib, triangle_entry)(*without_colour, float(min_weight), *cells, base, out[0], out[1], cursor.data_ptr() + 8,
                                                     self._stream()), triangle_entry)
 
-    def save_mesh_ply(self, file, min_weight=0):
-        """The mesh as a binary .ply (`pointcloud.write_mesh_ply`) to a path or a binary file object.  Returns (vertices, triangles)."""
-        vertices, triangles = (t.cpu().numpy() for t in self.mesh(min_weight))
-        _write(file, write_mesh_ply, vertices, triangles)
-        return vertices.shape[0], triangles.shape[0]
+    def save_mesh_ply(self, file, min_weight=0, cell=1, normals=False):
+        """The mesh as a binary .ply (`pointcloud.write_mesh_ply`) to a path or a binary file object; `cell` and `normals` as for `mesh`,
+        the normals as the properties nx ny nz.  Returns (vertices, triangles)."""
+        arrays = [t.cpu().numpy() for t in self.mesh(min_weight, **_mesh_options(cell, normals))]
+        _write(file, write_mesh_ply, *arrays)
+        return arrays[0].shape[0], arrays[1].shape[0]
 
     # -- the volume seen from a camera
     def render(self, cam_to_world, intrinsics, height, width, t_min=0.0, t_max=None, step=None, min_weight=0, normals=True, colour=True,
@@ -427,13 +470,17 @@ class TSDFVolume(_Volume):
     # -- surface
     _SURFACE_ENTRIES = ("mr_tsdf_extract_f32", "mr_tsdf_mesh_vertices_f32", "mr_tsdf_mesh_triangles_f32")
 
-    def _surface_args(self, vertex_base=None):
+    def _surface_args(self, vertex_base=None, cell=1):
         args = self._volume_args()
         return args, args[:2] + args[3:]
 
     def _mesh_voxels(self):
         """Elements of `mesh()`'s vertex_base: one per voxel of the grid."""
         return self.tsdf.numel()
+
+    def _mesh_clusters(self, cell):
+        """Elements of `mesh(cell=...)`'s cluster_base: one per cluster of the grid, partial ones on the high side included."""
+        return math.prod((d + cell - 1) // cell for d in self.dims)
 
     # -- the volume seen from a camera
     def skip_grid(self, min_weight=0):
@@ -595,15 +642,20 @@ class SparseTSDFVolume(_Volume):
     # -- surface
     _SURFACE_ENTRIES = ("mr_tsdf_sparse_extract_f32", "mr_tsdf_sparse_mesh_vertices_f32", "mr_tsdf_sparse_mesh_triangles_f32")
 
-    def _surface_args(self, vertex_base=None):
-        """Over the allocated slots (one read of the cursor), or over those a mesh's `vertex_base` was sized for."""
-        slots = self.allocated_blocks() if vertex_base is None else vertex_base.numel() // BLOCK ** 3
+    def _surface_args(self, vertex_base=None, cell=1):
+        """Over the allocated slots (one read of the cursor), or over those a mesh's `vertex_base` (with `cell` > 1: its cluster_base)
+        was sized for."""
+        slots = self.allocated_blocks() if vertex_base is None else vertex_base.numel() // (BLOCK // cell) ** 3
         args = self._table_args()
         return args + (self.block_of_slot.data_ptr(), slots), args[:6] + (self.block_of_slot.data_ptr(), slots)
 
     def _mesh_voxels(self):
         """Elements of `mesh()`'s vertex_base: one per pool voxel of the allocated blocks (one read of the cursor)."""
         return self.allocated_blocks() * BLOCK ** 3
+
+    def _mesh_clusters(self, cell):
+        """Elements of `mesh(cell=...)`'s cluster_base: (8 / cell)^3 per allocated block (one read of the cursor)."""
+        return self.allocated_blocks() * (BLOCK // cell) ** 3
 
     # -- the volume seen from a camera
     def _render_shared(self, march, min_weight, skip):
@@ -779,7 +831,7 @@ FUSED_METRICS = tuple(f"{base}_sparse_onlyvalid_metric" for base in ("abs_rel", 
 
 def fusion_settings(config):
     """The fusion keys of a runner config, checked: dict(voxel_size, trunc, bounds, max_bytes, fuse_batch, file_name, mesh_file_name,
-    save_volume, fused_metrics, render_dir)."""
+    save_volume, fused_metrics, render_dir).  `mesh_cell` and `mesh_normals` are checked here too; `mesh_settings` returns them."""
     voxel = float(config.get("voxel_size", 0.1))
     trunc_voxels = float(config.get("trunc_voxels", 5))
     batch = int(config.get("fuse_batch", 4))
@@ -799,9 +851,22 @@ def fusion_settings(config):
     if not isinstance(fused_metrics, (list, tuple)) or any(name not in FUSED_METRICS for name in fused_metrics):
         raise ValueError(f"monorec_amd.tsdf_fusion: fused_metrics {fused_metrics!r} must be a list of *_sparse_onlyvalid_metric names "
                          f"({', '.join(FUSED_METRICS)}): a render is 0 where no surface was hit, which only they leave out")
+    mesh_settings(config)                                      # checked here, with the other keys; `Fusion` keeps what it returns
     return dict(voxel_size=voxel, trunc=trunc_voxels * voxel, bounds=bounds, max_bytes=int(config.get("tsdf_max_bytes", 8 << 30)),
                 fuse_batch=batch, file_name=config.get("file_name", "tsdf.ply"), mesh_file_name=config.get("mesh_file_name", None),
                 save_volume=config.get("save_volume", None), fused_metrics=list(fused_metrics), render_dir=config.get("render_dir", None))
+
+
+def mesh_settings(config):
+    """The runner keys `mesh_cell` (default 1) and `mesh_normals` (default false), checked, as the keywords of `save_mesh_ply` that
+    differ from its defaults: what `Fusion.write()` passes on for `mesh_file_name`, with and without `sparse_mesh`."""
+    mesh_cell, mesh_normals = config.get("mesh_cell", 1), config.get("mesh_normals", False)
+    if isinstance(mesh_cell, bool) or mesh_cell not in MESH_CELLS:
+        raise ValueError(f"monorec_amd.tsdf_fusion: mesh_cell {mesh_cell!r} must be one of {', '.join(str(c) for c in MESH_CELLS)} "
+                         f"(1: the full mesh; a larger cell: one vertex per cluster of cell^3 voxels)")
+    if not isinstance(mesh_normals, bool):
+        raise ValueError(f"monorec_amd.tsdf_fusion: mesh_normals {mesh_normals!r} must be true or false")
+    return _mesh_options(int(mesh_cell), mesh_normals)
 
 
 def sparse_setting(config):
@@ -842,6 +907,7 @@ class Fusion:
     def __init__(self, config, model=None, dataset=None, device="cuda:0"):
         self.config, self.settings, self.sparse = config, fusion_settings(config), sparse_setting(config)
         self.sparse_render, self.sparse_mesh = sparse_render_setting(config), sparse_mesh_setting(config)
+        self.mesh_options = mesh_settings(config)              # cell and normals of the mesh file, where they are not the defaults
         settings = self.settings
         if settings["bounds"] is not None:
             self._check_dense_outputs(settings["bounds"])         # before the model is built
@@ -937,7 +1003,8 @@ class Fusion:
         os.makedirs(out_dir, exist_ok=True)
         count = self.volume.save_ply(os.path.join(out_dir, self.settings["file_name"]))
         if self.settings["mesh_file_name"] is not None:
-            self.mesh_counts = self.meshed().save_mesh_ply(os.path.join(out_dir, self.settings["mesh_file_name"]))
+            self.mesh_counts = self.meshed().save_mesh_ply(os.path.join(out_dir, self.settings["mesh_file_name"]),
+                                                           **self.mesh_options)
         if self.settings["save_volume"] is not None:
             self.volume.save(self.settings["save_volume"])
         if self.settings["render_dir"] is not None:
@@ -1007,7 +1074,8 @@ def run(config, model=None, dataset=None, device="cuda:0"):
     """Fuse the keyframes of a config of `tsdf_export.run`'s shape (same `data_set`, `arch`, `start` / `end`, `roi`, `min_d` / `max_d`,
     `use_mask`) and write the surface points to `output_dir/file_name` (default `tsdf.ply`).  Optional keys: `voxel_size` (0.1),
     `trunc_voxels` (5), `mesh_file_name` (None; a name: the surface is also written as a triangle mesh, `TSDFVolume.save_mesh_ply`, next to
-    the points), `bounds` (else `bounds_from_frusta` over the window's exported keyframe poses and `max_d`; without both it
+    the points), `mesh_cell` (1; 2, 4 or 8: that file holds the clustered level of detail `mesh(cell=...)`), `mesh_normals` (false; true:
+    it carries a unit normal per vertex), `bounds` (else `bounds_from_frusta` over the window's exported keyframe poses and `max_d`; without both it
     raises), `tsdf_max_bytes`, `fuse_batch` (keyframes per integrate launch, default 4), `save_volume` (a path for `TSDFVolume.save`),
     `render_dir` (a directory for `Fusion.write_renders`), `fused_metrics` (names for `Fusion.score()`; `main` prints its result),
     `sparse_volume` (false; true: fuse into a `SparseTSDFVolume` over the same bounds with `tsdf_max_bytes` as the budget of table and pool -
