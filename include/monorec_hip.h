@@ -14,6 +14,17 @@
  *     so all entry points may be recorded into a hipGraph (stream capture).
  *   - return value: 0 on success, a positive hipError_t, or a negative MR_ERR_* code. Nothing throws
  *     across the boundary. mr_error_string() maps a code to text.
+ *   - this file is the only statement of the ABI: the Python binding (monorec_amd/_lib.py) reads it at import and builds its ctypes
+ *     prototypes, structs and constants from it.  It reads these forms, and anything else at top level makes the import raise:
+ *       #define MR_NAME <integer expression over decimal / hex literals, + - * ( ) and earlier MR_ names>, also inside an
+ *         #ifndef MR_NAME ... #endif that gives a default;
+ *       enum { MR_NAME = <such an expression>, ... };
+ *       typedef struct [tag] { <type> name[, name...]; ... } mr_...;  fields scalar, pointer or array of <such an expression>;
+ *       <type> mr_...(<type> name, ...);  or (void);  what stands in #ifdef MR_DIAGNOSTIC_LIBRARY is typed when exported, not required.
+ *     <type> is int, int32_t, int64_t, float, double, size_t, a pointer (to those, to void, char or a fixed-width integer, to a
+ *     pointer, or to a struct declared earlier here), and const char* for a return value.  A struct the host fills carries its name as
+ *     the tag and the binding takes a typed pointer to it; a struct the device fills (mr_median_stats) is declared without a tag, and a
+ *     pointer to it is a device address like every other pointer.
  */
 #ifndef MONOREC_HIP_H
 #define MONOREC_HIP_H

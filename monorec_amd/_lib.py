@@ -1,403 +1,190 @@
-"""ctypes binding of libmonorec_hip.so (include/monorec_hip.h).
+"""ctypes binding of libmonorec_hip.so, read from include/monorec_hip.h when this module is imported.
+
+The header is the only statement of the C ABI: `ABI`, `DIAGNOSTIC_ABI`, the `ctypes.Structure` classes (`mr_conv_desc` -> `ConvDesc`)
+and the integer constants below are built from what `parse_header` reads there, so a new entry point, struct field or constant is an
+edit of the header (and of the .hip file behind it), never of this file.  The parser knows exactly the declaration forms the header
+uses (its "Conventions" list them) and raises on anything else - a declaration it cannot read is an error, not a hole in the binding.
 
 There is deliberately no fallback: if the HIP library is missing or does not export the whole
 ABI, importing the kernels raises - the product path never silently runs on PyTorch/CPU ops.
 """
 import ctypes
 import os
+import re
+import types
 
-MR_MAX_SOURCES = 3
-MR_MAX_FRAMES = 8
+HEADER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "monorec_hip.h")
 
-ACT_NONE, ACT_RELU, ACT_LEAKY_RELU, ACT_SIGMOID, ACT_ABS_TANH_AFFINE = range(5)
-IN_DIRECT, IN_UPSAMPLE2, IN_MAXPOOL2 = range(3)
-TF_NONE, TF_RESNET_NORM = range(2)
+# the one type table: C scalar -> ctypes.  Every pointer is a c_void_p (it takes ctypes arrays, byref(), None and the integer of
+# tensor.data_ptr() alike), but for `const char*` as a return type and a pointer to a struct the header declares WITH a tag
+# (`typedef struct mr_x { ... } mr_x;`: a struct the host fills), which is POINTER(its class).  A struct declared without a tag is one
+# the device fills (mr_median_stats): it gets a class, to read a copy with, and a pointer to it is a device address like any other
+C_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+             "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_POINTEES = ("void", "char", "uint8_t", "int16_t", "uint16_t", "uint32_t")      # type names that occur behind a `*` only
 
-_c_float_p = ctypes.POINTER(ctypes.c_float)
-
-
-class ConvDesc(ctypes.Structure):
-    """mirror of `mr_conv_desc` (include/monorec_hip.h) - field order and types must match."""
-    _fields_ = [
-        ("src", ctypes.c_void_p * MR_MAX_SOURCES),
-        ("src_channels", ctypes.c_int32 * MR_MAX_SOURCES),
-        ("num_src", ctypes.c_int32),
-        ("batch", ctypes.c_int32),
-        ("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32),
-        ("in_mode", ctypes.c_int32),
-        ("in_transform", ctypes.c_int32),
-        ("kh", ctypes.c_int32), ("kw", ctypes.c_int32),
-        ("stride_h", ctypes.c_int32), ("stride_w", ctypes.c_int32),
-        ("pad_top", ctypes.c_int32), ("pad_left", ctypes.c_int32),
-        ("out_h", ctypes.c_int32), ("out_w", ctypes.c_int32),
-        ("dst", ctypes.c_void_p),
-        ("out_channels", ctypes.c_int32),
-        ("dst_total_channels", ctypes.c_int32), ("dst_channel_offset", ctypes.c_int32),
-        ("dst_plane_h", ctypes.c_int32), ("dst_plane_w", ctypes.c_int32),
-        ("out_step_h", ctypes.c_int32), ("out_step_w", ctypes.c_int32),
-        ("out_off_h", ctypes.c_int32), ("out_off_w", ctypes.c_int32),
-        ("packed_weights", ctypes.c_void_p),
-        ("bias", ctypes.c_void_p),
-        ("residual", ctypes.c_void_p),
-        ("activation", ctypes.c_int32),
-        ("act_p0", ctypes.c_float), ("act_p1", ctypes.c_float),
-        ("cout_blocks_per_wg", ctypes.c_int32),
-        ("pixel_blocks_per_wave", ctypes.c_int32),
-        ("chunk_channels", ctypes.c_int32),
-        ("split_k", ctypes.c_int32),
-        ("workspace", ctypes.c_void_p),
-        ("num_phases", ctypes.c_int32),
-        ("phase_weights", ctypes.c_void_p * 4),
-        ("phase_pad_top", ctypes.c_int32 * 4), ("phase_pad_left", ctypes.c_int32 * 4),
-        ("phase_out_off_h", ctypes.c_int32 * 4), ("phase_out_off_w", ctypes.c_int32 * 4),
-        ("waves_per_wg", ctypes.c_int32),
-        ("compute_dtype", ctypes.c_int32),
-        ("phase_kh", ctypes.c_int32 * 4), ("phase_kw", ctypes.c_int32 * 4),
-        ("k_split_waves", ctypes.c_int32),
-    ]
+_DECLARATIONS = (
+    ("enum", re.compile(r"\s*enum\s*\{([^{}]*)\}\s*;")),
+    ("struct", re.compile(r"\s*typedef\s+struct\s*(\w+)?\s*\{([^{}]*)\}\s*(\w+)\s*;")),
+    ("prototype", re.compile(r"\s*([\w\s*]+?)\b(mr_\w+)\s*\(([^(){};]*)\)\s*;")),
+)
+_DECLARATOR = re.compile(r"(.*?)(\w+)\s*(?:\[([^\]]*)\])?$", re.S)
+_EXPRESSION = re.compile(r"(?:\s*(?:0[xX][0-9a-fA-F]+|[0-9]+|MR_[A-Z0-9_]+|[-+()]|\*(?!\*)))+\s*$")      # no `**`: Python's power, no C
 
 
-class WinoDesc(ctypes.Structure):
-    """mirror of `mr_wino_desc` (include/monorec_hip.h)."""
-    _fields_ = [("src", ctypes.c_void_p * MR_MAX_SOURCES), ("src_channels", ctypes.c_int32 * MR_MAX_SOURCES), ("num_src", ctypes.c_int32),
-                ("batch", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
-                ("dst", ctypes.c_void_p), ("out_channels", ctypes.c_int32),
-                ("packed_weights", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("residual", ctypes.c_void_p),
-                ("activation", ctypes.c_int32), ("act_p0", ctypes.c_float), ("cout_blocks_per_wave", ctypes.c_int32),
-                ("variant", ctypes.c_int32),
-                ("src_row_pitch", ctypes.c_int32), ("src_plane_floats", ctypes.c_int32), ("dst_split_columns", ctypes.c_int32)]
+def parse_header(text):
+    """The C ABI a header text declares: `constants` {name: int} of its `#define`s and enum members, `structs` {C name: ctypes class},
+    `abi` / `diagnostic_abi` {entry: (restype, argtypes)} and `abi_c` {entry: (return type, [parameter types])} as C text.  Raises
+    ValueError on anything but the forms include/monorec_hip.h lists under "Conventions"."""
+    constants, structs, abi, diagnostic_abi, abi_c, host_structs = {}, {}, {}, {}, {}, set()
+
+    def evaluate(expr):
+        if not _EXPRESSION.match(expr):
+            raise ValueError(f"not an integer expression over literals, + - * ( ) and MR_ names: {expr.strip()!r}")
+        try:
+            return int(eval(re.sub(r"MR_[A-Z0-9_]+", lambda m: str(constants[m.group()]), expr), {"__builtins__": {}}))
+        except (KeyError, SyntaxError, TypeError) as e:
+            raise ValueError(f"cannot evaluate {expr.strip()!r}: {e!r}") from e
+
+    def c_type(text):
+        """`const float * const*` -> (`const float* const*`, base type name, number of `*`)"""
+        words = re.sub(r"\bconst\b", " ", text.replace("*", " ")).split()
+        if len(words) != 1 or not (words[0] in C_SCALARS or words[0] in structs or (words[0] in _POINTEES and "*" in text)):
+            raise ValueError(f"unknown type {' '.join(text.split())!r}")
+        return re.sub(r"\s*\*", "*", " ".join(text.split())), words[0], text.count("*")
+
+    def ctypes_of(text, returned=False):
+        spelled, base, stars = c_type(text)
+        if stars == 0 and base in C_SCALARS:
+            return spelled, C_SCALARS[base]
+        if returned:
+            if spelled != "const char*":
+                raise ValueError(f"unknown return type {spelled!r}")
+            return spelled, ctypes.c_char_p
+        if stars == 1 and base in host_structs:
+            return spelled, ctypes.POINTER(structs[base])
+        if stars == 0:
+            raise ValueError(f"{spelled!r} by value")
+        return spelled, ctypes.c_void_p
+
+    def declare_enum(body):
+        for member in body.split(","):
+            name, eq, value = member.partition("=")
+            if not eq or not re.fullmatch(r"MR_[A-Z0-9_]+", name.strip()):
+                raise ValueError(f"enum member {member.strip()!r} is not `MR_NAME = value`")
+            constants[name.strip()] = evaluate(value)
+
+    def declare_struct(tag, body, name):
+        if tag not in (None, name):
+            raise ValueError(f"struct tag {tag!r} of {name}: the tag is the name, or absent for a struct the device fills")
+        if tag:
+            host_structs.add(name)
+        fields = []
+        for line in filter(None, (s.strip() for s in body.split(";"))):
+            type_text = _DECLARATOR.match(line.split(",")[0]).group(1)      # `int32_t src_h, src_w;`: one type, several declarators
+            spelled, ctype = ctypes_of(type_text)
+            if "," in line and "*" in spelled:
+                raise ValueError(f"several declarators of a pointer type in one line: {line!r}")
+            for declarator in line[len(type_text):].split(","):
+                m = re.fullmatch(r"\s*(\w+)\s*(?:\[([^\]]*)\])?\s*", declarator)
+                if not m:
+                    raise ValueError(f"cannot read the field declarator {declarator.strip()!r} of {name}")
+                fields.append((m.group(1), ctype if m.group(2) is None else ctype * evaluate(m.group(2))))
+        cls = "".join(w.capitalize() for w in name[len("mr_"):].split("_"))
+        structs[name] = type(cls, (ctypes.Structure,), {"_fields_": fields, "__doc__": f"`{name}` of include/monorec_hip.h"})
+
+    def declare_prototype(ret, name, params, table):
+        ret_c, restype = ctypes_of(ret, returned=True)
+        types_c, argtypes = [], []
+        if params.strip() != "void":
+            for param in params.split(","):
+                m = _DECLARATOR.match(param.strip())
+                if m.group(3) is not None:
+                    raise ValueError(f"array parameter {param.strip()!r} of {name}")
+                spelled, ctype = ctypes_of(m.group(1))
+                types_c.append(spelled)
+                argtypes.append(ctype)
+        table[name] = (restype, argtypes)
+        abi_c[name] = (ret_c, types_c)
+
+    def declare(pending, table):
+        while pending.strip():
+            for kind, pattern in _DECLARATIONS:
+                m = pattern.match(pending)
+                if m:
+                    break
+            else:
+                raise ValueError(f"cannot read the declaration {' '.join(pending.split())[:120]!r}")
+            if kind == "enum":
+                declare_enum(m.group(1))
+            elif kind == "struct":
+                declare_struct(m.group(1), m.group(2), m.group(3))
+            else:
+                declare_prototype(m.group(1), m.group(2), m.group(3), table)
+            pending = pending[m.end():]
+
+    text = re.sub(r"/\*.*?\*/", lambda m: "\n" * m.group().count("\n"), text, flags=re.S)      # comments go, line numbers stay
+    open_ifs, pending = [], ""
+    for number, line in enumerate(text.split("\n"), 1):
+        try:
+            line = line.strip()
+            if not line.startswith("#"):
+                if "__cplusplus" in open_ifs:
+                    if line not in ("", 'extern "C" {', "}"):
+                        raise ValueError(f"cannot read {line!r}")
+                    continue
+                pending += line + "\n"
+                if pending.count("{") == pending.count("}") and line.endswith(";"):
+                    declare(pending, diagnostic_abi if "MR_DIAGNOSTIC_LIBRARY" in open_ifs else abi)
+                    pending = ""
+                continue
+            if pending.strip():
+                raise ValueError(f"cannot read the declaration {' '.join(pending.split())[:120]!r}")
+            directive, _, rest = line[1:].strip().partition(" ")
+            rest = rest.strip()
+            if directive in ("ifdef", "ifndef"):
+                # the include guard, `#ifdef __cplusplus`, `#ifdef MR_DIAGNOSTIC_LIBRARY`, and `#ifndef MR_NAME` around a default
+                if (directive, rest) not in (("ifndef", "MONOREC_HIP_H"), ("ifdef", "__cplusplus"), ("ifdef", "MR_DIAGNOSTIC_LIBRARY")) \
+                        and not (directive == "ifndef" and re.fullmatch(r"MR_[A-Z0-9_]+", rest) and rest not in constants):
+                    raise ValueError(f"unknown condition {line!r}")
+                open_ifs.append(rest)
+            elif directive == "endif" and open_ifs and not rest:
+                open_ifs.pop()
+            elif directive == "define":
+                name, expr = (rest.split(None, 1) + [""])[:2]
+                if name == "MONOREC_HIP_H" and not expr:
+                    continue
+                if not re.fullmatch(r"MR_[A-Z0-9_]+", name) or name in constants:
+                    raise ValueError(f"cannot read {line!r}")
+                constants[name] = evaluate(expr)
+            elif not (directive == "include" and rest in ("<stddef.h>", "<stdint.h>")):
+                raise ValueError(f"unknown directive {line!r}")
+        except ValueError as e:
+            raise ValueError(f"line {number}: {e}") from None
+    if pending.strip() or open_ifs:
+        raise ValueError(f"unfinished at the end: {' '.join(pending.split())[:120]!r} {open_ifs}")
+    return types.SimpleNamespace(constants=constants, structs=structs, abi=abi, diagnostic_abi=diagnostic_abi, abi_c=abi_c)
 
 
-LAYOUT_F32_NCHW, LAYOUT_BF16_B8 = 0, 1
+try:
+    with open(HEADER_PATH) as _f:
+        HEADER = parse_header(_f.read())
+except OSError as _e:
+    raise RuntimeError(f"{HEADER_PATH} not found: monorec_amd reads the C ABI of libmonorec_hip.so from this header and does not "
+                       "work without it") from _e
+except ValueError as _e:
+    raise RuntimeError(f"{HEADER_PATH}, {_e}: not a declaration form the binding reads (the header's Conventions list them)") from _e
 
-
-class B8ConvDesc(ctypes.Structure):
-    """mirror of `mr_b8_conv_desc` (include/monorec_hip.h)."""
-    _fields_ = [("src", ctypes.c_void_p * MR_MAX_SOURCES), ("src_channels", ctypes.c_int32 * MR_MAX_SOURCES), ("src_layout", ctypes.c_int32 * MR_MAX_SOURCES),
-                ("num_src", ctypes.c_int32), ("batch", ctypes.c_int32), ("src_h", ctypes.c_int32), ("src_w", ctypes.c_int32),
-                ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("stride_h", ctypes.c_int32), ("stride_w", ctypes.c_int32),
-                ("out_h", ctypes.c_int32), ("out_w", ctypes.c_int32),
-                ("dst", ctypes.c_void_p), ("dst_layout", ctypes.c_int32), ("out_channels", ctypes.c_int32),
-                ("dst_plane_h", ctypes.c_int32), ("dst_plane_w", ctypes.c_int32), ("out_step_h", ctypes.c_int32), ("out_step_w", ctypes.c_int32),
-                ("bias", ctypes.c_void_p), ("activation", ctypes.c_int32), ("act_p0", ctypes.c_float),
-                ("cout_blocks_per_wg", ctypes.c_int32), ("pixel_blocks_per_wave", ctypes.c_int32), ("waves_per_wg", ctypes.c_int32),
-                ("num_phases", ctypes.c_int32),
-                ("phase_weights", ctypes.c_void_p * 4), ("phase_kh", ctypes.c_int32 * 4), ("phase_kw", ctypes.c_int32 * 4),
-                ("phase_pad_top", ctypes.c_int32 * 4), ("phase_pad_left", ctypes.c_int32 * 4),
-                ("phase_out_off_h", ctypes.c_int32 * 4), ("phase_out_off_w", ctypes.c_int32 * 4)]
-
-
-MR_MAX_COPY_SEGMENTS = 24
-MR_ABI_VERSION = 24            # include/monorec_hip.h
-
-
-class CopySegment(ctypes.Structure):
-    """mirror of `mr_copy_segment` (include/monorec_hip.h)."""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("bytes", ctypes.c_int64)]
-
-
-MR_TSDF_MAX_FRAMES = 8
-MR_TSDF_TILE = (32, 8, 4)      # MR_TSDF_TILE_X / _Y / _Z: voxels of one workgroup of mr_tsdf_integrate_f32, the unit of its culling
-
-
-class TsdfView(ctypes.Structure):
-    """mirror of `mr_tsdf_view` (include/monorec_hip.h)."""
-    _fields_ = [("m", ctypes.c_float * 12), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
-                ("depth_cm", ctypes.c_void_p), ("colour", ctypes.c_void_p)]
-
-
-MR_CONSISTENCY_MAX_VIEWS = 8
-
-
-class ConsistencyView(ctypes.Structure):
-    """mirror of `mr_consistency_view` (include/monorec_hip.h): m is neighbour camera <- reference camera, back its inverse."""
-    _fields_ = [("m", ctypes.c_float * 12), ("back", ctypes.c_float * 12), ("fx", ctypes.c_float), ("fy", ctypes.c_float),
-                ("cx", ctypes.c_float), ("cy", ctypes.c_float), ("inv_depth", ctypes.c_void_p)]
-
-
-MR_TSDF_BLOCK = 8            # edge of one block of the block-sparse volume (mr_tsdf_sparse_*_f32) in voxels
-MR_TSDF_BRICK = 4              # edge of one brick of mr_tsdf_skip_grid_u8 in voxels
-MR_TSDF_CLUSTER_TILE = (32, 8, 8)    # MR_TSDF_CLUSTER_TILE_X / _Y / _Z: voxels of one workgroup of mr_tsdf_mesh_cluster_vertices_f32
+ABI = HEADER.abi                          # every symbol include/monorec_hip.h declares: (restype, argtypes)
+DIAGNOSTIC_ABI = HEADER.diagnostic_abi    # under MR_DIAGNOSTIC_LIBRARY there (python -m monorec_amd.build --timeline): typed when present, never required
+ABI_C = HEADER.abi_c                      # both, as the C text of the return and parameter types
+globals().update(HEADER.constants)                                        # MR_ABI_VERSION, MR_MAX_SOURCES, ... under their header names
+globals().update({c.__name__: c for c in HEADER.structs.values()})        # mr_conv_desc -> ConvDesc, mr_tsdf_ray_view -> TsdfRayView, ...
+globals().update({name[len("MR_"):]: value for name, value in HEADER.constants.items()      # the families used without the prefix
+                  if name.startswith(("MR_ACT_", "MR_IN_", "MR_TF_", "MR_LAYOUT_", "MR_LAUNCH_", "MR_CV_FAMILY_", "MR_CV_FUSE_"))})
+MR_TSDF_TILE = tuple(HEADER.constants["MR_TSDF_TILE_" + a] for a in "XYZ")                    # voxels of one workgroup of mr_tsdf_integrate_f32
+MR_TSDF_CLUSTER_TILE = tuple(HEADER.constants["MR_TSDF_CLUSTER_TILE_" + a] for a in "XYZ")    # ... of mr_tsdf_mesh_cluster_vertices_f32
 MR_TSDF_MESH_CELLS = (1, 2, 4, 8)    # cluster edges of the mesh entries: the divisors of MR_TSDF_BLOCK (1: the full mesh)
-
-
-class TsdfRayView(ctypes.Structure):
-    """mirror of `mr_tsdf_ray_view` (include/monorec_hip.h): m is camera -> world."""
-    _fields_ = [("m", ctypes.c_float * 12), ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
-                ("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("colour", ctypes.c_void_p)]
-
-
-class LaunchItem(ctypes.Structure):
-    """mirror of `mr_launch_item` (include/monorec_hip.h)."""
-    _fields_ = [("kind", ctypes.c_int32), ("arg", ctypes.c_int32), ("desc", ctypes.c_void_p)]
-
-
-LAUNCH_CONV2D, LAUNCH_WINO3X3, LAUNCH_WINO_T, LAUNCH_WINO_1D, LAUNCH_UPCONV, LAUNCH_COOKTOOM_1D, LAUNCH_WINO44, LAUNCH_CONV_B8, LAUNCH_WINO44S, LAUNCH_WINO44W = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
-
-
-class HeadDesc(ctypes.Structure):
-    """mirror of `mr_head_desc` (include/monorec_hip.h)."""
-    _fields_ = [("src", ctypes.c_void_p), ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("dst", ctypes.c_void_p),
-                ("batch", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32)]
-
-
-MR_MAX_HEADS = 4
-
-CV_FAMILY_MARCH, CV_FAMILY_TILED, CV_FAMILY_PATCH = 1, 2, 3
-CV_FUSE_REG, CV_FUSE_GENERIC = 1, 2
-
-
-class CvLaunch(ctypes.Structure):
-    """mirror of `mr_cv_launch` (include/monorec_hip.h): what mr_cost_volume_launch_query reports."""
-    _fields_ = [("status", ctypes.c_int32), ("family", ctypes.c_int32), ("mode", ctypes.c_int32), ("opt", ctypes.c_int32),
-                ("sad_grid", ctypes.c_int32 * 3), ("sad_block", ctypes.c_int32),
-                ("dp", ctypes.c_int32), ("pixd", ctypes.c_int32), ("kfs", ctypes.c_int32), ("fd", ctypes.c_int32), ("relaxed", ctypes.c_int32),
-                ("strips", ctypes.c_int32), ("pitch", ctypes.c_int32), ("ty", ctypes.c_int32), ("ysegs", ctypes.c_int32), ("npairs", ctypes.c_int32),
-                ("kf_prepass", ctypes.c_int32), ("kf_grid", ctypes.c_int32 * 2),
-                ("tile_w", ctypes.c_int32), ("tile_h", ctypes.c_int32), ("tiles_x", ctypes.c_int32), ("tiles", ctypes.c_int32),
-                ("nchunk", ctypes.c_int32), ("dchunk", ctypes.c_int32), ("radius", ctypes.c_int32), ("lds_bytes", ctypes.c_int32),
-                ("flag_memset", ctypes.c_int32),
-                ("fuse", ctypes.c_int32), ("fuse_depths", ctypes.c_int32), ("fuse_b8", ctypes.c_int32), ("fuse_lean", ctypes.c_int32),
-                ("fuse_pflag", ctypes.c_int32), ("fuse_grid", ctypes.c_int32 * 2)]
-
-# every symbol include/monorec_hip.h declares: (restype, argtypes)
-ABI = {
-    "mr_conv_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
-                                                       ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "mr_conv_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_void_p]),
-    "mr_conv_packed_weight_floats_bf16": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
-                                                            ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "mr_conv_packed_weight_floats_bf16x3": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
-                                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "mr_conv_pack_weights_bf16x3": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
-                                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.c_void_p]),
-    "mr_conv_pack_weights_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
-                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_void_p]),
-    "mr_conv2d_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(ConvDesc)]),
-    "mr_conv2d_f32": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.c_void_p]),
-    "mr_wino_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32]),
-    "mr_wino_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_void_p]),
-    "mr_conv3x3_winograd_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(WinoDesc)]),
-    "mr_conv3x3_winograd_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_void_p]),
-    "mr_wino_t_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32]),
-    "mr_wino_t_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
-                                                  ctypes.c_int32, ctypes.c_void_p]),
-    "mr_convt4x4s2_winograd_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(WinoDesc)]),
-    "mr_convt4x4s2_winograd_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_void_p]),
-    "mr_cost_volume_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                          ctypes.c_float, _c_float_p,
-                                          ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
-    "mr_cost_volume_mode_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                               ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                               ctypes.c_float, _c_float_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                               ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
-    "mr_cost_volume_relaxed_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                  ctypes.c_float, _c_float_p, ctypes.c_int32, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
-    "mr_cost_volume_tiled_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_float, _c_float_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32,
-                                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
-    "mr_cost_volume_patch_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_float, _c_float_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
-    "mr_maxpool3x3s2_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                           ctypes.c_int32, ctypes.c_void_p]),
-    "mr_maxpool2x2_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
-                                         ctypes.c_int32, ctypes.c_void_p]),
-    "mr_resnet_normalize_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    "mr_exact_const_division": (ctypes.c_int, [ctypes.c_float]),
-    "mr_cost_volume_launch_query": (ctypes.c_int, [ctypes.c_int32] * 13 + [ctypes.POINTER(CvLaunch)]),
-    "mr_run_launches": (ctypes.c_int, [ctypes.POINTER(LaunchItem), ctypes.c_int32, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32)]),
-    "mr_upconv_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    "mr_upconv2x2_winograd_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_void_p]),
-    "mr_wino1d_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32]),
-    "mr_wino1d_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    "mr_conv1d3_winograd_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(WinoDesc)]),
-    "mr_conv1d3_winograd_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_int32, ctypes.c_void_p]),
-    "mr_cooktoom1d_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "mr_cooktoom1d_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    "mr_conv1d_cooktoom_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(WinoDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "mr_conv1d_cooktoom_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    "mr_wino_t_packed_weight_floats_tail": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
-    "mr_wino_t_pack_weights_tail_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_void_p]),
-    "mr_wino_packed_weight_floats_tail": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
-    "mr_wino_pack_weights_tail_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_void_p]),
-    "mr_b8_packed_weight_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "mr_b8_pack_weights": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                          ctypes.c_int32, ctypes.c_void_p]),
-    "mr_conv2d_b8_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(B8ConvDesc)]),
-    "mr_conv2d_b8": (ctypes.c_int, [ctypes.POINTER(B8ConvDesc), ctypes.c_void_p]),
-    "mr_pool2x2_framemax_b8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32,
-                                              ctypes.c_int32, ctypes.c_void_p]),
-    "mr_max_over_frames_b8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]),
-    "mr_f32_nchw_to_b8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]),
-    "mr_b8_to_f32_nchw": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]),
-    "mr_cost_volume_b8_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _c_float_p,
-                                             ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
-                                             ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
-    "mr_cost_volume_b8_lean_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _c_float_p,
-                                                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
-                                                  ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
-    "mr_mask_classifier_b8_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_gather_small_f32": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_copy_segments": (ctypes.c_int, [ctypes.POINTER(CopySegment), ctypes.c_int32, ctypes.c_void_p]),
-    "mr_max_over_frames_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
-                                              ctypes.c_void_p]),
-    "mr_nonzero_mean_over_frames_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64,
-                                                       ctypes.c_void_p]),
-    "mr_pool2x2_framemax_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                               ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    "mr_apply_mask_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                         ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p]),
-    "mr_mask_classifier_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                              ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
-    "mr_depth_heads_f32": (ctypes.c_int, [ctypes.POINTER(HeadDesc), ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
-    "mr_sparse_metric_sums_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_float,
-                                                 ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_median_select_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "mr_median_select_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_median_stage_scales_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p]),
-    "mr_metric_stage_sums_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_float, ctypes.c_void_p, ctypes.c_int32,
-                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_static_mask_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                          ctypes.c_float, ctypes.c_int32, ctypes.c_void_p]),
-    "mr_pointcloud_append_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                                ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                                ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_frame_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
-                                         ctypes.c_float, ctypes.POINTER(ctypes.c_int32), ctypes.c_float, ctypes.c_float,
-                                         ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_depth_consistency_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                                ctypes.POINTER(ConsistencyView), ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_int32,
-                                                ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_volume_reset_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                ctypes.c_void_p]),
-    "mr_tsdf_integrate_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                             _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.POINTER(TsdfView), ctypes.c_int32,
-                                             ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p]),
-    "mr_tsdf_extract_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                           _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                           ctypes.c_void_p]),
-    "mr_tsdf_mesh_vertices_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                 _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_mesh_triangles_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_skip_grid_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float,
-                                            ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_render_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                          _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.POINTER(TsdfRayView), ctypes.c_int32,
-                                          ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]),
-    "mr_tsdf_sparse_integrate_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, _c_float_p, ctypes.c_float,
-                                                    ctypes.c_float, ctypes.c_float, ctypes.POINTER(TsdfView), ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.c_int32, ctypes.c_void_p]),
-    "mr_tsdf_sparse_extract_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_float_p, ctypes.c_float, ctypes.c_float,
-                                                  ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_sparse_gather_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_sparse_render_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
-                                                 ctypes.c_void_p, ctypes.c_int64, _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.POINTER(TsdfRayView),
-                                                 ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                                 ctypes.c_void_p]),
-    "mr_tsdf_sparse_mesh_vertices_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_float_p, ctypes.c_float,
-                                                        ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
-                                                        ctypes.c_void_p]),
-    "mr_tsdf_sparse_mesh_triangles_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p,
-                                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_mesh_vertices_normals_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                         ctypes.c_int32, _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64,
-                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_mesh_cluster_vertices_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
-                                                         ctypes.c_int32, _c_float_p, ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p,
-                                                         ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_mesh_cluster_triangles_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                          ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
-                                                          ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_sparse_mesh_vertices_normals_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_float_p,
-                                                                ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
-                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_sparse_mesh_cluster_vertices_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, _c_float_p,
-                                                                ctypes.c_float, ctypes.c_float, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
-                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_tsdf_sparse_mesh_cluster_triangles_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_int32,
-                                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_resample_ksize_bilinear":(ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
-    "mr_resample_coeffs_bilinear": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                   ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_preprocess_image_u8_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                  ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                  ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_preprocess_image_u8_lut_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                      ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
-                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                      ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_preprocess_image_u8_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
-                                                 ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
-                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    "mr_unpack_frame_u8_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
-                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_scatter_sparse_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
-                                             ctypes.c_void_p]),
-    "mr_lidar_inverse_depth_u16_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32),
-                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_dso_inverse_depth_u16_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.c_double, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int32,
-                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "mr_wino44_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
-    "mr_wino44_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_void_p]),
-    "mr_conv3x3_winograd44_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(WinoDesc)]),
-    "mr_conv3x3_winograd44_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_void_p]),
-    "mr_wino44s_packed_weight_floats": (ctypes.c_size_t, [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
-    "mr_wino44s_pack_weights_f32": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_void_p]),
-    "mr_conv3x3_winograd44s_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(WinoDesc)]),
-    "mr_conv3x3_winograd44s_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_void_p]),
-    "mr_conv3x3_winograd44w_lds_bytes": (ctypes.c_int64, [ctypes.POINTER(WinoDesc)]),
-    "mr_conv3x3_winograd44w_f32": (ctypes.c_int, [ctypes.POINTER(WinoDesc), ctypes.c_void_p]),
-    "mr_abi_version": (ctypes.c_int, []),
-    "mr_error_string": (ctypes.c_char_p, [ctypes.c_int]),
-}
-
-# exported by the diagnostic library only (python -m monorec_amd.build --timeline; include/monorec_hip.h under MR_DIAGNOSTIC_LIBRARY): typed
-# when present, never required
-DIAGNOSTIC_ABI = {
-    "mr_diagnostic_forms": (ctypes.c_int, []),      # bit 0: F(2,7) instantiations present
-}
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmonorec_hip.so")
 _lib = None

@@ -38,32 +38,153 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert b"LDS" in hip_lib.mr_error_string(-3)
 
 
-def test_conv_desc_layout_matches_the_c_struct():
-    fields = ", ".join(f'offsetof(mr_conv_desc, {n})' for n, _ in _lib.ConvDesc._fields_)
-    src = f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\nint main(){{ size_t o[] = {{{fields}}};' \
-          'printf("%zu", sizeof(mr_conv_desc)); for (unsigned i = 0; i < sizeof(o)/sizeof(o[0]); ++i) printf(" %zu", o[i]); return 0; }'
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "t.c"), os.path.join(d, "t")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", c, "-o", exe], check=True)
-        vals = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    assert vals[0] == ctypes.sizeof(_lib.ConvDesc)
-    assert vals[1:] == [getattr(_lib.ConvDesc, n).offset for n, _ in _lib.ConvDesc._fields_]
+def _c_program_output(main_body, tmp_path):
+    """stdout of a C99 program, built by gcc, that includes the header and runs `main_body`"""
+    c, exe = str(tmp_path / "t.c"), str(tmp_path / "t")
+    open(c, "w").write(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\nint main(void) {{ {main_body} return 0; }}\n')
+    subprocess.run(["gcc", "-std=c99", c, "-o", exe], check=True)
+    return subprocess.run([exe], check=True, capture_output=True, text=True).stdout
 
 
-def test_wino_desc_layout_matches_the_c_struct():
-    """mr_wino_desc grew three fields in ABI 18 (strided source views, column-split destination: the stride-2 layers): ctypes mirror == C layout."""
-    fields = ", ".join(f'offsetof(mr_wino_desc, {n})' for n, _ in _lib.WinoDesc._fields_)
-    src = f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\nint main(){{ size_t o[] = {{{fields}}};' \
-          'printf("%zu", sizeof(mr_wino_desc)); for (unsigned i = 0; i < sizeof(o)/sizeof(o[0]); ++i) printf(" %zu", o[i]); return 0; }'
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "t.c"), os.path.join(d, "t")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", c, "-o", exe], check=True)
-        vals = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    assert vals[0] == ctypes.sizeof(_lib.WinoDesc)
-    assert vals[1:] == [getattr(_lib.WinoDesc, n).offset for n, _ in _lib.WinoDesc._fields_]
-    assert [n for n, _ in _lib.WinoDesc._fields_][-3:] == ["src_row_pitch", "src_plane_floats", "dst_split_columns"]
+HEADER_STRUCTS = re.findall(r"^\}\s*(mr_\w+)\s*;", open(HEADER).read(), flags=re.M)      # every `typedef struct ... } mr_name;`
+
+
+@pytest.mark.parametrize("name", HEADER_STRUCTS)
+def test_struct_layout_matches_the_c_struct(name, tmp_path):
+    """The ctypes class the binding builds for every struct of the header against gcc's sizeof, offsetof and member sizes
+    (mr_wino_desc grew three fields in ABI 18 - strided source views, column-split destination: the stride-2 layers - at its end)."""
+    assert HEADER_STRUCTS and set(HEADER_STRUCTS) == set(_lib.HEADER.structs)
+    cls = getattr(_lib, "".join(w.capitalize() for w in name[3:].split("_")))
+    assert cls is _lib.HEADER.structs[name] and issubclass(cls, ctypes.Structure)
+    fields = ", ".join(f"offsetof({name}, {n}), sizeof((({name}*)0)->{n})" for n, _ in cls._fields_)
+    vals = [int(v) for v in _c_program_output(
+        f'size_t o[] = {{{fields}}}; printf("%zu", sizeof({name})); for (unsigned i = 0; i < sizeof(o)/sizeof(o[0]); ++i) printf(" %zu", o[i]);',
+        tmp_path).split()]
+    assert vals[0] == ctypes.sizeof(cls)
+    assert vals[1::2] == [getattr(cls, n).offset for n, _ in cls._fields_]
+    assert vals[2::2] == [getattr(cls, n).size for n, _ in cls._fields_]
+    if name == "mr_wino_desc":
+        assert [n for n, _ in _lib.WinoDesc._fields_][-3:] == ["src_row_pitch", "src_plane_floats", "dst_split_columns"]
+
+
+SHORT_FAMILIES = ("ACT_", "IN_", "TF_", "LAYOUT_", "LAUNCH_", "CV_FAMILY_", "CV_FUSE_")      # exported without the MR_ prefix as well
+
+
+def test_constants_equal_what_the_c_compiler_sees(tmp_path):
+    """Every integer #define and enum member of the header, printed by a C program, against the binding's value; the short aliases and
+    the two tile tuples against their MR_ names."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    names = [n for n in re.findall(r"^#define\s+(MR_\w+)[ \t]+\S", text, flags=re.M)]
+    names += [n for body in re.findall(r"\benum\s*\{(.*?)\}", text, flags=re.S) for n in re.findall(r"(MR_\w+)\s*=", body)]
+    assert names and len(names) == len(set(names))
+    out = _c_program_output(" ".join(f'printf("{n} %lld\\n", (long long)({n}));' for n in names), tmp_path)
+    seen = {n: int(v) for n, v in (line.split() for line in out.splitlines())}
+    assert seen == _lib.HEADER.constants and list(seen) == names
+    for n, v in seen.items():
+        assert getattr(_lib, n) == v and type(getattr(_lib, n)) is int, n
+    short = [n[3:] for n in names if n[3:].startswith(SHORT_FAMILIES)]
+    assert {"ACT_ABS_TANH_AFFINE", "IN_MAXPOOL2", "TF_RESNET_NORM", "LAYOUT_BF16_B8", "LAUNCH_WINO44W",
+                                 "CV_FAMILY_PATCH", "CV_FUSE_GENERIC"} <= set(short)
+    for n in short:
+        assert getattr(_lib, n) == seen["MR_" + n], n
+    assert _lib.MR_TSDF_TILE == tuple(seen["MR_TSDF_TILE_" + a] for a in "XYZ")
+    assert _lib.MR_TSDF_CLUSTER_TILE == tuple(seen["MR_TSDF_CLUSTER_TILE_" + a] for a in "XYZ")
+    assert all(_lib.MR_TSDF_BLOCK % c == 0 for c in _lib.MR_TSDF_MESH_CELLS)
+
+
+def test_prototypes_equal_what_the_c_compiler_sees(tmp_path):
+    """Every function of the header declared a second time from the C text the binding kept (_lib.ABI_C): gcc rejects a redeclaration
+    with conflicting types, so the file compiles only if return type, arity, order and type of every parameter are the header's - and does
+    not compile with one int32_t turned into int64_t.  Then the ctypes side: each C type text maps to its class by the one table, whose
+    scalars have gcc's sizes."""
+    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
+               "size_t": ctypes.c_size_t}
+    assert _lib.C_SCALARS == scalars
+    assert _lib.ABI and _lib.DIAGNOSTIC_ABI and not set(_lib.ABI) & set(_lib.DIAGNOSTIC_ABI)
+    assert set(_lib.ABI_C) == set(_lib.ABI) | set(_lib.DIAGNOSTIC_ABI)
+
+    def source(abi_c):
+        return f'#include "{HEADER}"\n' + "".join(f"{ret} {name}({', '.join(params) or 'void'});\n" for name, (ret, params) in abi_c.items())
+
+    def compiles(text):
+        c = str(tmp_path / "protos.c")
+        open(c, "w").write(text)
+        return subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-DMR_DIAGNOSTIC_LIBRARY", c],
+                              capture_output=True, text=True)
+    good = compiles(source(_lib.ABI_C))
+    assert good.returncode == 0, good.stderr[-2000:]
+    ret, params = _lib.ABI_C["mr_maxpool3x3s2_f32"]
+    assert params[3] == "int32_t"
+    wrong = compiles(source({**_lib.ABI_C, "mr_maxpool3x3s2_f32": (ret, params[:3] + ["int64_t"] + params[4:])}))
+    assert wrong.returncode != 0 and "conflicting types" in wrong.stderr and "mr_maxpool3x3s2_f32" in wrong.stderr
+
+    # gcc above is the judge of what the binding read.  What follows only pins the rule by which a type it read becomes a ctypes class - the
+    # table of the binding's docstring, said a second time - so that an argument cannot be typed otherwise than its C text says.
+    tagless = re.findall(r"typedef\s+struct\s*\{[^{}]*\}\s*(mr_\w+)\s*;", re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S))
+    assert "mr_median_stats" in tagless
+
+    def mapped(text, returned=False):
+        if text in scalars:
+            return scalars[text]
+        assert text.endswith("*"), text
+        if returned:
+            assert text == "const char*"
+            return ctypes.c_char_p
+        base = text.replace("const", "").replace("*", "").strip()
+        if text.count("*") == 1 and base in _lib.HEADER.structs and base not in tagless:      # without a tag: the device fills it, a device address
+            return ctypes.POINTER(_lib.HEADER.structs[base])
+        return ctypes.c_void_p
+    for name, (ret, params) in _lib.ABI_C.items():
+        restype, argtypes = (_lib.ABI.get(name) or _lib.DIAGNOSTIC_ABI[name])
+        assert restype is mapped(ret, returned=True) and list(argtypes) == [mapped(p) for p in params], name
+    sizes = [int(v) for v in _c_program_output(" ".join(f'printf("%zu ", sizeof({t}));' for t in list(scalars) + ["void*", "const char*"]),
+                                               tmp_path).split()]
+    assert sizes == [ctypes.sizeof(t) for t in list(scalars.values()) + [ctypes.c_void_p, ctypes.c_char_p]]
+
+
+GOOD_HEADER = """/* a comment */
+#define MR_N (2 + 0x1)
+enum { MR_A = 0, MR_B = MR_N * 2 };
+typedef struct mr_thing { const float* src[MR_N]; int32_t h, w[MR_B]; } mr_thing;
+typedef struct { int32_t count; float median; } mr_stats;
+int mr_run(const mr_thing* thing, const float* const* planes, int64_t count, const mr_stats* stats, void* stream);
+#ifdef MR_DIAGNOSTIC_LIBRARY
+const char* mr_name(void);
+#endif
+"""
+
+
+@pytest.mark.parametrize("good,bad", [
+    ("int64_t count", "long count"),                                 # an unknown type
+    ("int32_t h,", "unsigned h,"),
+    ("int mr_run", "static int mr_count;\nint mr_run"),              # a top-level line that is none of the known declarations
+    ("#ifdef MR_DIAGNOSTIC_LIBRARY", "#if 1"),
+    ("(2 + 0x1)", "(1 << 2)"),                                       # a #define whose text leaves the alphabet of integer expressions
+    ("(2 + 0x1)", "sizeof(int)"),
+    ("(2 + 0x1)", "__import__('os').getpid()"),
+    ("(2 + 0x1)", "(2 ** 3)"),                                       # every character allowed, but Python's power operator and no C
+    ("struct mr_thing {", "struct mr_other {"),                      # a tag that is not the name
+], ids=["type-long", "type-unsigned", "top-level-variable", "directive-if", "define-shift", "define-sizeof", "define-call", "define-power",
+        "struct-tag"])
+def test_header_parser_raises_on_what_it_does_not_know(good, bad):
+    h = _lib.parse_header(GOOD_HEADER)
+    assert h.constants == {"MR_N": 3, "MR_A": 0, "MR_B": 6} and list(h.abi) == ["mr_run"] and list(h.diagnostic_abi) == ["mr_name"]
+    assert [(n, ctypes.sizeof(t)) for n, t in h.structs["mr_thing"]._fields_] == [("src", 24), ("h", 4), ("w", 24)]
+    assert h.abi["mr_run"] == (ctypes.c_int, [ctypes.POINTER(h.structs["mr_thing"]), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p])
+    assert [n for n, _ in h.structs["mr_stats"]._fields_] == ["count", "median"]
+    assert good in GOOD_HEADER
+    with pytest.raises(ValueError):
+        _lib.parse_header(GOOD_HEADER.replace(good, bad))
+
+
+def test_missing_header_raises_at_import_and_names_the_path(tmp_path):
+    import importlib.util
+    (tmp_path / "pkg").mkdir()
+    copy = tmp_path / "pkg" / "_lib.py"
+    copy.write_text(open(_lib.__file__).read())
+    spec = importlib.util.spec_from_file_location("_lib_without_header", str(copy))
+    with pytest.raises(RuntimeError, match=re.escape(os.path.join("include", "monorec_hip.h")) + " not found"):
+        spec.loader.exec_module(importlib.util.module_from_spec(spec))
 
 
 def test_bad_arguments_are_reported_not_crashed(hip_lib):
@@ -1354,19 +1475,6 @@ def test_forward_slot_avoids_uncollected_handles_of_copying_plans():
 
 
 # ------------------------------------------------------------------------------------------ bf16 MFMA path with B8 activation storage
-def test_b8_conv_desc_layout_matches_the_c_struct():
-    fields = ", ".join(f'offsetof(mr_b8_conv_desc, {n})' for n, _ in _lib.B8ConvDesc._fields_)
-    src = f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\nint main(){{ size_t o[] = {{{fields}}};' \
-          'printf("%zu", sizeof(mr_b8_conv_desc)); for (unsigned i = 0; i < sizeof(o)/sizeof(o[0]); ++i) printf(" %zu", o[i]); return 0; }'
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "t.c"), os.path.join(d, "t")
-        open(c, "w").write(src)
-        subprocess.run(["gcc", c, "-o", exe], check=True)
-        vals = [int(v) for v in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
-    assert vals[0] == ctypes.sizeof(_lib.B8ConvDesc)
-    assert vals[1:] == [getattr(_lib.B8ConvDesc, n).offset for n, _ in _lib.B8ConvDesc._fields_]
-
-
 def test_b8_weight_packing(hip_lib):
     """mr_b8_pack_weights: the bf16 A-fragment stream of csrc/conv_b8.hip - [cout group of 16 mb][chunk of 32 channels, source-major][tap]
     [cout block][64 lanes][8]; lane l = (cout l & 15, channel block l >> 4 of the chunk), element e = channel 8 (l >> 4) + e of the chunk;
